@@ -7,7 +7,11 @@ project (predict) -> updateWeights (contact model against the MLS map) -> normal
 stratified resample, forced every step (minEffective = N + 1, measurement gate forced).
 Workload at N=1: BASELINE configs[2] -- 4M particles, 100 x 100 m MLS map @ 0.1 m.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--particles P] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own: the per-kernel HIP-event pass (kernel_ms, roofline) and the CPU baseline.
+--dump-outputs DIR writes the particle set the last timed step left as DIR/<name>.npy.
 
 For N > 1 launch with torch.distributed.run (one process per GPU); each rank holds
 P particles of one global filter (weak scaling).
@@ -76,7 +80,13 @@ def parse():
     ap.add_argument("--match", action="store_true",
                     help="with --local-maps: processMap(scan, match = true, update = true), the match "
                          "weighting (eslam_gpu_map_match) before every merge")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel pass (HIP events around every launch of "
+                         "a second K steps: kernel_ms, roofline) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the particle set a caller downloads, the "
+                         "step's return value and update info) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-cpu-aos", action="store_true",
                     help="skip cpu_baseline.aos, the oracle with the reference's 288-byte particle records")
     ap.add_argument("--sharded", action="store_true",
@@ -282,8 +292,35 @@ def spawn_ranks(args):
     sys.exit(0 if not bad else (bad[0] if bad[0] > 0 else 128 - bad[0]))
 
 
+DUMP_SAMPLE = 262144          # particles written by --dump-outputs (64 B each as float64 / float32 arrays)
+DUMP_SEED = 20231
+
+
+def dump_outputs(out_dir, f, updated, info):
+    """--dump-outputs: the state the last timed step left, as a caller receives it
+    (GpuFilter.download(), step()'s return value, sync()'s update info), one .npy per array.
+    Above DUMP_SAMPLE particles a fixed, seeded sample of them (sample_index holds the indices)."""
+    import numpy as np
+    pa = f.download()
+    idx = np.arange(pa.n)
+    if pa.n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pa.n, DUMP_SAMPLE, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"sample_index": idx.astype(np.float64)}
+    for name, a in pa.as_dict().items():
+        arrays[name] = a[idx].astype(np.float64 if a.dtype == np.float64 else np.float32)
+    arrays["step_updated"] = np.array([1.0 if updated else 0.0], dtype=np.float32)
+    arrays["update_info"] = np.array([info.effective, info.weight_sum, info.floating_weight, info.max_weight,
+                                      info.data_particles, info.total_points, info.resampled, info.uniform_reset],
+                                     dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.sharded):
+        raise SystemExit("bench.py: --dump-outputs writes one GPU's whole particle set (not with --gpus > 1 / --sharded)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
     if args.local_maps:
@@ -334,7 +371,7 @@ def main():
     if args.local_maps:
         grid = S.unmapped_beyond(grid, 0.3)    # the front feet stand on cells only the scans map
         scan = S.scan_area(args.scan_patches) if args.scan_patches > 0 else S.scan_patches()
-    stream = S.step_stream(args.warmup + 2 * args.steps + 1, tilt=args.local_maps)
+    stream = S.step_stream(args.warmup + (2 if args.full else 1) * args.steps, tilt=args.local_maps)
     cfg = S.bench_config(A.default_config(), n * world)
     if args.match and not args.local_maps:
         raise SystemExit("bench.py: --match needs --local-maps (the match reads per-particle maps)")
@@ -393,48 +430,70 @@ def main():
     # timed region: K steps back to back, no per-kernel events (HIP event records between
     # the launches cost ~10 % of a step here)
     t0 = time.perf_counter()
+    updated = False
     for st in stream[args.warmup:args.warmup + args.steps]:
-        f_step(st)
+        updated = f_step(st)
     t_enq = time.perf_counter()             # the host has queued every launch (nothing waits on the GPU)
     info = f.sync()
     barrier()
     dt = time.perf_counter() - t0
-    # kernel breakdown: the next K steps of the same stream with HIP events around every
-    # launch, on the context's stream (eslam_gpu_enable_timing)
-    f.enable_timing(True)
-    barrier()
-    t1 = time.perf_counter()
-    for st in stream[args.warmup + args.steps:args.warmup + 2 * args.steps]:
-        f_step(st)
-    f.sync()
-    barrier()
-    dt_ev = time.perf_counter() - t1
-    kt = f.kernel_times()
-    f.enable_timing(False)
     if dist is not None:
         import torch
-        t = torch.tensor([dt, dt_ev], device="cuda")
+        t = torch.tensor([dt], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_ev = float(t[0].item()), float(t[1].item())
+        dt = float(t[0].item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, f, updated, info)
     total_updates = n * world * args.steps
     value = total_updates / dt / 1e6
     ms_step = dt / args.steps * 1e3
 
-    # roofline of the dominant kernel (HIP events around every launch of the timed region);
-    # per-particle maps: the map merge competes too (its write-back covers the changed stores)
-    per_kernel = {"k_project_weight": (kt["project_weight_ms"], (BYTES_K1_DELTA if args.local_maps else BYTES_K1) * n),
-                  "k_normalize_segments": (kt["normalize_scan_ms"], BYTES_K3 * n)}
-    if args.local_maps:
-        slots = window_slots(cfg.max_sensor_range, 0.1)
-        per_kernel["k_map_merge"] = (kt["map_merge_ms"], BYTES_MERGE_PARTICLE * n + BYTES_MERGE_CELL * info.map_cells_written
-                                     + BYTES_MERGE_PAGE * info.map_pages_taken
-                                     + merge_table_bytes(slots) * info.map_stores_copied)
-    dom = max(per_kernel, key=lambda k: per_kernel[k][0])
-    dom_ms, dom_launch_bytes = per_kernel[dom]
-    dom_bytes = dom_launch_bytes / n
-    achieved = dom_launch_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    workload = "local-maps" if args.local_maps else ("rough" if args.rough else "flat")
-    traffic = pmc_traffic(dom, n, args.map_cells, workload) if not sharded else None
+    def kernel_pass():
+        """--full: the kernel breakdown (the next K steps of the same stream with HIP events
+        around every launch, on the context's stream: eslam_gpu_enable_timing) and the roofline
+        of the dominant kernel it gives."""
+        f.enable_timing(True)
+        barrier()
+        t1 = time.perf_counter()
+        for st in stream[args.warmup + args.steps:args.warmup + 2 * args.steps]:
+            f_step(st)
+        f.sync()
+        barrier()
+        dt_ev = time.perf_counter() - t1
+        kt = f.kernel_times()
+        f.enable_timing(False)
+        if dist is not None:
+            import torch
+            t = torch.tensor([dt_ev], device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_ev = float(t[0].item())
+        # per-particle maps: the map merge competes too (its write-back covers the changed stores)
+        per_kernel = {"k_project_weight": (kt["project_weight_ms"], (BYTES_K1_DELTA if args.local_maps else BYTES_K1) * n),
+                      "k_normalize_segments": (kt["normalize_scan_ms"], BYTES_K3 * n)}
+        if args.local_maps:
+            slots = window_slots(cfg.max_sensor_range, 0.1)
+            per_kernel["k_map_merge"] = (kt["map_merge_ms"], BYTES_MERGE_PARTICLE * n + BYTES_MERGE_CELL * info.map_cells_written
+                                         + BYTES_MERGE_PAGE * info.map_pages_taken
+                                         + merge_table_bytes(slots) * info.map_stores_copied)
+        dom = max(per_kernel, key=lambda k: per_kernel[k][0])
+        dom_ms, dom_launch_bytes = per_kernel[dom]
+        dom_bytes = dom_launch_bytes / n
+        achieved = dom_launch_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        workload = "local-maps" if args.local_maps else ("rough" if args.rough else "flat")
+        traffic = pmc_traffic(dom, n, args.map_cells, workload) if not sharded else None
+        return {
+            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                         "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_detail": traffic,
+                         "algorithmic_bytes_per_particle": round(dom_bytes, 2),
+                         "avg_launch_ms": round(dom_ms, 5)},
+            "kernel_ms": {k: round(v, 5) for k, v in kt.items()},
+            "kernel_ms_note": "HIP events around every launch on the context stream, over a second pass of "
+                              "the same K steps (ms_per_step with events: %.4f); single-GPU update steps fold the finalize "
+                              "into k_normalize_segments (block 0), so finalize_ms times an empty region there"
+                              % (dt_ev / args.steps * 1e3),
+        }
+
     result = {
         "metric": "M particle-updates/s (predict+weight+resample) @ 1/2/4/8 MI355X",
         "value": round(value, 3),
@@ -464,17 +523,7 @@ def main():
                    "particles_per_gpu": n, "global_particles": n * world,
                    "parallelism": "dp%d (particle shards%s)" % (world, (", sharded path, %s exchanges" % args.comm)
                                                                    if sharded else "")},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_detail": traffic,
-                     "algorithmic_bytes_per_particle": round(dom_bytes, 2),
-                     "avg_launch_ms": round(dom_ms, 5)},
-        "kernel_ms": {k: round(v, 5) for k, v in kt.items()},
         "host_enqueue_ms_per_step": round((t_enq - t0) / args.steps * 1e3, 4),
-        "kernel_ms_note": "HIP events around every launch on the context stream, over a second pass of "
-                          "the same K steps (ms_per_step with events: %.4f); single-GPU update steps fold the finalize "
-                          "into k_normalize_segments (block 0), so finalize_ms times an empty region there"
-                          % (dt_ev / args.steps * 1e3),
         "step_roofline_frac": round(BYTES_STEP * n * world / (dt / args.steps) / 1e9 / (HBM_PEAK_GBS * world), 4),
         "step_roofline_note": "%d B per particle-update: the fused step's algorithmic bytes (K1 %d + K3 %d); the "
                               "reference algorithm's unfused passes would move %d B (fraction %.4f)"
@@ -497,7 +546,9 @@ def main():
            if args.local_maps else {}),
         "build_id": eslam_amd.build_id(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result.update(kernel_pass())
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, grid, cfg.flags & A.FLAG_PARTICLE_MAPS, scan)
     sys.stdout.flush()
     os.dup2(json_fd, 1)

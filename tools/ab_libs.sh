@@ -12,7 +12,7 @@ for n in $sizes; do
   for r in $(seq 1 $reps); do
     for lib in "$@"; do
       printf "n=%s %s " $n "$(basename $lib)" | tee -a $out/ab.log
-      ESLAM_GPU_LIB=$PWD/$lib timeout -k 10 120 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --particles $n $BENCH_ARGS \
+      ESLAM_GPU_LIB=$PWD/$lib timeout -k 10 120 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --particles $n $BENCH_ARGS \
         | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernel_ms'])" | tee -a $out/ab.log
       [ ${PIPESTATUS[0]} -eq 0 ] || exit 1
     done
@@ -21,7 +21,7 @@ done
 for lib in "$@"; do
   b=$(basename $lib .so)
   ESLAM_GPU_LIB=$PWD/$lib timeout -s KILL 90 rocprofv3 --pmc ${PMC:-SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU} \
-    --output-format csv -d $out/pmc_$b -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline $BENCH_ARGS > $out/pmc_$b.log 2>&1 || { echo "pmc $b failed"; exit 1; }
+    --output-format csv -d $out/pmc_$b -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $BENCH_ARGS > $out/pmc_$b.log 2>&1 || { echo "pmc $b failed"; exit 1; }
 done
 python3 - "$out" <<'PY'
 import csv, glob, os, sys

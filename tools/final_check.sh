@@ -15,7 +15,7 @@ step() {  # step <name> <timeout> <cmd...>: stop at the first failure
 }
 step pytest_gpu 900 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 300 python bench.py
-step bench_sharded_4m 200 python bench.py --sharded --steps 50 --warmup 10 --no-cpu-baseline
-step bench_4m_b 200 python bench.py --steps 50 --warmup 10 --no-cpu-baseline
-step bench_sharded_4m_b 200 python bench.py --sharded --steps 50 --warmup 10 --no-cpu-baseline
+step bench 300 python bench.py --full
+step bench_sharded_4m 200 python bench.py --full --sharded --steps 50 --warmup 10 --no-cpu-baseline
+step bench_4m_b 200 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline
+step bench_sharded_4m_b 200 python bench.py --full --sharded --steps 50 --warmup 10 --no-cpu-baseline

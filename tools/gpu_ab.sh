@@ -18,7 +18,7 @@ line() {  # line <label> <lib or ""> <bench args...>
   local label=$1 lib=$2; shift 2
   printf "%s " "$label" >> $out/ab.log
   if [ -n "$lib" ]; then export ESLAM_GPU_LIB=$PWD/$L/lib_$lib.so; else unset ESLAM_GPU_LIB; fi
-  timeout -k 10 200 python bench.py --no-cpu-baseline "$@" > $out/tmp.json 2>> $out/bench_err.log || { echo "bench $label failed"; tail -5 $out/bench_err.log; exit 1; }
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline "$@" > $out/tmp.json 2>> $out/bench_err.log || { echo "bench $label failed"; tail -5 $out/bench_err.log; exit 1; }
   unset ESLAM_GPU_LIB
   tail -1 $out/tmp.json | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], json.dumps(d.get('kernel_ms')))" >> $out/ab.log
 }

@@ -27,9 +27,9 @@ run() {  # run <name> <timeout> <cmd...>; 0/1 (test failures) continue, anything
 }
 prof() {  # prof <name> <bench args...>
   local name=$1; shift
-  run ${name}_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name/trace -o run -- python3 bench.py --no-cpu-baseline "$@"
+  run ${name}_trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name/trace -o run -- python3 bench.py --full --no-cpu-baseline "$@"
   for c in FETCH_SIZE WRITE_SIZE VALUBusy; do
-    run ${name}_$c 300 rocprofv3 --pmc $c --output-format csv -d $out/$name/$c -o run -- python3 bench.py --no-cpu-baseline "$@"
+    run ${name}_$c 300 rocprofv3 --pmc $c --output-format csv -d $out/$name/$c -o run -- python3 bench.py --full --no-cpu-baseline "$@"
   done
 }
 rocm-smi --showproductname > $out/gpu.txt 2>&1; nproc >> $out/gpu.txt; lscpu | grep "Model name" >> $out/gpu.txt
@@ -38,10 +38,10 @@ for step in "$@"; do
     tests) run pytest_gpu 1150 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread ;;
     tests:*) f=${step#tests:}; run pytest_${f%.py} 900 python -u -m pytest tests/$f -m gpu -v --timeout 900 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 300 python bench.py --steps 50 --warmup 10 --cpu-steps 8 ;;
-    bench256k) run bench256k 300 python bench.py --particles 262144 --steps 50 --warmup 10 --no-cpu-baseline ;;
-    benchlm) run benchlm 300 python bench.py --local-maps --steps 20 --warmup 5 --no-cpu-baseline ;;
-    benchsh) run benchsh 300 python bench.py --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline ;;
+    bench) run bench 300 python bench.py --full --steps 50 --warmup 10 --cpu-steps 8 ;;
+    bench256k) run bench256k 300 python bench.py --full --particles 262144 --steps 50 --warmup 10 --no-cpu-baseline ;;
+    benchlm) run benchlm 300 python bench.py --full --local-maps --steps 20 --warmup 5 --no-cpu-baseline ;;
+    benchsh) run benchsh 300 python bench.py --full --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline ;;
     proflm) prof proflm --local-maps --steps 20 --warmup 5 ;;
     prof) prof prof --steps 50 --warmup 10 ;;
   esac

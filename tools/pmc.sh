@@ -12,7 +12,7 @@ for pass in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM
             "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64" \
             "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_MFMA_F64 SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $out/p$i -o run -- python3 bench.py --no-cpu-baseline "$@" > $out/p$i.log 2>&1 || { echo "pass $i rc=$?"; tail -5 $out/p$i.log; }
+  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d $out/p$i -o run -- python3 bench.py --full --no-cpu-baseline "$@" > $out/p$i.log 2>&1 || { echo "pass $i rc=$?"; tail -5 $out/p$i.log; }
 done
 python3 - "$out" <<'PY'
 import csv, glob, os, sys, json

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 out=gpurun_out/pmcb_$tag
 mkdir -p $out
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $out/$c -o run -- python3 bench.py --no-cpu-baseline "$@" > $out/$c.log 2>&1 || { echo "$c rc=$?"; tail -3 $out/$c.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $out/$c -o run -- python3 bench.py --full --no-cpu-baseline "$@" > $out/$c.log 2>&1 || { echo "$c rc=$?"; tail -3 $out/$c.log; exit 1; }
 done
 python3 - "$out" <<'PY'
 import csv, glob, os, sys

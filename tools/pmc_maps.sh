@@ -14,7 +14,7 @@ for pass in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM
             "TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum" \
             "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum"; do
   i=$((i+1))
-  timeout -s KILL 240 rocprofv3 --pmc $pass --output-format csv -d $out/p$i -o run -- python3 bench.py --no-cpu-baseline --local-maps "$@" > $out/p$i.log 2>&1 || { echo "pass $i rc=$?"; tail -3 $out/p$i.log; }
+  timeout -s KILL 240 rocprofv3 --pmc $pass --output-format csv -d $out/p$i -o run -- python3 bench.py --full --no-cpu-baseline --local-maps "$@" > $out/p$i.log 2>&1 || { echo "pass $i rc=$?"; tail -3 $out/p$i.log; }
 done
 python3 - "$out" <<'PY'
 import csv, glob, os, sys, json

@@ -22,18 +22,18 @@ rocm-smi --showproductname > $out/gpu_box.txt 2>&1; nproc >> $out/gpu_box.txt; l
 if [[ $part == *a* ]]; then
 step profile 900 bash tools/profile.sh $tag --steps 50 --warmup 10
 step pmc 900 bash tools/pmc.sh $tag --steps 20 --warmup 5
-step bench 600 python bench.py
-step bench_256k 300 python bench.py --particles 262144 --steps 50 --warmup 10 --no-cpu-baseline
-step bench_sharded 300 python bench.py --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
-step bench_2m 300 python bench.py --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
-step bench_sharded_b 300 python bench.py --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
-step bench_2m_b 300 python bench.py --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
+step bench 600 python bench.py --full
+step bench_256k 300 python bench.py --full --particles 262144 --steps 50 --warmup 10 --no-cpu-baseline
+step bench_sharded 300 python bench.py --full --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
+step bench_2m 300 python bench.py --full --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
+step bench_sharded_b 300 python bench.py --full --sharded --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
+step bench_2m_b 300 python bench.py --full --particles 2097152 --steps 50 --warmup 10 --no-cpu-baseline
 fi
 if [[ $part == *b* ]]; then
-step bench_16m 300 python bench.py --particles 16777216 --steps 20 --warmup 5 --no-cpu-baseline
-step bench_rough 300 python bench.py --rough --steps 50 --warmup 10 --no-cpu-baseline
-step bench_local_maps 600 python bench.py --local-maps --steps 20 --warmup 5
-step bench_local_maps_steady 600 python bench.py --local-maps --steps 20 --warmup 30 --no-cpu-baseline
+step bench_16m 300 python bench.py --full --particles 16777216 --steps 20 --warmup 5 --no-cpu-baseline
+step bench_rough 300 python bench.py --full --rough --steps 50 --warmup 10 --no-cpu-baseline
+step bench_local_maps 600 python bench.py --full --local-maps --steps 20 --warmup 5
+step bench_local_maps_steady 600 python bench.py --full --local-maps --steps 20 --warmup 30 --no-cpu-baseline
 step prof_lm 900 bash tools/profile.sh ${tag}_lm --local-maps --steps 20 --warmup 30
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread
