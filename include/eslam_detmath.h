@@ -1848,5 +1848,22 @@ DM_FN int dm_lm_fuse(float m1f, float s1f, double wz, double var, float* mo, flo
     *so = (float)dm_sqrt(v);
     return 1;
 }
+/* getPatch's 3-sigma gate of one stored patch {mean, stdev, height} against a query (q_mean,
+ * q_var): diff^2 < 9 (stdev^2 + q_var), a vertical patch (height > 0) spanning
+ * [mean - height, mean].  The shared-map merge (eslam_gpu_shared_map_update) walks a cell's
+ * patches with it: the first patch that passes takes the scan patch.                        */
+DM_FN int dm_mls_gate(float meanf, float stdevf, float heightf, double q_mean, double q_var)
+{
+    const double pm = (double)meanf, ps = (double)stdevf, ph = (double)heightf;
+    double diff;
+    if (ph > 0.0) {
+        if (q_mean > pm) diff = q_mean - pm;
+        else if (q_mean < pm - ph) diff = (pm - ph) - q_mean;
+        else diff = 0.0;
+    } else {
+        diff = pm > q_mean ? pm - q_mean : q_mean - pm;
+    }
+    return diff * diff < 9.0 * (ps * ps + q_var);
+}
 
 #endif /* ESLAM_DETMATH_H */

@@ -304,6 +304,61 @@ int eslam_gpu_set_particle_maps(eslam_ctx* ctx, int on);
 int eslam_gpu_get_particle_map(eslam_ctx* ctx, uint64_t index, uint32_t* cells, float* mean, float* stdev,
                                uint32_t capacity, uint32_t* count);
 
+/* ---- the shared map (useSharedMap = true): processMap's merge into the one grid ----------
+ * EmbodiedSlamFilter::processMap(scanMap, match, update = true) with a shared map
+ * (src/EmbodiedSlamFilter.cpp:184-227; the camera path's call at :301): every particle's pgrid
+ * is the one shared grid, so the scan is merged into it once per particle, at that particle's
+ * pose, in particle order.  envire's MLSGrid::merge is not in the reference, so the fuse rule
+ * is this build's (parity unpinned):
+ *   particles i = 0..N-1 in index order, scan patches k = 0..P-1 in scan order; a particle
+ *   whose x - offset_x, y - offset_y or theta is not finite is skipped; a patch is placed as
+ *   eslam_gpu_map_update places it (wz = z + zPos_i, var = stdev^2 + zSigma_i^2) and skipped
+ *   when it falls off the grid.  A placed patch goes to the first patch of its cell, in list
+ *   order, that passes getPatch's 3-sigma gate (dm_mls_gate): a horizontal one becomes their
+ *   variance-weighted fusion (dm_lm_fuse), a vertical one (height > 0) stays and absorbs it;
+ *   when none passes, {(float)wz, (float)sqrt(var), height 0} is appended to the cell's list.
+ * A later particle sees what earlier ones wrote: the result is that of the sequential loop,
+ * bit for bit, however the work is split.  Particles, weights and the RNG do not change; the
+ * pose hash is not rebuilt (the reference builds it once, in init); later steps, matches and
+ * eslam_gpu_hash_create see the merged grid.                                               */
+typedef struct eslam_shared_merge_info {
+    uint64_t particles_done;               /* particles worked through (all of them on success) */
+    uint64_t patches_placed;               /* (particle, patch) pairs that landed on the grid  */
+    uint64_t patches_off_grid;             /* pairs not placed: off the grid, or of a particle
+                                              with a non-finite pose                           */
+    uint64_t cells_touched;                /* distinct cells that received a placed patch      */
+    uint64_t fused;                        /* placed patches fused into a horizontal patch     */
+    uint64_t absorbed;                     /* placed patches a vertical patch absorbed (or a
+                                              fuse left as it was): placed - fused - inserted  */
+    uint64_t inserted;                     /* placed patches appended as new patches           */
+    uint64_t n_patches;                    /* patches of the grid after the call               */
+    uint64_t runs;                         /* runs the particles were worked through in        */
+} eslam_shared_merge_info;
+/* The particles are worked through in consecutive runs of whole particles, each of at most
+ * max_records (particle, patch) records and at least one particle; a run places its records,
+ * sorts them stably by cell, merges every touched cell's records in order and rebuilds the
+ * grid's arrays.  max_records bounds the device scratch at about 32 bytes per record (plus 12
+ * per cell); 0 means 2^21 records, 64 MiB.  The scratch stays with the context.  While the
+ * call runs, a second copy of the grid's arrays exists.
+ * Errors: ESLAM_ERR_INVALID_ARG (null arguments, a filter with ESLAM_FLAG_PARTICLE_MAPS,
+ * non-finite patches), ESLAM_ERR_NO_ENVIRONMENT (no map), ESLAM_ERR_NOT_INITIALISED (no
+ * particles), ESLAM_ERR_UNSUPPORTED (a sharded filter: every rank holds its own copy of the
+ * grid, and a merge in global particle order across ranks is not built),
+ * ESLAM_ERR_OUT_OF_MEMORY (an allocation failed, or a run's placed patches could take the
+ * grid past 2^32 - 1 patches).  After a failure the grid holds the runs merged before it
+ * (info->particles_done particles).  count == 0 succeeds and changes nothing.  info may be
+ * NULL.                                                                                    */
+int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
+                                eslam_shared_merge_info* info);
+/* the shared grid as the device holds it (after eslam_gpu_set_map and every merge since): its
+ * size (any pointer may be NULL) ...                                                        */
+int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64_t* n_patches, int* has_height);
+/* ... and its arrays: cell_start (width * height + 1 entries), mean and stdev (n_patches, at
+ * most patch_capacity: ESLAM_ERR_INVALID_ARG when it holds more), patch_height (may be NULL;
+ * zeros when the grid has no heights)                                                       */
+int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* mean, float* stdev, float* patch_height,
+                      uint64_t patch_capacity);
+
 /* ---- PoseParticle records with the debug fields (getParticles() for logging / viz) ------ */
 /* ContactPoint  src/PoseParticle.hpp:20-43: one contact point evaluatePose pushed           */
 typedef struct eslam_cpoint {

@@ -627,6 +627,22 @@ public:
         }
         check(ctx_, eslam_gpu_map_update(ctx_, p.data(), (uint32_t)p.size()));
     }
+    // the same merge with the shared map (useShared = true: every particle's pgrid is the one
+    // grid, src/EmbodiedSlamFilter.cpp:184-227): the scan goes into the shared grid once per
+    // particle, at that particle's pose, in particle order (eslam_gpu_shared_map_update; the
+    // particles do not change).  Returns the merge's counters.
+    eslam_shared_merge_info updateSharedMap(const std::vector<ScanPatch>& scan, uint64_t maxRecords = 0)
+    {
+        flush();
+        std::vector<eslam_scan_patch> p(scan.size());
+        for (size_t k = 0; k < scan.size(); ++k) {
+            for (int i = 0; i < 3; ++i) p[k].position[i] = scan[k].position[i];
+            p[k].stdev = scan[k].stdev;
+        }
+        eslam_shared_merge_info info;
+        check(ctx_, eslam_gpu_shared_map_update(ctx_, p.data(), (uint32_t)p.size(), maxRecords, &info));
+        return info;
+    }
 
     // init(numParticles, hash)  src/PoseEstimator.cpp:75-86 (the hash is built on the device
     // from the environment's grid; the SurfaceHashConfig was given at construction)
@@ -970,14 +986,17 @@ public:
     }
 
     // processMap(scanMap, match, update)  src/EmbodiedSlamFilter.cpp:179-232 with the scan's
-    // MLS as patches: update merges them into every particle's own map (useSharedMap = false;
-    // the reference's update-only call, src/EmbodiedSlamFilter.cpp:340-342); match weights every
-    // particle against its map first -- the shared grid (useSharedMap = true: the laser path's
-    // match-only call, :342-344) or its own map (the build's match rule, eslam_gpu_map_match)
+    // MLS as patches: match weights every particle against its map first -- the shared grid
+    // (useSharedMap = true: the laser path's match-only call, :342-344) or its own map (the
+    // build's match rule, eslam_gpu_map_match); update then merges the patches into every
+    // particle's own map (useSharedMap = false; the reference's update-only call, :340-342) or,
+    // with the shared map, into the one grid once per particle in particle order (the camera
+    // path's processMap(scanMap, false, true), :301)
     void processMap(const std::vector<ScanPatch>& scanMap, bool match, bool update)
     {
         if (match) estimator().matchMaps(scanMap);
         if (update && !sharedMap_) estimator().updateMaps(scanMap);
+        if (update && sharedMap_) estimator().updateSharedMap(scanMap);
     }
 
     std::vector<PoseParticle>& getParticles() { return estimator().getParticles(); }

@@ -28,7 +28,7 @@ LIB = os.path.join(OUT_DIR, "libeslam_gpu.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ESLAM_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["eslam_kernels.hip", "eslam_hash.hip", "eslam_ctx.hip"]
+SOURCES = ["eslam_kernels.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_ctx.hip"]
 HEADERS = [os.path.join(CSRC, "eslam_internal.h"), os.path.join(ROOT, "include", "eslam_gpu.h"),
            os.path.join(ROOT, "include", "eslam_detmath.h")]
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -98,18 +98,21 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_facade_test(verbose=True):
-    """g++ the C++ façade test (include/eslam_gpu.hpp over the C ABI) against the library."""
-    deps = [FACADE_SRC, LIB, os.path.join(ROOT, "include", "eslam_gpu.hpp"), os.path.join(ROOT, "include", "eslam_gpu.h")]
-    if not _stale(FACADE_BIN, deps):
-        return FACADE_BIN
-    os.makedirs(os.path.dirname(FACADE_BIN), exist_ok=True)
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{os.path.join(ROOT, 'include')}", FACADE_SRC,
-           f"-L{OUT_DIR}", "-leslam_gpu", "-Wl,-rpath,$ORIGIN/../../../slam-eslam_amd/lib", "-o", FACADE_BIN]
+def build_facade_test(verbose=True, name="test_facade"):
+    """g++ a C++ façade test (include/eslam_gpu.hpp over the C ABI) against the library:
+    tests/cpp/<name>.cpp -> tests/cpp/_build/<name> (test_facade, test_facade_shared_map)."""
+    src = os.path.join(os.path.dirname(FACADE_SRC), name + ".cpp")
+    exe = os.path.join(os.path.dirname(FACADE_BIN), name)
+    deps = [src, LIB, os.path.join(ROOT, "include", "eslam_gpu.hpp"), os.path.join(ROOT, "include", "eslam_gpu.h")]
+    if not _stale(exe, deps):
+        return exe
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", f"-I{os.path.join(ROOT, 'include')}", src,
+           f"-L{OUT_DIR}", "-leslam_gpu", "-Wl,-rpath,$ORIGIN/../../../slam-eslam_amd/lib", "-o", exe]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    return FACADE_BIN
+    return exe
 
 
 if __name__ == "__main__":

@@ -69,6 +69,12 @@ extern "C" hipError_t eslam_launch_project_weight(int project, int weight, int m
                                                   const GatherView* gv, const LocalMaps* store, hipStream_t stream,
                                                   const ChunkSel* sel, double* bspill);
 extern "C" hipError_t eslam_launch_commit(Ctl* ctl, hipStream_t stream);
+// eslam_shared_map.hip
+extern "C" size_t eslam_sm_sort_bytes(uint64_t records);
+extern "C" hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const SmRun* run,
+                                            const SmScratch* s, hipStream_t stream);
+extern "C" hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl* ctl, const SmRun* run, const SmGrid* cur,
+                                            const SmGrid* next, const SmScratch* s, hipStream_t stream);
 extern "C" hipError_t eslam_launch_weight_stats(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, Shard* shards,
                                                 hipStream_t stream);
 extern "C" hipError_t eslam_launch_finalize(Shard* recs, int nrec, Ctl* ctl, const FinParams* fp, hipStream_t stream);
@@ -332,6 +338,11 @@ struct eslam_ctx {
     float* d_height = nullptr;
     uint32_t* d_occ = nullptr;               // MapView::occ
     uint4* d_cell_tab = nullptr;             // MapView::cell_tab
+    uint64_t map_np = 0;                     // patches of the grid (cell_start[width * height])
+    uint64_t map_np_cap = 0;                 // patches d_patch / d_height have room for
+    // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
+    void* sm_mem = nullptr;
+    uint64_t sm_bytes = 0;
     uint32_t maxp = 4;
     // host-side filter state
     uint64_t proj_event = 0, init_event = 0, hash_event = 0;
@@ -711,6 +722,7 @@ static void free_map(eslam_ctx* ctx)
     (void)hipFree(ctx->d_cell_tab);
     ctx->d_cells = nullptr; ctx->d_patch = nullptr; ctx->d_height = nullptr; ctx->d_occ = nullptr;
     ctx->d_cell_tab = nullptr;
+    ctx->map_np = ctx->map_np_cap = 0;
     ctx->has_map = false;
 }
 
@@ -740,6 +752,7 @@ extern "C" void eslam_gpu_destroy(eslam_ctx* ctx)
     (void)hipFree(ctx->sendhdr); (void)hipFree(ctx->recvhdr); (void)hipFree(ctx->payoff); (void)hipFree(ctx->rhead);
     (void)hipFree(ctx->d_hash); (void)hipFree(ctx->d_hash_blist); (void)hipFree(ctx->d_sort); (void)hipFree(ctx->sort_tmp); (void)hipFree(ctx->d_draws);
     (void)hipFree(ctx->hsend); (void)hipFree(ctx->hrecv); (void)hipFree(ctx->hsort);
+    (void)hipFree(ctx->sm_mem);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ring) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->mring) if (e) (void)hipEventDestroy(e);
@@ -1223,6 +1236,8 @@ extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
     m.patch = ctx->d_patch;
     m.height = ctx->d_height;
     m.has_height = ctx->d_height ? 1u : 0u;
+    ctx->map_np = g->n_patches;
+    ctx->map_np_cap = np;
     m.width = g->width;
     m.height_cells = g->height;
     m.inv_scale_x = 1.0 / g->scale_x;
@@ -1955,6 +1970,223 @@ extern "C" int eslam_gpu_get_particle_map(eslam_ctx* ctx, uint64_t index, uint32
             }
     }
     *count = k;
+    return ESLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the shared map: processMap's merge into the one grid (eslam_shared_map.hip)
+// ---------------------------------------------------------------------------------------
+static void sm_free_grid(SmGrid* g)
+{
+    (void)hipFree(g->cell_start); (void)hipFree(g->patch); (void)hipFree(g->height); (void)hipFree(g->occ);
+    (void)hipFree(g->cell_tab);
+    *g = SmGrid{};
+}
+
+// a second set of the grid's arrays with room for `cap` patches; false (nothing held) when
+// the device has no room
+static bool sm_alloc_grid(SmGrid* g, uint64_t ncell, uint64_t cap, bool heights)
+{
+    *g = SmGrid{};
+    const uint64_t c = cap ? cap : 1;
+    bool ok = hipMalloc(&g->cell_start, (ncell + 1) * 4) == hipSuccess && hipMalloc(&g->patch, c * sizeof(float2)) == hipSuccess &&
+              hipMalloc(&g->occ, ((ncell + 31) / 32) * 4) == hipSuccess &&
+              hipMalloc(&g->cell_tab, ncell * sizeof(uint4)) == hipSuccess;
+    if (ok && heights) ok = hipMalloc(&g->height, c * 4) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        sm_free_grid(g);
+    }
+    return ok;
+}
+
+// the run scratch for `rec` records and `ncell` cells, carved from one allocation the context keeps
+static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t scan_patches, SmScratch* s, ScanPatch** sp)
+{
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const size_t sort_bytes = eslam_sm_sort_bytes(rec);
+    const uint64_t off_keys = 0, off_vals = off_keys + up((rec + 1) * 4), off_ko = off_vals + up(rec * 4),
+                   off_ord = off_ko + up(rec * 4), off_app = off_ord + up(rec * 4), off_add = off_app + up(rec * sizeof(float2)),
+                   off_seg = off_add + up(ncell * 4), off_tch = off_seg + up(ncell * 4), off_cnt = off_tch + up(ncell * 4),
+                   off_sort = off_cnt + up(kSmCounters * 8), off_sp = off_sort + up(sort_bytes),
+                   total = off_sp + up(scan_patches * sizeof(ScanPatch));
+    if (total > ctx->sm_bytes) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->sm_mem);
+        ctx->sm_mem = nullptr;
+        ctx->sm_bytes = 0;
+        if (hipMalloc(&ctx->sm_mem, total) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->sm_mem = nullptr;
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the run scratch (lower max_records)");
+        }
+        ctx->sm_bytes = total;
+    }
+    char* m = (char*)ctx->sm_mem;
+    s->keys = (uint32_t*)(m + off_keys);
+    s->vals = (uint32_t*)(m + off_vals);
+    s->keys_out = (uint32_t*)(m + off_ko);
+    s->order = (uint32_t*)(m + off_ord);
+    s->app = (float2*)(m + off_app);
+    s->add = (uint32_t*)(m + off_add);
+    s->segpos = (uint32_t*)(m + off_seg);
+    s->touched = (uint32_t*)(m + off_tch);
+    s->cnt = (uint64_t*)(m + off_cnt);
+    s->sort_tmp = m + off_sort;
+    s->sort_tmp_bytes = sort_bytes;
+    *sp = (ScanPatch*)(m + off_sp);
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
+                                           eslam_shared_merge_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx || (!patches && count)) return ESLAM_ERR_INVALID_ARG;
+    if (particle_maps(ctx))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "shared_map_update: the filter has per-particle maps (eslam_gpu_map_update merges into those)");
+    for (uint32_t k = 0; k < count; ++k)
+        if (!dm_isfinite(patches[k].position[0]) || !dm_isfinite(patches[k].position[1]) ||
+            !dm_isfinite(patches[k].position[2]) || !dm_isfinite(patches[k].stdev))
+            return fail(ctx, ESLAM_ERR_INVALID_ARG, "shared_map_update: scan patches must be finite");
+    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (ctx->sharded)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
+                    "shared_map_update: a sharded filter keeps a copy of the grid per rank; the merge in global particle "
+                    "order across ranks is not built");
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    if (info) info->n_patches = ctx->map_np;
+    if (!count) return ESLAM_OK;
+    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    if (ncell >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
+    // a run: whole particles, at most max_records records, at least one particle
+    const uint64_t P = count, n = ctx->n;
+    uint64_t lim = max_records ? max_records : kSmDefaultRecords;
+    if (lim > (1ull << 31)) lim = 1ull << 31;                  // record indices are 32-bit
+    uint64_t per = lim / P;
+    per = per < 1 ? 1 : (per > n ? n : per);
+    SmScratch sc;
+    ScanPatch* d_sp = nullptr;
+    int rc = sm_scratch(ctx, per * P, ncell, P, &sc, &d_sp);
+    if (!rc) rc = materialize(ctx);                           // the particles as they stand
+    if (rc) return rc;
+    static_assert(sizeof(ScanPatch) == sizeof(eslam_scan_patch), "scan patch layout");
+    HIPCHK(ctx, hipMemcpyAsync(d_sp, patches, P * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(sc.cnt, 0, kSmCounters * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(sc.touched, 0, ncell * 4, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // `patches` is the caller's
+    SmGrid spare = {};
+    uint64_t spare_cap = 0;
+    uint64_t cnt[kSmCounters] = {};
+    uint64_t done = 0, runs = 0, placed_all = 0;
+    hipError_t he = hipSuccess;
+    for (uint64_t i0 = 0; i0 < n && !rc; i0 += per) {
+        SmRun run = {};
+        run.i0 = i0;
+        run.P = count;
+        run.R = (n - i0 < per ? n - i0 : per) * P;
+        run.ncell = (uint32_t)ncell;
+        run.is_id = ctx->map.g2l_identity;
+        run.sp = d_sp;
+        if ((he = eslam_launch_sm_place(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &run, &sc, ctx->stream)) != hipSuccess) break;
+        uint64_t placed = 0;
+        if ((he = hipMemcpyAsync(&placed, sc.cnt + kSmRunPlaced, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
+        if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
+        if (placed) {
+            // the new arrays exist before anything of the grid changes: a run that finds no room
+            // leaves the grid as the runs before it made it
+            const uint64_t need = ctx->map_np + placed;
+            if (need > 0xffffffffull) {
+                rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: the grid would pass 2^32 - 1 patches");
+                break;
+            }
+            if (!spare.cell_start || spare_cap < need) {
+                sm_free_grid(&spare);
+                uint64_t want = need + need / 4;
+                want = want > 0xffffffffull ? 0xffffffffull : want;
+                spare_cap = want;
+                if (!sm_alloc_grid(&spare, ncell, want, ctx->d_height != nullptr)) {
+                    spare_cap = need;
+                    if (!sm_alloc_grid(&spare, ncell, need, ctx->d_height != nullptr)) {
+                        spare_cap = 0;
+                        rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
+                        break;
+                    }
+                }
+            }
+            const SmGrid cur{ctx->d_cells, ctx->d_patch, ctx->d_height, ctx->d_occ, ctx->d_cell_tab};
+            if ((he = eslam_launch_sm_merge(ctx->st[0], ctx->st[1], ctx->ctl, &run, &cur, &spare, &sc, ctx->stream)) != hipSuccess) break;
+            uint32_t total = 0;
+            if ((he = hipMemcpyAsync(&total, spare.cell_start + ncell, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
+            if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
+            // the swap: every later launch takes the grid from ctx->map (K1's window staging, the
+            // match, the hash build and get_map read these pointers at their call)
+            const uint64_t old_cap = ctx->map_np_cap;
+            ctx->d_cells = spare.cell_start; ctx->d_patch = spare.patch; ctx->d_height = spare.height;
+            ctx->d_occ = spare.occ; ctx->d_cell_tab = spare.cell_tab;
+            ctx->map_np = total;
+            ctx->map_np_cap = spare_cap;
+            ctx->map.cell_start = ctx->d_cells; ctx->map.patch = ctx->d_patch; ctx->map.height = ctx->d_height;
+            ctx->map.occ = ctx->d_occ; ctx->map.cell_tab = ctx->d_cell_tab;
+            spare = cur;                                          // the next run rebuilds into the old arrays
+            spare_cap = old_cap;
+        }
+        placed_all += placed;
+        done = i0 + run.R / P;
+        ++runs;
+    }
+    if (he == hipSuccess) he = hipMemcpy(cnt, sc.cnt, sizeof(cnt), hipMemcpyDeviceToHost);
+    sm_free_grid(&spare);                                        // (hipFree waits for the device)
+    if (info) {
+        info->particles_done = done;
+        info->patches_placed = placed_all;
+        info->patches_off_grid = done * P - placed_all;
+        info->cells_touched = cnt[kSmTouched];
+        info->fused = cnt[kSmFused];
+        info->absorbed = cnt[kSmAbsorbed];
+        info->inserted = cnt[kSmInserted];
+        info->n_patches = ctx->map_np;
+        info->runs = runs;
+    }
+    if (he != hipSuccess) {
+        ctx->err = std::string("shared_map_update: ") + hipGetErrorString(he);
+        return ESLAM_ERR_HIP;
+    }
+    return rc;
+}
+
+extern "C" int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64_t* n_patches, int* has_height)
+{
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
+    if (width) *width = ctx->map.width;
+    if (height) *height = ctx->map.height_cells;
+    if (n_patches) *n_patches = ctx->map_np;
+    if (has_height) *has_height = ctx->d_height ? 1 : 0;
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* mean, float* stdev, float* patch_height,
+                                 uint64_t patch_capacity)
+{
+    if (!ctx || !cell_start || ((!mean || !stdev) && patch_capacity)) return ESLAM_ERR_INVALID_ARG;
+    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
+    const uint64_t np = ctx->map_np, ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    if (patch_capacity < np) return fail(ctx, ESLAM_ERR_INVALID_ARG, "get_map: patch_capacity is below the grid's patch count (eslam_gpu_map_size)");
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(cell_start, ctx->d_cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
+    if (!np) return ESLAM_OK;
+    std::vector<float2> patch(np);
+    HIPCHK(ctx, hipMemcpy(patch.data(), ctx->d_patch, np * sizeof(float2), hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < np; ++k) {
+        mean[k] = patch[k].x;
+        stdev[k] = patch[k].y;
+    }
+    if (patch_height) {
+        if (ctx->d_height) HIPCHK(ctx, hipMemcpy(patch_height, ctx->d_height, np * 4, hipMemcpyDeviceToHost));
+        else memset(patch_height, 0, np * 4);
+    }
     return ESLAM_OK;
 }
 

@@ -241,10 +241,11 @@ extern "C" hipError_t eslam_launch_init_from_hash(DevState s0, const uint32_t* i
 
 // stable radix sort of n (key, value) pairs: keys/vals in, sorted into keys_out/order.
 // tmp: scratch for the digit histograms and one ping-pong pair (query its size with
-// tmp == NULL).  Four passes of 8 bits; the pass results alternate so the last lands in
-// keys_out/order.
-extern "C" hipError_t eslam_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_out, uint32_t* order, uint64_t n,
-                                             void* tmp, size_t* tmp_bytes, hipStream_t stream)
+// tmp == NULL).  `passes` (1..4) passes of 8 bits, from the lowest: keys below 2^(8 passes)
+// need no more (the shared map's merge sorts by cell); the pass results alternate so the
+// last lands in keys_out/order.
+extern "C" hipError_t eslam_radix_sort_pairs_passes(uint32_t* keys, uint32_t* vals, uint32_t* keys_out, uint32_t* order,
+                                                    uint64_t n, void* tmp, size_t* tmp_bytes, int passes, hipStream_t stream)
 {
     const uint32_t ntiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
     const uint64_t hist_words = (uint64_t)kDigits * (ntiles ? ntiles : 1);
@@ -255,12 +256,14 @@ extern "C" hipError_t eslam_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uin
     uint32_t* hist = (uint32_t*)tmp;
     uint32_t* tk = hist + hist_words;
     uint32_t* tv = tk + n;
-    // passes: keys -> (tk, tv) -> (keys_out, order) -> (tk, tv) -> (keys_out, order)
+    if (passes < 1 || passes > 4) return hipErrorInvalidValue;
+    // four passes: keys -> (tk, tv) -> (keys_out, order) -> (tk, tv) -> (keys_out, order)
     const uint32_t* ki = keys;
     const uint32_t* vi = vals;
-    for (int pass = 0; pass < 4; ++pass) {
-        uint32_t* ko = (pass & 1) ? keys_out : tk;
-        uint32_t* vo = (pass & 1) ? order : tv;
+    for (int pass = 0; pass < passes; ++pass) {
+        const bool last = ((passes - 1 - pass) & 1) == 0;
+        uint32_t* ko = last ? keys_out : tk;
+        uint32_t* vo = last ? order : tv;
         hipLaunchKernelGGL(k_radix_hist, dim3(ntiles), dim3(kBlock), 0, stream, ki, n, 8 * pass, hist, ntiles);
         (void)eslam_launch_scan_excl(hist, hist_words, stream);
         hipLaunchKernelGGL(k_radix_scatter, dim3(ntiles), dim3(kBlock), 0, stream, ki, vi, ko, vo, n, 8 * pass, hist, ntiles);
@@ -268,6 +271,13 @@ extern "C" hipError_t eslam_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uin
         vi = vo;
     }
     return hipGetLastError();
+}
+
+// all 32 key bits
+extern "C" hipError_t eslam_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_out, uint32_t* order, uint64_t n,
+                                             void* tmp, size_t* tmp_bytes, hipStream_t stream)
+{
+    return eslam_radix_sort_pairs_passes(keys, vals, keys_out, order, n, tmp, tmp_bytes, 4, stream);
 }
 
 // the k lowest particles by (float weight, index) into order[0..k): keys + the stable sort.

@@ -383,6 +383,44 @@ struct MergeParams {
     const ScanPatch* sp;                 // the part's patches (device copy of the scan)
 };
 
+// ---- the shared map's merge (eslam_gpu_shared_map_update, eslam_shared_map.hip) ----------
+// One run: particles [i0, i0 + np) x the scan's P patches = R records, record r = (i0 + r / P,
+// r % P), so record order is the contract's (particle, patch) order.
+struct SmRun {
+    uint64_t i0;
+    uint64_t R;                          // np * P < 2^32
+    uint32_t P;
+    uint32_t ncell;                      // width * height: also the key of a record that is not placed
+    uint32_t is_id;                      // the grid's global2local is the identity
+    uint32_t pad;
+    const ScanPatch* sp;                 // the scan (device)
+};
+// the grid's arrays a merge reads and writes (fuses in place) or rebuilds into
+struct SmGrid {
+    uint32_t* cell_start;
+    float2* patch;
+    float* height;                       // null: all horizontal
+    uint32_t* occ;
+    uint4* cell_tab;
+};
+// the scratch of a run, bounded by max_records (and the cell count): about 32 bytes per record
+struct SmScratch {
+    uint32_t* keys;                      // R + 1: the records' cells in record order; after the sort, the
+                                         //   segment-head flags and their exclusive scan (flag[R]: heads)
+    uint32_t* vals;                      // R: the record indices; after the sort, the heads' positions
+    uint32_t* keys_out;                  // R: cells, sorted (stable)
+    uint32_t* order;                     // R: the records in sorted order
+    float2* app;                         // R: patches a cell's segment appended, at the segment's start
+    uint32_t* add;                       // per cell: patches this run appended (zeroed per run)
+    uint32_t* segpos;                    // per cell with add > 0: its segment's start
+    uint32_t* touched;                   // per cell: a placed patch reached it in this call
+    uint64_t* cnt;                       // kSmCounters counters: the call's, and the current run's placed records
+    void* sort_tmp;
+    size_t sort_tmp_bytes;
+};
+enum SmCounter : uint32_t { kSmFused = 0, kSmAbsorbed, kSmInserted, kSmTouched, kSmRunPlaced, kSmCounters = 8 };
+constexpr uint64_t kSmDefaultRecords = 1ull << 21;   // max_records = 0: 64 MiB of scratch
+
 // logDebug records of the last update (k_contact_records), indexed by the particle's
 // position during that update: meas 4 doubles (x, y, zPos, theta), ncp, and maxc contact
 // points of 6 doubles (surface point xyz, zdiff, zvar, prob)

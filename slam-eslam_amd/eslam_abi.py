@@ -123,6 +123,24 @@ class ScanPatch(C.Structure):
     ]
 
 
+class SharedMergeInfo(C.Structure):
+    """eslam_shared_merge_info: the counters of eslam_gpu_shared_map_update"""
+    _fields_ = [
+        ("particles_done", C.c_uint64),
+        ("patches_placed", C.c_uint64),
+        ("patches_off_grid", C.c_uint64),
+        ("cells_touched", C.c_uint64),
+        ("fused", C.c_uint64),
+        ("absorbed", C.c_uint64),
+        ("inserted", C.c_uint64),
+        ("n_patches", C.c_uint64),
+        ("runs", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class CPoint(C.Structure):
     """eslam_cpoint: ContactPoint (src/PoseParticle.hpp:20-43)"""
     _fields_ = [

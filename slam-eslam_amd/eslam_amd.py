@@ -67,6 +67,13 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_map_update.argtypes = [vp, C.POINTER(A.ScanPatch), C.c_uint32]
     if hasattr(L, "eslam_gpu_map_match"):                 # absent from older builds (A/B runs)
         L.eslam_gpu_map_match.argtypes = [vp, C.POINTER(A.ScanPatch), C.c_uint32]
+    if hasattr(L, "eslam_gpu_shared_map_update"):        # absent from older builds (A/B runs)
+        L.eslam_gpu_shared_map_update.argtypes = [vp, C.POINTER(A.ScanPatch), C.c_uint32, C.c_uint64,
+                                                  C.POINTER(A.SharedMergeInfo)]
+        L.eslam_gpu_map_size.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_int)]
+        L.eslam_gpu_get_map.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float), C.c_uint64]
     L.eslam_gpu_set_particle_maps.argtypes = [vp, C.c_int]
     L.eslam_gpu_get_particle_map.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -196,6 +203,35 @@ class GpuFilter:
         """eslam_gpu_map_match: processMap's visual weighting (match = true) against each
         particle's map: the shared grid, or its own map (per-particle maps)"""
         self._check(self.L.eslam_gpu_map_match(self.h, patches, len(patches)))
+
+    def shared_map_update(self, patches, max_records=0):
+        """eslam_gpu_shared_map_update: processMap's merge of a scan into the shared grid, once
+        per particle in index order (useSharedMap = true); returns the SharedMergeInfo.  On an
+        error the EslamError carries the counters of the runs merged before it (`.info`)."""
+        info = A.SharedMergeInfo()
+        rc = self.L.eslam_gpu_shared_map_update(self.h, patches, len(patches), max_records, C.byref(info))
+        if rc != 0:
+            e = EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+            e.info = info
+            raise e
+        return info
+
+    def get_map(self):
+        """eslam_gpu_get_map: the shared grid as the device holds it (GridArrays with the
+        geometry of the grid given to set_map)"""
+        if self._grid is None:
+            raise EslamError(A.ERR_NO_ENVIRONMENT, "No environment attached.")
+        w, h, n, hh = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_int()
+        self._check(self.L.eslam_gpu_map_size(self.h, C.byref(w), C.byref(h), C.byref(n), C.byref(hh)))
+        cells = np.zeros(w.value * h.value + 1, np.uint32)
+        mean = np.zeros(n.value, np.float32)
+        sd = np.zeros(n.value, np.float32)
+        hgt = np.zeros(n.value, np.float32) if hh.value else None
+        fp = C.POINTER(C.c_float)
+        self._check(self.L.eslam_gpu_get_map(self.h, cells.ctypes.data_as(C.POINTER(C.c_uint32)), mean.ctypes.data_as(fp),
+                                             sd.ctypes.data_as(fp), hgt.ctypes.data_as(fp) if hh.value else None, n.value))
+        g = self._grid
+        return A.GridArrays(w.value, h.value, g.scale, g.offset, cells, mean, sd, hgt, g.g2l)
 
     def particle_map(self, i, cap=1024):
         """particle i's own patches: (cells, mean, stdev), tiles in slot order, cells row by row"""
