@@ -444,6 +444,56 @@ typedef struct eslam_rng_state {
 int eslam_gpu_get_rng_state(eslam_ctx* ctx, eslam_rng_state* st);
 int eslam_gpu_set_rng_state(eslam_ctx* ctx, const eslam_rng_state* st);
 
+/* ---- snapshots: everything a filter needs to continue bit for bit -------------------------
+ * One blob (little-endian, layout in DESIGN.md 5e) holds the particles, the RNG state and the
+ * scalars the next update reads, the shared grid as the device holds it now, the pose hash,
+ * and with ESLAM_FLAG_PARTICLE_MAPS every particle's map: tables and pages under compact ids
+ * in a canonical order (tables by the lowest particle naming them, pages by first reference),
+ * sharing and page ownership kept.  The bytes depend on the filter's logical state only.
+ * The format carries its own version; ESLAM_ABI_VERSION is unchanged.
+ *
+ * The blob is produced and consumed on the device in chunks of at most chunk_bytes (0: 64 MiB;
+ * any value from 4 KiB up; a table row longer than that goes as one chunk), through two pinned
+ * and two device staging buffers the context keeps.  A callback returning non-zero ends the
+ * call with ESLAM_ERR_COMM.
+ *
+ * Save first does what eslam_gpu_download_particles does (a pending gather is run), and
+ * changes nothing a later step, map update, match, download or counter can see.
+ * Load works on a context that was only created (no set_map / init_* / hash_create) and
+ * replaces whatever a live one holds.  It checks the header, the section sizes and, on the
+ * host, every table and page id before a kernel reads it: ESLAM_ERR_INVALID_ARG for a blob
+ * that fails, or whose ESLAM_FLAG_PARTICLE_MAPS bit, window half-widths (max_sensor_range) or
+ * local_map_trail differ from the context's; ESLAM_ERR_OUT_OF_MEMORY for more live pages than
+ * the context's pool (local_map_pages may differ from the saving context's).  After a failed
+ * load the context holds no particles and is not poisoned.  The rest of the configuration is
+ * the context's own, as with eslam_gpu_upload_particles.
+ * Not carried: the last update's eslam_update_info, the RECORD_CONTACTS records, the
+ * ancestors and the kernel times; after a load they read as after upload_particles.
+ * Sharded filters (nranks > 1): ESLAM_ERR_UNSUPPORTED from all five calls, deliberately, as
+ * for eslam_gpu_shared_map_update (per-rank blobs and re-sharding are not built).            */
+#define ESLAM_SNAPSHOT_VERSION 1
+#define ESLAM_SNAPSHOT_GRID 0x1u
+#define ESLAM_SNAPSHOT_HASH 0x2u
+#define ESLAM_SNAPSHOT_PARTICLES 0x4u
+#define ESLAM_SNAPSHOT_SCALARS 0x8u
+#define ESLAM_SNAPSHOT_MAPS 0x10u
+typedef struct eslam_snapshot_info {
+    uint64_t bytes;                        /* size of the snapshot                          */
+    uint64_t particles, tables, pages;     /* distinct live tables / pages written          */
+    uint64_t grid_patches, hash_poses, chunks;
+    uint32_t version, sections;            /* ESLAM_SNAPSHOT_VERSION; ESLAM_SNAPSHOT_* mask  */
+} eslam_snapshot_info;
+typedef int (*eslam_write_fn)(void* user, const void* data, uint64_t bytes);  /* 0 = ok */
+typedef int (*eslam_read_fn)(void* user, void* data, uint64_t bytes);         /* 0 = ok */
+
+int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info);
+int eslam_gpu_save_stream(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info);
+int eslam_gpu_load_stream(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info);
+/* thin wrappers over the stream forms: capacity below the snapshot's size, or bytes other
+ * than the blob's own size, are ESLAM_ERR_INVALID_ARG                                      */
+int eslam_gpu_save(eslam_ctx* ctx, void* buf, uint64_t capacity, uint64_t chunk_bytes, eslam_snapshot_info* info);
+int eslam_gpu_load(eslam_ctx* ctx, const void* buf, uint64_t bytes, uint64_t chunk_bytes, eslam_snapshot_info* info);
+
 /* ---- SurfaceHash (useHash = true): pose hash of the map by terrain slope ----------------
  * SurfaceHash::create  src/SurfaceHash.hpp:155-231 on the map of eslam_gpu_set_map, with
  * the config's hash_slope_bins / hash_angular_steps (a sweep over segments x cells on the

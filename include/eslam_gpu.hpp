@@ -23,6 +23,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <istream>
+#include <ostream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -486,9 +488,98 @@ struct OdometryConfiguration {
     double distYawError = 0.01;                             // rad per metre
 };
 
+// plain values to and from a stream (EmbodiedSlamFilter::saveState / loadState)
+namespace detail {
+template <class T> inline void put(std::ostream& os, const T& v) { os.write(reinterpret_cast<const char*>(&v), sizeof(T)); }
+template <class T> inline void get(std::istream& is, T& v)
+{
+    is.read(reinterpret_cast<char*>(&v), sizeof(T));
+    if (!is) throw std::runtime_error("loadState: the stream ended early");
+}
+inline void putQ(std::ostream& os, const Quaterniond& q)
+{
+    const double v[4] = {q.w(), q.x(), q.y(), q.z()};
+    put(os, v);
+}
+inline void getQ(std::istream& is, Quaterniond& q)
+{
+    double v[4];
+    get(is, v);
+    q = Quaterniond(v[0], v[1], v[2], v[3]);
+}
+inline void putV(std::ostream& os, const Vector3d& p)
+{
+    const double v[3] = {p[0], p[1], p[2]};
+    put(os, v);
+}
+inline void getV(std::istream& is, Vector3d& p)
+{
+    double v[3];
+    get(is, v);
+    p = Vector3d(v[0], v[1], v[2]);
+}
+inline void putState(std::ostream& os, const BodyContactState& s)
+{
+    put(os, (uint64_t)s.points.size());
+    put(os, s.time);
+    for (const BodyContactPoint& p : s.points) {
+        putV(os, p.position);
+        put(os, p.contact);
+        put(os, (int32_t)p.groupId);
+        put(os, p.slip);
+    }
+}
+inline void getState(std::istream& is, BodyContactState& s)
+{
+    uint64_t n = 0;
+    get(is, n);
+    if (n > 4096) throw std::runtime_error("loadState: bad body contact state");
+    get(is, s.time);
+    s.points.resize((size_t)n);
+    for (BodyContactPoint& p : s.points) {
+        int32_t g = 0;
+        getV(is, p.position);
+        get(is, p.contact);
+        get(is, g);
+        get(is, p.slip);
+        p.groupId = g;
+    }
+}
+}  // namespace detail
+
 class FootContact {
 public:
     explicit FootContact(const OdometryConfiguration& config = OdometryConfiguration()) : config_(config) {}
+
+    // what the odometry carries from one update to the next (the configuration is the caller's)
+    void saveState(std::ostream& os) const
+    {
+        detail::put(os, (uint32_t)(has_prev_ ? 1 : 0));
+        detail::put(os, (int32_t)stance_);
+        detail::putState(os, prev_);
+        detail::putQ(os, prev_q_);
+        detail::putV(os, delta_.position);
+        detail::putQ(os, delta_.orientation);
+        detail::put(os, mean2d_);
+        detail::put(os, sigma_);
+        detail::put(os, yawVar_);
+    }
+    void loadState(std::istream& is)
+    {
+        uint32_t hp = 0;
+        int32_t st = 0;
+        detail::get(is, hp);
+        detail::get(is, st);
+        detail::getState(is, prev_);
+        detail::getQ(is, prev_q_);
+        detail::getV(is, delta_.position);
+        detail::getQ(is, delta_.orientation);
+        detail::get(is, mean2d_);
+        detail::get(is, sigma_);
+        detail::get(is, yawVar_);
+        has_prev_ = hp != 0;
+        stance_ = st;
+    }
 
     void update(const BodyContactState& state, const Quaterniond& orientation)
     {
@@ -956,6 +1047,7 @@ public:
     void init(const MlsGrid& env, const Pose& pose, bool useSharedMap = true,
               const SurfaceHashConfig& hashConfig = SurfaceHashConfig())
     {
+        hashConfig_ = hashConfig;
         filter_.reset(new PoseEstimator(odometry_, eslamConfig_, device_, hashConfig));
         filter_->setEnvironment(env, useSharedMap);
         filter_->invalidate();
@@ -997,6 +1089,55 @@ public:
         if (match) estimator().matchMaps(scanMap);
         if (update && !sharedMap_) estimator().updateMaps(scanMap);
         if (update && sharedMap_) estimator().updateSharedMap(scanMap);
+    }
+
+    // saveState / loadState: everything the filter needs to continue bit for bit -- this object's
+    // own state (the map mode, the update count, the contact odometry between two updates), then
+    // the device's snapshot through eslam_gpu_save_stream / eslam_gpu_load_stream (include/
+    // eslam_gpu.h: particles, RNG, grid, pose hash, per-particle maps).  loadState works on a
+    // filter that was only constructed (init() not called; hashConfig as init() would get it) and
+    // replaces what an initialised one holds; the two configurations are this filter's own.
+    // Failures are exceptions (std::runtime_error with the library's message).
+    void saveState(std::ostream& os, uint64_t chunkBytes = 0)
+    {
+        PoseEstimator& f = estimator();
+        f.flush();                        // edits made through getParticles()
+        detail::put(os, kStateMagic);
+        detail::put(os, (uint32_t)(sharedMap_ ? 1 : 0));
+        detail::put(os, (uint32_t)0);
+        detail::put(os, update_idx_);
+        odometry_.saveState(os);
+        detail::putState(os, last_state_);
+        detail::putQ(os, last_orientation_);
+        check(f.handle(), eslam_gpu_save_stream(f.handle(), &EmbodiedSlamFilter::writeStream, &os, chunkBytes, nullptr));
+        if (!os) throw std::runtime_error("saveState: the stream failed");
+    }
+    void loadState(std::istream& is, uint64_t chunkBytes = 0) { loadState(is, hashConfig_, chunkBytes); }
+    void loadState(std::istream& is, const SurfaceHashConfig& hashConfig, uint64_t chunkBytes = 0)
+    {
+        uint64_t magic = 0, idx = 0;
+        uint32_t shared = 0, pad = 0;
+        detail::get(is, magic);
+        if (magic != kStateMagic) throw std::runtime_error("loadState: not a filter state");
+        detail::get(is, shared);
+        detail::get(is, pad);
+        detail::get(is, idx);
+        FootContact odo = odometry_;
+        BodyContactState ls;
+        Quaterniond lo;
+        odo.loadState(is);
+        detail::getState(is, ls);
+        detail::getQ(is, lo);
+        hashConfig_ = hashConfig;
+        filter_.reset(new PoseEstimator(odometry_, eslamConfig_, device_, hashConfig));
+        check(filter_->handle(), eslam_gpu_set_particle_maps(filter_->handle(), shared ? 0 : 1));
+        check(filter_->handle(), eslam_gpu_load_stream(filter_->handle(), &EmbodiedSlamFilter::readStream, &is, chunkBytes, nullptr));
+        filter_->invalidate();
+        odometry_ = odo;
+        sharedMap_ = shared != 0;
+        update_idx_ = idx;
+        last_state_ = ls;
+        last_orientation_ = lo;
     }
 
     std::vector<PoseParticle>& getParticles() { return estimator().getParticles(); }
@@ -1046,7 +1187,21 @@ private:
         PoseEstimator& operator*() const { return *p; }
         PoseEstimator* operator->() const { return p; }
     };
+    static constexpr uint64_t kStateMagic = 0x3154534641465345ull;   // "ESFAFST1"
+    static int writeStream(void* user, const void* data, uint64_t bytes)
+    {
+        std::ostream& os = *static_cast<std::ostream*>(user);
+        os.write(static_cast<const char*>(data), (std::streamsize)bytes);
+        return os ? 0 : 1;
+    }
+    static int readStream(void* user, void* data, uint64_t bytes)
+    {
+        std::istream& is = *static_cast<std::istream*>(user);
+        is.read(static_cast<char*>(data), (std::streamsize)bytes);
+        return is ? 0 : 1;
+    }
     Configuration eslamConfig_;
+    SurfaceHashConfig hashConfig_;
     FootContact odometry_;
     int device_;
     Holder filter_;

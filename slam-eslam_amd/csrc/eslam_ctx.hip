@@ -19,6 +19,7 @@
 #include <chrono>
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <vector>
 
 #include "eslam_internal.h"
@@ -343,6 +344,15 @@ struct eslam_ctx {
     // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
     void* sm_mem = nullptr;
     uint64_t sm_bytes = 0;
+    // eslam_gpu_save / eslam_gpu_load: two pinned and two device staging slots of
+    // snap_cap bytes with their events, and the census scratch (dropped with the local maps)
+    void* snap_host[2] = {nullptr, nullptr};
+    void* snap_dev[2] = {nullptr, nullptr};
+    uint64_t snap_cap = 0;
+    hipEvent_t snap_ev[2] = {nullptr, nullptr};
+    void* snap_census = nullptr;             // first, trank, tlist, firstref, prank, plist
+    uint32_t* snap_counts = nullptr;         // the census' tile counts
+    uint64_t snap_counts_cap = 0;
     uint32_t maxp = 4;
     // host-side filter state
     uint64_t proj_event = 0, init_event = 0, hash_event = 0;
@@ -692,6 +702,8 @@ static void free_local_maps(eslam_ctx* ctx)
     (void)hipFree(ctx->lm.ctr); (void)hipFree(ctx->lm.slot); (void)hipFree(ctx->lm.page); (void)hipFree(ctx->lm.tgen);
     (void)hipFree(ctx->lm.owner); (void)hipFree(ctx->lm.frees); (void)hipFree(ctx->lm.mark);
     (void)hipFree(ctx->lm_off); (void)hipFree(ctx->lm_job); (void)hipFree(ctx->lm_codes); ctx->lm_codes_cap = 0; (void)hipFree(ctx->lm_poff); (void)hipFree(ctx->lm_pgc); (void)hipFree(ctx->match_sp);
+    (void)hipFree(ctx->snap_census); (void)hipFree(ctx->snap_counts);
+    ctx->snap_census = nullptr; ctx->snap_counts = nullptr; ctx->snap_counts_cap = 0;
     ctx->lm = LocalMaps{};
     ctx->lm_off = nullptr; ctx->lm_job = nullptr; ctx->lm_codes = nullptr; ctx->lm_poff = nullptr; ctx->lm_pgc = nullptr; ctx->match_sp = nullptr; ctx->match_cap = 0;
     ctx->lm_ready = false;
@@ -761,6 +773,11 @@ extern "C" void eslam_gpu_destroy(eslam_ctx* ctx)
         if (ctx->scan_ev[k]) (void)hipEventDestroy(ctx->scan_ev[k]);
         (void)hipHostFree(ctx->scan_host[k]);
         (void)hipFree(ctx->scan_dev[k]);
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (ctx->snap_ev[k]) (void)hipEventDestroy(ctx->snap_ev[k]);
+        (void)hipHostFree(ctx->snap_host[k]);
+        (void)hipFree(ctx->snap_dev[k]);
     }
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -3252,4 +3269,756 @@ extern "C" int eslam_gpu_selftest_math(int device, int fn, const double* x, cons
     if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
     (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
     return e == hipSuccess ? ESLAM_OK : ESLAM_ERR_HIP;
+}
+
+// ---------------------------------------------------------------------------------------
+// snapshots: eslam_gpu_save / eslam_gpu_load (kernels in eslam_snapshot.hip)
+// ---------------------------------------------------------------------------------------
+extern "C" hipError_t eslam_launch_snap_census_tables(const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t n,
+                                                      hipStream_t stream);
+extern "C" hipError_t eslam_launch_snap_census_pages(const LocalMaps* lm, const SnapCensus* c, uint64_t T, hipStream_t stream);
+extern "C" hipError_t eslam_launch_snap_pack(int what, const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t T,
+                                             uint64_t k0, uint64_t cnt, uint32_t rw, void* out, hipStream_t stream);
+extern "C" hipError_t eslam_launch_snap_unpack(int what, const LocalMaps* lm, uint64_t k0, uint64_t cnt, uint32_t rw, const void* in,
+                                               hipStream_t stream);
+extern "C" hipError_t eslam_launch_snap_finish(const LocalMaps* lm, uint64_t T, uint64_t P, hipStream_t stream);
+
+namespace {
+
+const char kSnapMagic[8] = {'E', 'S', 'L', 'A', 'M', 'S', 'N', 'P'};
+enum { kSecGrid = 0, kSecHash, kSecParticles, kSecScalars, kSecMaps, kSecCount };   // bit k of SnapHeader::sections
+struct SnapSection {
+    uint64_t off, size;
+};
+struct SnapHeader {
+    char magic[8];
+    uint32_t version, sections;
+    uint64_t bytes;
+    uint64_t n;
+    uint32_t particle_maps, local_map_trail;
+    uint32_t hx, hy;                         // the window's half-widths (0 without per-particle maps)
+    double max_sensor_range;
+    uint32_t width, height;
+    double scale_x, scale_y, offset_x, offset_y;
+    double g2l[12];
+    uint64_t n_patches;
+    uint32_t has_height, hash_bins;
+    uint64_t hash_n;
+    uint64_t tables, pages;
+    uint32_t wx, wy;
+    uint32_t row_words, pad;
+    SnapSection sec[kSecCount];
+    uint64_t reserved;
+};
+static_assert(sizeof(SnapHeader) == 336, "snapshot header");
+struct SnapScalars {
+    eslam_rng_state rng;
+    uint64_t pad;
+    int32_t wexp;
+    uint32_t minstd;
+    double max_weight;
+    uint64_t update_count;
+    double inv_n;
+};
+static_assert(sizeof(eslam_rng_state) == 280 && sizeof(SnapScalars) == 320, "snapshot scalars");
+
+inline uint64_t pad16(uint64_t b) { return (b + 15) & ~(uint64_t)15; }
+inline uint32_t snap_row_words(uint32_t W, uint32_t V) { return (4u + W + 3u * V + 3u) & ~3u; }
+constexpr uint64_t kPageBytes = DM_LM_PAGE_CELLS * sizeof(float2);
+
+// the sections' offsets and sizes that the header's counts imply (the one layout a blob may have)
+void snap_layout(const SnapHeader& h, SnapSection sec[kSecCount], uint64_t* bytes)
+{
+    uint64_t at = sizeof(SnapHeader);
+    const uint64_t ncell = (uint64_t)h.width * h.height, np = h.n_patches, n = h.n;
+    uint64_t size[kSecCount];
+    size[kSecGrid] = pad16((ncell + 1) * 4) + pad16(np * 8) + (h.has_height ? pad16(np * 4) : 0);
+    size[kSecHash] = 4 * pad16(h.hash_n * 8) + pad16(h.hash_n * 4) + pad16((uint64_t)h.hash_bins * h.hash_bins * 4);
+    size[kSecParticles] = 7 * pad16(n * 8) + pad16(n);
+    size[kSecScalars] = sizeof(SnapScalars);
+    size[kSecMaps] = pad16(n * 4) + pad16(h.tables * h.row_words * 4) + pad16(h.pages * 4) + h.pages * kPageBytes;
+    for (int k = 0; k < kSecCount; ++k) {
+        sec[k] = SnapSection{0, 0};
+        if (!(h.sections & (1u << k))) continue;
+        sec[k] = SnapSection{at, size[k]};
+        at += size[k];
+    }
+    *bytes = at;
+}
+
+enum PieceKind { PK_HOST = 0, PK_DEV, PK_SID, PK_TABLES, PK_OWNER, PK_PAGES };
+// one array of the blob: count units of unit bytes (then zeros up to 16 bytes)
+struct Piece {
+    int kind;
+    const void* src;                         // PK_HOST: host memory; PK_DEV: device memory
+    uint64_t count, unit;
+};
+
+struct SnapPlan {
+    SnapHeader h;
+    SnapScalars sc;
+    std::vector<Piece> pieces;
+    SnapCensus cen;
+    const uint32_t* sid;
+    std::vector<uint32_t> bsizes;            // the pose hash's bucket sizes
+};
+
+int snap_staging(eslam_ctx* ctx, uint64_t bytes)
+{
+    for (int k = 0; k < 2; ++k)
+        if (!ctx->snap_ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->snap_ev[k], hipEventDisableTiming));
+    if (bytes <= ctx->snap_cap) return ESLAM_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; ++k) {
+        (void)hipHostFree(ctx->snap_host[k]); ctx->snap_host[k] = nullptr;
+        (void)hipFree(ctx->snap_dev[k]); ctx->snap_dev[k] = nullptr;
+    }
+    ctx->snap_cap = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (hipHostMalloc(&ctx->snap_host[k], bytes) != hipSuccess || hipMalloc(&ctx->snap_dev[k], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no memory for the staging buffers (lower chunk_bytes)");
+        }
+    }
+    ctx->snap_cap = bytes;
+    return ESLAM_OK;
+}
+
+// the staging size for pieces of at most `largest` bytes with units of at most `unit` bytes
+uint64_t snap_stage_bytes(uint64_t chunk, uint64_t largest, uint64_t unit)
+{
+    uint64_t b = chunk < largest ? chunk : largest;
+    b = b < unit ? unit : b;
+    return pad16(b < 4096 ? 4096 : b);
+}
+
+uint64_t snap_tiles(uint64_t items) { return (items + kCompactTileItems - 1) / kCompactTileItems; }
+
+int snap_read_count(eslam_ctx* ctx, const uint32_t* dev, uint64_t* out)
+{
+    uint32_t* h = reinterpret_cast<uint32_t*>(ctx->scratch_host);
+    HIPCHK(ctx, hipMemcpyAsync(h, dev, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = *h;
+    return ESLAM_OK;
+}
+
+// the census of the per-particle maps: the live tables and pages, ranked (pl.cen), and their counts
+int snap_census(eslam_ctx* ctx, SnapPlan& pl)
+{
+    const LocalMaps& lm = ctx->lm;
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t o_first = 0, o_trank = o_first + up(lm.ntables * 4), o_tlist = o_trank + up(lm.ntables * 4),
+                   o_fref = o_tlist + up(ctx->cap * 4), o_prank = o_fref + up(lm.npages * 8), o_plist = o_prank + up(lm.npages * 4),
+                   total = o_plist + up(lm.npages * 4);
+    if (!ctx->snap_census) {                 // kept until the maps are dropped (free_local_maps)
+        if (hipMalloc(&ctx->snap_census, total) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->snap_census = nullptr;
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the census");
+        }
+    }
+    char* m = (char*)ctx->snap_census;
+    SnapCensus& c = pl.cen;
+    c.first = (uint32_t*)(m + o_first);
+    c.trank = (uint32_t*)(m + o_trank);
+    c.tlist = (uint32_t*)(m + o_tlist);
+    c.firstref = (uint64_t*)(m + o_fref);
+    c.prank = (uint32_t*)(m + o_prank);
+    c.plist = (uint32_t*)(m + o_plist);
+    const uint64_t n = ctx->n, ttiles = snap_tiles(n);
+    int rc = grow(ctx, (void**)&ctx->snap_counts, &ctx->snap_counts_cap, (ttiles + 1) * 4, false);
+    if (rc) return rc;
+    c.counts = ctx->snap_counts;
+    HIPCHK(ctx, eslam_launch_snap_census_tables(&lm, &c, pl.sid, n, ctx->stream));
+    uint64_t T = 0, P = 0;
+    rc = snap_read_count(ctx, c.counts + ttiles, &T);
+    if (rc) return rc;
+    const uint64_t ptiles = snap_tiles(T * (lm.wx * lm.wy + lm.V));
+    if (ptiles >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: the page census has 2^32 tiles or more");
+    rc = grow(ctx, (void**)&ctx->snap_counts, &ctx->snap_counts_cap, (ptiles + 1) * 4, false);
+    if (rc) return rc;
+    c.counts = ctx->snap_counts;
+    HIPCHK(ctx, eslam_launch_snap_census_pages(&lm, &c, T, ctx->stream));
+    rc = snap_read_count(ctx, c.counts + ptiles, &P);
+    if (rc) return rc;
+    pl.h.tables = T;
+    pl.h.pages = P;
+    return ESLAM_OK;
+}
+
+// settle, run a pending gather, take the census: the header, the scalars and the pieces of a save
+int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
+{
+    if (ctx->sharded)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: a sharded filter is not saved or loaded (per-rank blobs are not built)");
+    if (const int rc_ = settle(ctx)) return rc_;
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
+    int rc = materialize(ctx);
+    if (!rc) rc = read_ctl(ctx);
+    if (rc) return rc;
+    const Ctl& ctl = *ctx->ctl_host;
+    const DevState& s = ctx->st[ctl.base ^ ctl.flip];
+    SnapHeader& h = pl.h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, kSnapMagic, 8);
+    h.version = ESLAM_SNAPSHOT_VERSION;
+    h.n = ctx->n;
+    h.particle_maps = particle_maps(ctx) ? 1u : 0u;
+    h.local_map_trail = ctx->cfg.local_map_trail;
+    h.max_sensor_range = ctx->cfg.max_sensor_range;
+    h.width = ctx->map.width;
+    h.height = ctx->map.height_cells;
+    h.scale_x = ctx->map_scale[0];
+    h.scale_y = ctx->map_scale[1];
+    h.offset_x = ctx->map.offset_x;
+    h.offset_y = ctx->map.offset_y;
+    memcpy(h.g2l, ctx->map.g2l, sizeof(h.g2l));
+    h.n_patches = ctx->map_np;
+    h.has_height = ctx->d_height ? 1u : 0u;
+    h.sections = (1u << kSecGrid) | (1u << kSecParticles) | (1u << kSecScalars);
+    if (h.particle_maps) {
+        h.hx = dm_lm_half(ctx->cfg.max_sensor_range, ctx->map_scale[0]);
+        h.hy = dm_lm_half(ctx->cfg.max_sensor_range, ctx->map_scale[1]);
+    }
+    if (ctx->has_hash) {
+        h.sections |= 1u << kSecHash;
+        h.hash_n = ctx->hash_n;
+        h.hash_bins = (uint32_t)ctx->cfg.hash_slope_bins;
+        pl.bsizes.resize(ctx->hash_bstart.size() - 1);
+        for (size_t b = 0; b + 1 < ctx->hash_bstart.size(); ++b) pl.bsizes[b] = ctx->hash_bstart[b + 1] - ctx->hash_bstart[b];
+    }
+    pl.sid = s.sid;
+    if (ctx->lm_ready && ctx->n) {
+        h.sections |= 1u << kSecMaps;
+        h.wx = ctx->lm.wx;
+        h.wy = ctx->lm.wy;
+        h.row_words = snap_row_words(ctx->lm.wx * ctx->lm.wy, ctx->lm.V);
+        rc = snap_census(ctx, pl);
+        if (rc) return rc;
+    }
+    snap_layout(h, h.sec, &h.bytes);
+    // the scalars: eslam_gpu_get_rng_state's, and what the next update reads of the control block
+    SnapScalars& sc = pl.sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.rng.minstd_x = ctl.minstd;
+    sc.rng.project_count = ctx->proj_event;
+    sc.rng.init_count = ctx->init_event;
+    sc.rng.hash_count = *ctx->hash_ev;
+    sc.rng.max_weight = ctl.max_weight;
+    memcpy(sc.rng.ud_pose, ctx->ud_pose, sizeof(ctx->ud_pose));
+    memcpy(sc.rng.libc_rand, ctx->libcp->r, sizeof(sc.rng.libc_rand));
+    sc.rng.libc_rand_pos = ctx->libcp->i;
+    sc.wexp = ctl.wexp;
+    sc.minstd = ctl.minstd;
+    sc.max_weight = ctl.max_weight;
+    sc.update_count = ctl.update_count;
+    sc.inv_n = ctl.inv_n;
+    // the pieces, in the blob's order
+    std::vector<Piece>& p = pl.pieces;
+    const uint64_t ncell = (uint64_t)h.width * h.height, n = h.n;
+    p.push_back(Piece{PK_HOST, &pl.h, sizeof(SnapHeader), 1});
+    p.push_back(Piece{PK_DEV, ctx->d_cells, ncell + 1, 4});
+    p.push_back(Piece{PK_DEV, ctx->d_patch, h.n_patches, 8});
+    if (h.has_height) p.push_back(Piece{PK_DEV, ctx->d_height, h.n_patches, 4});
+    if (ctx->has_hash) {
+        for (int f = 0; f < 4; ++f) p.push_back(Piece{PK_DEV, hash_field(ctx, f), h.hash_n, 8});
+        p.push_back(Piece{PK_HOST, ctx->hash_bucket.data(), h.hash_n * 4, 1});
+        p.push_back(Piece{PK_HOST, pl.bsizes.data(), pl.bsizes.size() * 4, 1});
+    }
+    const double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
+    for (int f = 0; f < 7; ++f) p.push_back(Piece{PK_DEV, f7[f], n, 8});
+    p.push_back(Piece{PK_DEV, s.flags, n, 1});
+    p.push_back(Piece{PK_HOST, &pl.sc, sizeof(SnapScalars), 1});
+    if (h.sections & (1u << kSecMaps)) {
+        p.push_back(Piece{PK_SID, nullptr, n, 4});
+        p.push_back(Piece{PK_TABLES, nullptr, h.tables, (uint64_t)h.row_words * 4});
+        p.push_back(Piece{PK_OWNER, nullptr, h.pages, 4});
+        p.push_back(Piece{PK_PAGES, nullptr, h.pages, kPageBytes});
+    }
+    uint64_t total = 0;
+    for (const Piece& q : p) total += pad16(q.count * q.unit);
+    if (total != h.bytes) return fail(ctx, ESLAM_ERR_HIP, "snapshot: the pieces do not add up to the layout");
+    return ESLAM_OK;
+}
+
+// chunks a piece splits into: whole units, at most chunk bytes (one unit when a unit is longer);
+// the piece's padding rides on its last chunk
+uint64_t snap_units_per_chunk(const Piece& q, uint64_t chunk)
+{
+    const uint64_t u = chunk / q.unit;       // chunk is a multiple of 16: the padded last chunk fits too
+    return u ? u : 1;
+}
+
+uint64_t snap_chunk_count(const std::vector<Piece>& p, uint64_t chunk)
+{
+    uint64_t c = 0;
+    for (const Piece& q : p) {
+        if (!q.count) continue;
+        const uint64_t per = snap_units_per_chunk(q, chunk);
+        c += (q.count + per - 1) / per;
+    }
+    return c;
+}
+
+void snap_fill_info(const SnapHeader& h, uint64_t chunks, eslam_snapshot_info* info)
+{
+    if (!info) return;
+    memset(info, 0, sizeof(*info));
+    info->bytes = h.bytes;
+    info->particles = h.n;
+    info->tables = h.tables;
+    info->pages = h.pages;
+    info->grid_patches = h.n_patches;
+    info->hash_poses = h.hash_n;
+    info->chunks = chunks;
+    info->version = h.version;
+    info->sections = h.sections;
+}
+
+struct SnapChunk {
+    size_t piece;
+    uint64_t k0, cnt;
+    bool last;                               // the piece's last chunk: its padding follows
+};
+
+int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t capacity)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx || !w) return ESLAM_ERR_INVALID_ARG;
+    if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
+    const uint64_t chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
+    SnapPlan pl;
+    int rc = snap_plan(ctx, pl);
+    if (rc) return rc;
+    if (capacity < pl.h.bytes) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: the buffer is smaller than the snapshot (eslam_gpu_snapshot_size)");
+    uint64_t largest = 0, unit = 16;
+    for (const Piece& q : pl.pieces) {
+        largest = std::max(largest, pad16(q.count * q.unit));
+        unit = std::max(unit, pad16(q.unit));
+    }
+    rc = snap_staging(ctx, snap_stage_bytes(chunk, largest, unit));
+    if (rc) return rc;
+    const std::vector<Piece>& P = pl.pieces;
+    // the next chunk after (piece, k0 + cnt); piece == P.size(): none
+    auto next = [&](const SnapChunk& c) {
+        SnapChunk d = c;
+        d.k0 = c.k0 + c.cnt;
+        while (d.piece < P.size() && d.k0 >= P[d.piece].count) {
+            ++d.piece;
+            d.k0 = 0;
+        }
+        if (d.piece < P.size()) {
+            const uint64_t per = snap_units_per_chunk(P[d.piece], chunk), left = P[d.piece].count - d.k0;
+            d.cnt = left < per ? left : per;
+            d.last = d.cnt == left;
+        }
+        return d;
+    };
+    // chunk c into its slot: packed or copied on the stream into the pinned buffer, the slot's event after it
+    auto issue = [&](const SnapChunk& c, uint32_t slot) -> int {
+        const Piece& q = P[c.piece];
+        const uint64_t bytes = c.cnt * q.unit, off = c.k0 * q.unit;
+        char* host = (char*)ctx->snap_host[slot];
+        if (q.kind == PK_HOST) {
+            memcpy(host, (const char*)q.src + off, bytes);
+        } else if (q.kind == PK_DEV) {
+            HIPCHK(ctx, hipMemcpyAsync(host, (const char*)q.src + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            HIPCHK(ctx, eslam_launch_snap_pack(q.kind - PK_SID, &ctx->lm, &pl.cen, pl.sid, pl.h.tables, c.k0, c.cnt, pl.h.row_words,
+                                               ctx->snap_dev[slot], ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(host, ctx->snap_dev[slot], bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
+        return ESLAM_OK;
+    };
+    SnapChunk cur = next(SnapChunk{0, 0, 0, false});
+    uint32_t slot = 0;
+    uint64_t chunks = 0;
+    if (cur.piece < P.size()) rc = issue(cur, slot);
+    while (!rc && cur.piece < P.size()) {
+        // the device packs chunk c + 1 while the host writes chunk c
+        const SnapChunk nxt = next(cur);
+        if (nxt.piece < P.size()) rc = issue(nxt, slot ^ 1u);
+        if (rc) break;
+        HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));
+        const Piece& q = P[cur.piece];
+        uint64_t bytes = cur.cnt * q.unit;
+        if (cur.last) {                      // zeros up to the next 16-byte boundary
+            const uint64_t all = q.count * q.unit, padded = pad16(all);
+            memset((char*)ctx->snap_host[slot] + bytes, 0, padded - all);
+            bytes += padded - all;
+        }
+        if (w(user, ctx->snap_host[slot], bytes) != 0) {
+            rc = fail(ctx, ESLAM_ERR_COMM, "snapshot: the write callback failed");
+            break;
+        }
+        ++chunks;
+        cur = nxt;
+        slot ^= 1u;
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);    // a copy into the pinned buffers may be in flight
+        return rc;
+    }
+    snap_fill_info(pl.h, chunks, info);
+    return ESLAM_OK;
+}
+
+// ---- load -------------------------------------------------------------------------------
+struct SnapReader {
+    eslam_ctx* ctx;
+    eslam_read_fn r;
+    void* user;
+    uint64_t chunk;
+    uint32_t slot = 0;
+    uint64_t chunks = 0;
+};
+typedef std::function<int(const void* data, uint64_t k0, uint64_t cnt)> SnapCheck;
+
+int snap_bad(eslam_ctx* ctx, const char* msg) { return fail(ctx, ESLAM_ERR_INVALID_ARG, msg); }
+
+// one array of the blob through the staging buffers: every chunk is read into a pinned slot,
+// checked on the host (check; may be empty), and then copied to dst (PK_HOST: host memory,
+// may be null; PK_DEV: device memory) or unpacked into pool entries [k0, k0 + cnt)
+int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check)
+{
+    eslam_ctx* ctx = rd.ctx;
+    const uint64_t all = count * unit, tail = pad16(all) - all;
+    uint64_t per = rd.chunk / unit;
+    per = per ? per : 1;
+    for (uint64_t k0 = 0; k0 < count; k0 += per) {
+        const uint64_t cnt = count - k0 < per ? count - k0 : per, bytes = cnt * unit;
+        const bool last = k0 + cnt == count;
+        const uint32_t slot = rd.slot;
+        rd.slot ^= 1u;
+        HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));     // the slot's previous chunk has left it
+        char* host = (char*)ctx->snap_host[slot];
+        if (rd.r(rd.user, host, bytes + (last ? tail : 0)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
+        ++rd.chunks;
+        if (check) {
+            const int rc = check(host, k0, cnt);
+            if (rc) return rc;
+        }
+        if (kind == PK_HOST) {
+            if (dst) memcpy((char*)dst + k0 * unit, host, bytes);
+            continue;
+        }
+        if (kind == PK_DEV) {
+            HIPCHK(ctx, hipMemcpyAsync((char*)dst + k0 * unit, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            HIPCHK(ctx, hipMemcpyAsync(ctx->snap_dev[slot], host, bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, eslam_launch_snap_unpack(kind - PK_SID, &ctx->lm, k0, cnt, rw, ctx->snap_dev[slot], ctx->stream));
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
+    }
+    return ESLAM_OK;
+}
+
+int snap_check_header(eslam_ctx* ctx, const SnapHeader& h, uint64_t known_bytes)
+{
+    if (memcmp(h.magic, kSnapMagic, 8) != 0) return snap_bad(ctx, "snapshot: bad magic");
+    if (h.version != ESLAM_SNAPSHOT_VERSION) return snap_bad(ctx, "snapshot: unknown version");
+    const uint32_t need = (1u << kSecGrid) | (1u << kSecParticles) | (1u << kSecScalars);
+    if ((h.sections & need) != need || (h.sections >> kSecCount)) return snap_bad(ctx, "snapshot: section mask");
+    if (h.particle_maps > 1u || (h.particle_maps != 0u) != particle_maps(ctx))
+        return snap_bad(ctx, "snapshot: ESLAM_FLAG_PARTICLE_MAPS differs from the context's");
+    if (h.local_map_trail != ctx->cfg.local_map_trail) return snap_bad(ctx, "snapshot: local_map_trail differs from the context's");
+    if (h.n >= (1ull << 32) - 1 || h.tables > h.n || h.pages >= 0xffffffffull) return snap_bad(ctx, "snapshot: counts out of range");
+    if (!h.width || !h.height || (uint64_t)h.width * h.height >= 0xffffffffull || h.n_patches > 0xffffffffull || h.has_height > 1u)
+        return snap_bad(ctx, "snapshot: grid size");
+    if (!(h.scale_x > 0.0) || !(h.scale_y > 0.0) || !dm_isfinite(h.scale_x) || !dm_isfinite(h.scale_y))
+        return snap_bad(ctx, "snapshot: grid scale");
+    const bool hash = (h.sections >> kSecHash) & 1u, maps = (h.sections >> kSecMaps) & 1u;
+    if (hash ? (h.hash_bins == 0 || h.hash_bins > 4096 || h.hash_bins != (uint32_t)ctx->cfg.hash_slope_bins || h.hash_n >= (1ull << 32))
+             : (h.hash_bins != 0 || h.hash_n != 0))
+        return snap_bad(ctx, "snapshot: pose hash size (hash_slope_bins differs from the context's?)");
+    if (h.particle_maps) {
+        const double r = ctx->cfg.max_sensor_range;
+        if (!(r == r) || r < 0.0 || r > 1e6) return snap_bad(ctx, "max_sensor_range must be finite and >= 0");
+        if (h.hx != dm_lm_half(r, h.scale_x) || h.hy != dm_lm_half(r, h.scale_y))
+            return snap_bad(ctx, "snapshot: max_sensor_range (the window's half-widths) differs from the context's");
+        if (h.local_map_trail > 4096) return snap_bad(ctx, "local_map_trail: at most 4096 tiles");
+    } else if (h.hx || h.hy) {
+        return snap_bad(ctx, "snapshot: window without per-particle maps");
+    }
+    if (maps != (h.particle_maps && h.n > 0)) return snap_bad(ctx, "snapshot: per-particle map section");
+    if (maps) {
+        if (h.wx != 2 * h.hx + 1 || h.wy != 2 * h.hy + 1 || h.row_words != snap_row_words(h.wx * h.wy, h.local_map_trail))
+            return snap_bad(ctx, "snapshot: table row size");
+    } else if (h.tables || h.pages || h.wx || h.wy || h.row_words) {
+        return snap_bad(ctx, "snapshot: tables without a map section");
+    }
+    SnapSection sec[kSecCount];
+    uint64_t bytes = 0;
+    snap_layout(h, sec, &bytes);
+    for (int k = 0; k < kSecCount; ++k)
+        if (sec[k].off != h.sec[k].off || sec[k].size != h.sec[k].size)
+            return snap_bad(ctx, "snapshot: a section's offset or size does not match the header's counts");
+    if (bytes != h.bytes || (known_bytes && known_bytes != h.bytes)) return snap_bad(ctx, "snapshot: size does not match the header (truncated?)");
+    if (maps) {
+        const uint64_t per = ctx->cfg.local_map_pages ? ctx->cfg.local_map_pages : kDefaultMapPages;
+        if (h.pages > (h.n ? h.n : 1) * per)
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: more live pages than the context's pool holds (raise eslam_config.local_map_pages)");
+    }
+    return ESLAM_OK;
+}
+
+int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known_bytes)
+{
+    if (known_bytes && known_bytes < sizeof(SnapHeader)) return snap_bad(ctx, "snapshot: shorter than its header");
+    if (rd.r(rd.user, &h, sizeof(h)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
+    ++rd.chunks;
+    int rc = snap_check_header(ctx, h, known_bytes);
+    if (rc) return rc;
+    const uint64_t ncell = (uint64_t)h.width * h.height, np = h.n_patches, n = h.n;
+    const bool hash = (h.sections >> kSecHash) & 1u, maps = (h.sections >> kSecMaps) & 1u;
+    uint64_t largest = std::max(std::max((ncell + 1) * 4, np * 8), std::max(n * 8, h.hash_n * 8));
+    largest = std::max(largest, std::max(h.tables * h.row_words * 4, h.pages * kPageBytes));
+    rc = snap_staging(ctx, snap_stage_bytes(rd.chunk, pad16(largest), pad16(std::max<uint64_t>(kPageBytes, (uint64_t)h.row_words * 4))));
+    if (rc) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    free_particles(ctx);                     // whatever the context held goes first
+    const SnapCheck none;
+    // ---- the shared grid: through eslam_gpu_set_map (occ and cell_tab rebuilt as there)
+    {
+        std::vector<uint32_t> cells(ncell + 1);
+        std::vector<float2> patch(np);
+        std::vector<float> mean(np ? np : 1), stdev(np ? np : 1), height;
+        uint32_t prev = 0;
+        rc = snap_read(rd, PK_HOST, cells.data(), ncell + 1, 4, 0, [&](const void* d, uint64_t k0, uint64_t cnt) {
+            const uint32_t* c = (const uint32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k) {
+                if (c[k] < prev || c[k] > np || (k0 + k == 0 && c[k] != 0)) return snap_bad(ctx, "snapshot: the grid's cell_start is not a prefix sum");
+                prev = c[k];
+            }
+            return (int)ESLAM_OK;
+        });
+        if (!rc && prev != np) rc = snap_bad(ctx, "snapshot: cell_start[width*height] != n_patches");
+        if (!rc) rc = snap_read(rd, PK_HOST, patch.data(), np, 8, 0, none);
+        if (!rc && h.has_height) {
+            height.resize(np ? np : 1);
+            rc = snap_read(rd, PK_HOST, height.data(), np, 4, 0, none);
+        }
+        if (rc) return rc;
+        for (uint64_t k = 0; k < np; ++k) {
+            mean[k] = patch[k].x;
+            stdev[k] = patch[k].y;
+        }
+        eslam_mls_grid g;
+        memset(&g, 0, sizeof(g));
+        g.width = h.width;
+        g.height = h.height;
+        g.scale_x = h.scale_x;
+        g.scale_y = h.scale_y;
+        g.offset_x = h.offset_x;
+        g.offset_y = h.offset_y;
+        memcpy(g.global2local, h.g2l, sizeof(h.g2l));
+        g.cell_start = cells.data();
+        g.n_patches = np;
+        g.patch_mean = mean.data();
+        g.patch_stdev = stdev.data();
+        g.patch_height = h.has_height ? height.data() : nullptr;
+        rc = eslam_gpu_set_map(ctx, &g);
+        if (rc) return rc;
+    }
+    // ---- the pose hash: restored, not recomputed
+    if (hash) {
+        const uint64_t hn = h.hash_n, cap = hn ? hn : 1;
+        const uint32_t nb = h.hash_bins * h.hash_bins;
+        (void)hipFree(ctx->d_hash); ctx->d_hash = nullptr;
+        (void)hipFree(ctx->d_hash_blist); ctx->d_hash_blist = nullptr;
+        ctx->hash_n = 0;
+        if (hipMalloc(&ctx->d_hash, sizeof(double) * 4 * cap) != hipSuccess || hipMalloc(&ctx->d_hash_blist, sizeof(uint32_t) * cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash pose buffers");
+        }
+        for (int f = 0; f < 4 && !rc; ++f) rc = snap_read(rd, PK_DEV, ctx->d_hash + (uint64_t)f * cap, hn, 8, 0, none);
+        std::vector<int32_t> bucket(hn);
+        std::vector<uint32_t> sizes(nb), bstart(nb + 1, 0u);
+        if (!rc) rc = snap_read(rd, PK_HOST, bucket.data(), hn, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
+            const int32_t* b = (const int32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k)
+                if (b[k] < 0 || (uint32_t)b[k] >= nb) return snap_bad(ctx, "snapshot: a hash pose's bucket is out of range");
+            return (int)ESLAM_OK;
+        });
+        if (!rc) rc = snap_read(rd, PK_HOST, sizes.data(), nb, 4, 0, none);
+        if (rc) return rc;
+        for (uint64_t i = 0; i < hn; ++i) bstart[bucket[i] + 1]++;
+        for (uint32_t b = 0; b < nb; ++b) {
+            if (bstart[b + 1] != sizes[b]) return snap_bad(ctx, "snapshot: the hash's bucket sizes do not match its buckets");
+            bstart[b + 1] += bstart[b];
+        }
+        std::vector<uint32_t> blist(cap), fill(bstart.begin(), bstart.end() - 1);
+        for (uint64_t i = 0; i < hn; ++i) blist[fill[bucket[i]]++] = (uint32_t)i;
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (hn) HIPCHK(ctx, hipMemcpy(ctx->d_hash_blist, blist.data(), sizeof(uint32_t) * hn, hipMemcpyHostToDevice));
+        ctx->hash_bucket.swap(bucket);
+        ctx->hash_bstart.swap(bstart);
+        ctx->hash_n = hn;
+        ctx->has_hash = true;
+    }
+    // ---- the particles (the eight arrays of the current buffer, into buffer 0)
+    rc = alloc_particles(ctx, n);
+    if (rc) return rc;
+    if (maps && !ctx->lm_ready) return fail(ctx, ESLAM_ERR_HIP, "snapshot: per-particle maps not allocated");
+    {
+        const DevState& s = ctx->st[0];
+        double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
+        for (int f = 0; f < 7 && !rc; ++f) rc = snap_read(rd, PK_DEV, f7[f], n, 8, 0, none);
+        if (!rc) rc = snap_read(rd, PK_DEV, s.flags, n, 1, 0, none);
+        if (rc) return rc;
+    }
+    // ---- the scalars
+    SnapScalars sc;
+    rc = snap_read(rd, PK_HOST, &sc, sizeof(sc), 1, 0, none);
+    if (!rc) rc = reset_ctl_for_new_particles(ctx, sc.wexp);
+    if (rc) return rc;
+    {
+        Ctl& ctl = *ctx->ctl_host;           // as reset_ctl_for_new_particles read it
+        ctl.minstd = sc.minstd;
+        ctl.max_weight = sc.max_weight;
+        ctl.update_count = sc.update_count;
+        ctl.inv_n = sc.inv_n;
+        if (maps) {
+            ctl.pg_cursor = 0;
+            ctl.pg_nfree = ctx->lm.npages - h.pages;
+            ctl.pg_total = 0;
+            ctl.pg_gc = 0;
+        }
+        ctx->proj_event = sc.rng.project_count;
+        ctx->init_event = sc.rng.init_count;
+        *ctx->hash_ev = sc.rng.hash_count;
+        memcpy(ctx->ud_pose, sc.rng.ud_pose, sizeof(ctx->ud_pose));
+        memcpy(ctx->libcp->r, sc.rng.libc_rand, sizeof(sc.rng.libc_rand));
+        ctx->libcp->i = sc.rng.libc_rand_pos % 34u;
+        rc = write_ctl(ctx);
+        if (rc) return rc;
+        ctx->dbg_valid = false;
+    }
+    // ---- the per-particle maps: table k into pool entry k, page k into pool entry k
+    if (maps) {
+        const uint64_t T = h.tables, P = h.pages;
+        const uint32_t rw = h.row_words, W = h.wx * h.wy, V = h.local_map_trail;
+        rc = snap_read(rd, PK_DEV, ctx->st[0].sid, n, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
+            const uint32_t* v = (const uint32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k)
+                if (v[k] >= T) return snap_bad(ctx, "snapshot: a particle names a table past the snapshot's tables");
+            return (int)ESLAM_OK;
+        });
+        if (!rc) rc = snap_read(rd, PK_TABLES, nullptr, T, (uint64_t)rw * 4, rw, [&](const void* d, uint64_t, uint64_t cnt) {
+            const uint32_t* v = (const uint32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k) {
+                const uint32_t* r = v + k * rw;
+                if (r[2] > 1u || r[3] > V) return snap_bad(ctx, "snapshot: a table's shadow flag or trail mark is out of range");
+                for (uint32_t s = 0; s < W; ++s)
+                    if (r[4 + s] != DM_LM_NONE && r[4 + s] >= P) return snap_bad(ctx, "snapshot: a window slot names a page past the snapshot's pages");
+                for (uint32_t e = 0; e < V; ++e) {
+                    const uint32_t pg = r[4 + W + 3 * e + 2];
+                    if (pg != DM_LM_NONE && pg >= P) return snap_bad(ctx, "snapshot: a trail entry names a page past the snapshot's pages");
+                }
+            }
+            return (int)ESLAM_OK;
+        });
+        if (!rc) rc = snap_read(rd, PK_OWNER, nullptr, P, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
+            const uint32_t* v = (const uint32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k)
+                if (v[k] != DM_LM_NONE && v[k] >= T) return snap_bad(ctx, "snapshot: a page's owner is past the snapshot's tables");
+            return (int)ESLAM_OK;
+        });
+        if (!rc) rc = snap_read(rd, PK_DEV, ctx->lm.page, P, kPageBytes, 0, none);
+        if (rc) return rc;
+        HIPCHK(ctx, eslam_launch_snap_finish(&ctx->lm, T, P, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ESLAM_OK;
+}
+
+int snap_load(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t known_bytes)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx || !r) return ESLAM_ERR_INVALID_ARG;
+    if (ctx->sharded)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: a sharded filter is not saved or loaded (per-rank blobs are not built)");
+    if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
+    if (const int rc_ = settle(ctx)) return rc_;
+    SnapReader rd;
+    rd.ctx = ctx;
+    rd.r = r;
+    rd.user = user;
+    rd.chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
+    SnapHeader h;
+    memset(&h, 0, sizeof(h));
+    const int rc = snap_load_body(ctx, rd, h, known_bytes);
+    if (rc) {
+        // the context reads as "no particles"; set_map + init_* or another load starts it over
+        const std::string msg = ctx->err;
+        (void)hipStreamSynchronize(ctx->stream);
+        free_particles(ctx);
+        ctx->err = msg;
+        return rc;
+    }
+    snap_fill_info(h, rd.chunks, info);
+    return ESLAM_OK;
+}
+
+struct SnapMem {
+    char* p;
+    uint64_t left;
+};
+int snap_mem_write(void* user, const void* data, uint64_t bytes)
+{
+    SnapMem* m = (SnapMem*)user;
+    if (bytes > m->left) return 1;
+    memcpy(m->p, data, bytes);
+    m->p += bytes;
+    m->left -= bytes;
+    return 0;
+}
+int snap_mem_read(void* user, void* data, uint64_t bytes)
+{
+    SnapMem* m = (SnapMem*)user;
+    if (bytes > m->left) return 1;
+    memcpy(data, m->p, bytes);
+    m->p += bytes;
+    m->left -= bytes;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx || !info) return ESLAM_ERR_INVALID_ARG;
+    SnapPlan pl;
+    const int rc = snap_plan(ctx, pl);
+    if (rc) return rc;
+    snap_fill_info(pl.h, snap_chunk_count(pl.pieces, kSnapDefaultChunk), info);
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_save_stream(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
+{
+    return snap_save(ctx, w, user, chunk_bytes, info, ~0ull);
+}
+
+extern "C" int eslam_gpu_load_stream(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
+{
+    return snap_load(ctx, r, user, chunk_bytes, info, 0);
+}
+
+extern "C" int eslam_gpu_save(eslam_ctx* ctx, void* buf, uint64_t capacity, uint64_t chunk_bytes, eslam_snapshot_info* info)
+{
+    if (!buf) return ESLAM_ERR_INVALID_ARG;
+    SnapMem m{(char*)buf, capacity};
+    return snap_save(ctx, snap_mem_write, &m, chunk_bytes, info, capacity);
+}
+
+extern "C" int eslam_gpu_load(eslam_ctx* ctx, const void* buf, uint64_t bytes, uint64_t chunk_bytes, eslam_snapshot_info* info)
+{
+    if (!buf) return ESLAM_ERR_INVALID_ARG;
+    SnapMem m{(char*)const_cast<void*>(buf), bytes};
+    return snap_load(ctx, snap_mem_read, &m, chunk_bytes, info, bytes ? bytes : 1);
 }

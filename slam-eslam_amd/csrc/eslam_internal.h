@@ -421,6 +421,19 @@ struct SmScratch {
 enum SmCounter : uint32_t { kSmFused = 0, kSmAbsorbed, kSmInserted, kSmTouched, kSmRunPlaced, kSmCounters = 8 };
 constexpr uint64_t kSmDefaultRecords = 1ull << 21;   // max_records = 0: 64 MiB of scratch
 
+// ---- snapshots (eslam_gpu_save / eslam_gpu_load, eslam_snapshot.hip) ---------
+// the census of a save: the live tables and pages and their compact ids in canonical order
+struct SnapCensus {
+    uint32_t* first;                     // per pool table: the lowest particle naming it (0xffffffff: none)
+    uint32_t* trank;                     // per pool table: its compact id
+    uint32_t* tlist;                     // per compact id: the pool table (n entries)
+    uint64_t* firstref;                  // per pool page: the lowest key (table rank x (W + V) + word) naming it
+    uint32_t* prank;                     // per pool page: its compact id
+    uint32_t* plist;                     // per compact id: the pool page
+    uint32_t* counts;                    // the compactions' tile counts
+};
+constexpr uint64_t kSnapDefaultChunk = 64ull << 20;
+
 // logDebug records of the last update (k_contact_records), indexed by the particle's
 // position during that update: meas 4 doubles (x, y, zPos, theta), ncp, and maxc contact
 // points of 6 doubles (surface point xyz, zdiff, zvar, prob)

@@ -17,6 +17,7 @@ ERR_HIP = -6
 ERR_NOT_INITIALISED = -7
 ERR_UNSUPPORTED = -8
 ERR_OUT_OF_MEMORY = -9
+ERR_COMM = -10
 
 FLAG_RECORD_ANCESTORS = 0x1
 FLAG_NO_MAP_LDS = 0x2
@@ -224,6 +225,41 @@ class KernelTimes(C.Structure):
         ("map_plan_ms", C.c_float),
         ("map_match_ms", C.c_float),
     ]
+
+
+SNAPSHOT_VERSION = 1
+SNAPSHOT_GRID, SNAPSHOT_HASH, SNAPSHOT_PARTICLES, SNAPSHOT_SCALARS, SNAPSHOT_MAPS = 0x1, 0x2, 0x4, 0x8, 0x10
+
+
+class SnapshotInfo(C.Structure):
+    """eslam_snapshot_info (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("bytes", C.c_uint64),
+        ("particles", C.c_uint64),
+        ("tables", C.c_uint64),
+        ("pages", C.c_uint64),
+        ("grid_patches", C.c_uint64),
+        ("hash_poses", C.c_uint64),
+        ("chunks", C.c_uint64),
+        ("version", C.c_uint32),
+        ("sections", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)     # eslam_write_fn
+READ_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)      # eslam_read_fn
+
+# the snapshot entry points of include/eslam_gpu.h (after the eslam_ctx*): name -> argument types
+SNAPSHOT_PROTOTYPES = {
+    "eslam_gpu_snapshot_size": [C.POINTER(SnapshotInfo)],
+    "eslam_gpu_save_stream": [WRITE_FN, C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
+    "eslam_gpu_load_stream": [READ_FN, C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
+    "eslam_gpu_save": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SnapshotInfo)],
+    "eslam_gpu_load": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SnapshotInfo)],
+}
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)

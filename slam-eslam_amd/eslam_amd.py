@@ -109,12 +109,29 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_init_hash.argtypes = [vp, C.c_uint64]
     L.eslam_gpu_hash_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.eslam_gpu_hash_poses.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    for name, args in A.SNAPSHOT_PROTOTYPES.items():     # a library without them is an error at the call
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [vp] + args
     _lib = L
     return L
 
 
 def _dv(v):
     return (C.c_double * len(v))(*v)
+
+
+_SNAP_HEADER = 336
+
+
+class _SnapshotGrid:
+    """The grid geometry in a snapshot's header: what get_map() needs of the
+    GridArrays a set_map() would have left."""
+
+    def __init__(self, head):
+        d = np.frombuffer(head[64:192], "<f8")
+        self.scale = (float(d[0]), float(d[1]))
+        self.offset = (float(d[2]), float(d[3]))
+        self.g2l = [float(v) for v in d[4:16]]
 
 
 class GpuFilter:
@@ -333,6 +350,77 @@ class GpuFilter:
 
     def set_rng_state(self, s):
         self._check(self.L.eslam_gpu_set_rng_state(self.h, C.byref(s)))
+
+    # -- snapshots -------------------------------------------------------------
+    def snapshot_info(self):
+        """eslam_gpu_snapshot_size: the size and counts of the snapshot a save would write now"""
+        info = A.SnapshotInfo()
+        self._check(self.L.eslam_gpu_snapshot_size(self.h, C.byref(info)))
+        return info
+
+    def save_state(self, chunk_bytes=0, file=None):
+        """eslam_gpu_save: the whole filter as one blob (np.ndarray[uint8]); with `file` (an
+        object with write()) the chunks go to it through eslam_gpu_save_stream instead and the
+        SnapshotInfo is returned.  `last_snapshot` holds the call's SnapshotInfo."""
+        info = A.SnapshotInfo()
+        if file is None:
+            size = self.snapshot_info().bytes
+            blob = np.zeros(size, np.uint8)
+            self._check(self.L.eslam_gpu_save(self.h, blob.ctypes.data_as(C.c_void_p), size, chunk_bytes, C.byref(info)))
+            self.last_snapshot = info
+            return blob
+        failed = []
+
+        def write(_user, data, nbytes):
+            try:
+                file.write(C.string_at(data, nbytes))
+                return 0
+            except Exception as e:           # the C side reports ESLAM_ERR_COMM
+                failed.append(e)
+                return 1
+
+        cb = A.WRITE_FN(write)
+        rc = self.L.eslam_gpu_save_stream(self.h, cb, None, chunk_bytes, C.byref(info))
+        if rc != 0:
+            e = EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+            e.__cause__ = failed[0] if failed else None
+            raise e
+        self.last_snapshot = info
+        return info
+
+    def load_state(self, blob=None, chunk_bytes=0, file=None):
+        """eslam_gpu_load: replace whatever the filter holds by a snapshot (bytes, bytearray or a
+        uint8 array; or `file`, an object with read(), through eslam_gpu_load_stream).  Works on
+        a filter that was only created.  Returns the SnapshotInfo."""
+        info = A.SnapshotInfo()
+        if file is None:
+            a = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if not isinstance(blob, np.ndarray) else blob, dtype=np.uint8)
+            rc = self.L.eslam_gpu_load(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0], chunk_bytes, C.byref(info))
+            head = a[:_SNAP_HEADER].tobytes()
+        else:
+            heads = []
+
+            def read(_user, data, nbytes):
+                try:
+                    b = file.read(nbytes)
+                    if len(b) != nbytes:
+                        return 1
+                    if not heads:
+                        heads.append(b)
+                    C.memmove(data, b, nbytes)
+                    return 0
+                except Exception:
+                    return 1
+
+            cb = A.READ_FN(read)
+            rc = self.L.eslam_gpu_load_stream(self.h, cb, None, chunk_bytes, C.byref(info))
+            head = heads[0] if heads else b""
+        if rc != 0:
+            self._grid = None
+            raise EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+        self._grid = _SnapshotGrid(head)     # the geometry get_map() reports
+        self.last_snapshot = info
+        return info
 
     def enable_timing(self, on=True):
         self._check(self.L.eslam_gpu_enable_timing(self.h, 1 if on else 0))
