@@ -1866,4 +1866,160 @@ DM_FN int dm_mls_gate(float meanf, float stdevf, float heightf, double q_mean, d
     return diff * diff < 9.0 * (ps * ps + q_var);
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* the scan MLS from a sensor reading (eslam_gpu_scan_from_laser / _depth)  */
+/* ------------------------------------------------------------------------------------ */
+/* what a reading's points share: the transforms, the squared sigmas and the scan grid    */
+typedef struct dm_scan_frame {
+    double Rs[9], ts[3];                 /* sensor2body                                        */
+    double Rw[9];                        /* removeYaw(orientation) as a matrix                 */
+    double a[3];                         /* (R_w R_s2b).row(2)                                 */
+    double ss[3], sb[3];                 /* sensor_rot_sigma^2, body_rot_sigma^2               */
+    double min_var;                      /* min_sigma^2                                        */
+    double res, inv_res, thickness, max_range;
+    uint32_t half, width;                /* the grid: width = 2 half cells a side, cell (0, 0) of the
+                                            scan frame at (half, half)                         */
+} dm_scan_frame;
+#define DM_SCAN_MAX_HALF 32767u          /* (2 * 32767)^2 < 2^32 - 1 cells                     */
+#define DM_SCAN_VALID 0
+#define DM_SCAN_INVALID 1
+#define DM_SCAN_OUT_OF_RANGE 2
+
+/* sensor2body (3x4 row-major), R_w, the sigmas and the grid for points within `reach` metres of
+ * the sensor (max_sensor_range times the widest ray's length per unit depth); 0 when the grid
+ * would pass DM_SCAN_MAX_HALF (or reach is not finite)                                        */
+DM_FN int dm_scan_frame_init(dm_scan_frame* f, const double s2b[12], const double Rw[9], const double ssig[3],
+                             const double bsig[3], double min_sigma, double res, double thickness, double max_range,
+                             double reach)
+{
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            f->Rs[r * 3 + c] = s2b[r * 4 + c];
+            f->Rw[r * 3 + c] = Rw[r * 3 + c];
+        }
+        f->ts[r] = s2b[r * 4 + 3];
+        f->ss[r] = ssig[r] * ssig[r];
+        f->sb[r] = bsig[r] * bsig[r];
+    }
+    for (int c = 0; c < 3; ++c) f->a[c] = (Rw[6] * f->Rs[c] + Rw[7] * f->Rs[3 + c]) + Rw[8] * f->Rs[6 + c];
+    f->min_var = min_sigma * min_sigma;
+    f->res = res;
+    f->inv_res = 1.0 / res;
+    f->thickness = thickness;
+    f->max_range = max_range;
+    const double tn = dm_sqrt((f->ts[0] * f->ts[0] + f->ts[1] * f->ts[1]) + f->ts[2] * f->ts[2]);
+    const double h = dm_floor((reach + tn) * f->inv_res) + 2.0;
+    if (!(h <= (double)DM_SCAN_MAX_HALF)) return 0;
+    f->half = (uint32_t)h;
+    f->width = 2u * f->half;
+    return 1;
+}
+/* the longest ray of a depth image per unit depth: |(x, y, 1)| at the corner farthest from the axis */
+DM_FN double dm_scan_depth_ray(uint32_t width, uint32_t height, double sx, double sy, double cx, double cy)
+{
+    const double x0 = dm_fabs(cx), x1 = dm_fabs((double)(width - 1u) * sx + cx);
+    const double y0 = dm_fabs(cy), y1 = dm_fabs((double)(height - 1u) * sy + cy);
+    const double x = x0 > x1 ? x0 : x1, y = y0 > y1 ? y0 : y1;
+    return dm_sqrt((x * x + y * y) + 1.0);
+}
+/* laser beam i in the sensor frame */
+DM_FN int dm_scan_laser_point(const dm_scan_frame* f, double start_angle, double angular_resolution, uint32_t min_range,
+                              uint32_t max_range, uint32_t i, uint32_t range, double q[3])
+{
+    q[0] = q[1] = q[2] = 0.0;
+    if (!(range > 5u && range >= min_range && range <= max_range)) return DM_SCAN_INVALID;
+    const double r = (double)range * 1e-3;
+    if (r > f->max_range) return DM_SCAN_OUT_OF_RANGE;
+    const double ang = start_angle + (double)i * angular_resolution;
+    double sn, co;
+    dm_sincos(ang, &sn, &co);
+    q[0] = r * co;
+    q[1] = r * sn;
+    return DM_SCAN_VALID;
+}
+/* depth pixel (u, v) in the sensor frame */
+DM_FN int dm_scan_depth_point(const dm_scan_frame* f, double sx, double sy, double cx, double cy, uint32_t u, uint32_t v,
+                              float depth, double q[3])
+{
+    q[0] = q[1] = q[2] = 0.0;
+    const double d = (double)depth;
+    if (!(dm_isfinite(d) && d > 0.0)) return DM_SCAN_INVALID;
+    if (d > f->max_range) return DM_SCAN_OUT_OF_RANGE;
+    q[0] = ((double)u * sx + cx) * d;
+    q[1] = ((double)v * sy + cy) * d;
+    q[2] = d;
+    return DM_SCAN_VALID;
+}
+/* a sensor-frame point in the yaw-free body frame: its height, the height's variance and its
+ * cell (my * width + mx); 0 when it falls off the grid                                       */
+DM_FN int dm_scan_place(const dm_scan_frame* f, const double q[3], double* pz, double* var, uint32_t* cell)
+{
+    const double* Rs = f->Rs;
+    const double* Rw = f->Rw;
+    const double bx = ((Rs[0] * q[0] + Rs[1] * q[1]) + Rs[2] * q[2]) + f->ts[0];
+    const double by = ((Rs[3] * q[0] + Rs[4] * q[1]) + Rs[5] * q[2]) + f->ts[1];
+    const double bz = ((Rs[6] * q[0] + Rs[7] * q[1]) + Rs[8] * q[2]) + f->ts[2];
+    const double px = (Rw[0] * bx + Rw[1] * by) + Rw[2] * bz;
+    const double py = (Rw[3] * bx + Rw[4] * by) + Rw[5] * bz;
+    *pz = (Rw[6] * bx + Rw[7] * by) + Rw[8] * bz;
+    /* row(2) . (e_k x v): k = x: r2 vy - r1 vz, y: r0 vz - r2 vx, z: r1 vx - r0 vy */
+    const double* a = f->a;
+    const double gs0 = a[2] * q[1] - a[1] * q[2], gs1 = a[0] * q[2] - a[2] * q[0], gs2 = a[1] * q[0] - a[0] * q[1];
+    const double gb0 = Rw[8] * by - Rw[7] * bz, gb1 = Rw[6] * bz - Rw[8] * bx, gb2 = Rw[7] * bx - Rw[6] * by;
+    double v = f->ss[0] * (gs0 * gs0);
+    v = v + f->ss[1] * (gs1 * gs1);
+    v = v + f->ss[2] * (gs2 * gs2);
+    v = v + f->sb[0] * (gb0 * gb0);
+    v = v + f->sb[1] * (gb1 * gb1);
+    v = v + f->sb[2] * (gb2 * gb2);
+    *var = v < f->min_var ? f->min_var : v;
+    const double mx = dm_floor(px * f->inv_res) + (double)f->half;
+    const double my = dm_floor(py * f->inv_res) + (double)f->half;
+    const double w = (double)f->width;
+    *cell = 0u;
+    if (!((mx >= 0.0) & (mx < w) & (my >= 0.0) & (my < w))) return 0;
+    *cell = (uint32_t)my * f->width + (uint32_t)mx;
+    return 1;
+}
+/* the orderable key of (float)z: ascending keys = ascending floats, -0 as +0 */
+DM_FN uint32_t dm_scan_zkey(double z)
+{
+    float zf = (float)z;
+    if (zf == 0.0f) zf = 0.0f;
+    const uint32_t u = dm_fbits(zf);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+/* the centre of a cell's column or row m (0 .. width - 1) */
+DM_FN double dm_scan_cell_centre(const dm_scan_frame* f, uint32_t m)
+{
+    return (((double)m - (double)f->half) + 0.5) * f->res;
+}
+/* One cluster of a cell: n points in canonical order starting at z[0], var[0] (stride in
+ * elements), joined while z[k] - z[k - 1] <= thickness; *len = its points, mu and stdev its
+ * patch.  Sums are sequential.                                                             */
+DM_FN uint32_t dm_scan_cluster_len(const double* z, uint32_t n, double thickness)
+{
+    uint32_t k = 1;
+    while (k < n && z[k] - z[k - 1] <= thickness) ++k;
+    return k;
+}
+DM_FN void dm_scan_cluster_patch(const double* z, const double* var, uint32_t len, double* mu, double* stdev)
+{
+    double sw = 0.0, swz = 0.0;
+    for (uint32_t k = 0; k < len; ++k) {
+        const double w = 1.0 / var[k];
+        sw = sw + w;
+        swz = swz + w * z[k];
+    }
+    const double m = swz / sw;
+    double sd = 0.0;
+    for (uint32_t k = 0; k < len; ++k) {
+        const double w = 1.0 / var[k];
+        const double d = z[k] - m;
+        sd = sd + w * (d * d);
+    }
+    *mu = m;
+    *stdev = dm_sqrt(1.0 / sw + sd / sw);
+}
+
 #endif /* ESLAM_DETMATH_H */

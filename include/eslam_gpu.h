@@ -359,6 +359,85 @@ int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64
 int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* mean, float* stdev, float* patch_height,
                       uint64_t patch_capacity);
 
+/* ---- the scan MLS from a sensor reading ------------------------------------
+ * EmbodiedSlamFilter::update(body2odometry, LaserScan, laser2body) and
+ * update(body2odometry, DistanceImage, camera2body) (src/EmbodiedSlamFilter.cpp:311-351,
+ * 239-309) hand the reading to envire's ScanMeshing / DistanceGridToPointcloud and MLSProjection,
+ * which are not in the reference tree; the rule below is this build's (parity unpinned).  All
+ * arithmetic is fp64 of eslam_detmath.h, no contraction.
+ *   points   laser beam i: a = start_angle + i * angular_resolution, r = ranges[i] * 1e-3,
+ *            q = (r cos a, r sin a, 0) (dm_sincos); valid when ranges[i] > 5 (the error codes) and
+ *            min_range <= ranges[i] <= max_range; dropped (out of range) when r > max_sensor_range.
+ *            depth pixel (u, v), d = data[v * width + u]: q = ((u scale_x + center_x) d,
+ *            (v scale_y + center_y) d, d); valid when d is finite and > 0; dropped when
+ *            d > max_sensor_range.
+ *   placed   b = R_s2b q + t_s2b, p = R_w b with R_w = removeYaw(orientation): the yaw-free body
+ *            frame of eslam_scan_patch.
+ *   variance of p.z, first order in small rotation errors: about sensor axis e_k (sigma
+ *            sensor_rot_sigma[k]) g = (R_w R_s2b).row(2) . (e_k x q); about body axis e_k (sigma
+ *            body_rot_sigma[k]) g = R_w.row(2) . (e_k x b); var = sum sigma_k^2 g_k^2 over the six,
+ *            at least min_sigma^2.
+ *   cells    (floor(p.x / resolution), floor(p.y / resolution)) on a square grid centred on the
+ *            scan frame's origin that holds every valid point (sized from max_sensor_range, the
+ *            image's widest ray and |t_s2b|; below 2^32 - 1 cells, else ESLAM_ERR_INVALID_ARG).
+ *   patches  a cell's points by ((float)p.z, point index) ascending; a point joins the current
+ *            cluster when p.z - the previous p.z <= patch_thickness; a cluster's patch is the
+ *            inverse-variance mean: w = 1 / var, mu = sum w z / sum w, v = 1 / sum w +
+ *            sum w (z - mu)^2 / sum w, sums sequential in that order; position = (cell centre,
+ *            mu), stdev = sqrt(v).  Patches come out by cell index (y-major), then by cluster.
+ * The result does not depend on how the device splits the work.  Out of the rule: negative
+ * information (gridUseNegativeInformation), the texture image, update(Featurecloud*).          */
+typedef struct eslam_scan_params {
+    double sensor2body[12];                /* laser2body / camera2body, 3x4 row-major         */
+    double orientation[4];                 /* body2odometry's rotation, quaternion (w, x, y, z) */
+    double sensor_rot_sigma[3];            /* (5 deg, 0, 0)  src/EmbodiedSlamFilter.cpp:323-325 */
+    double body_rot_sigma[3];              /* (3 deg, 3 deg, 0)  :332-334                      */
+    double min_sigma;                      /* 1e-3 (the z-sigma floor of :124); > 0            */
+    double resolution;                     /* Configuration::gridResolution (0.05)             */
+    double patch_thickness;                /* Configuration::gridPatchThickness (0.1)          */
+    double max_sensor_range;               /* Configuration::maxSensorRange                    */
+} eslam_scan_params;
+/* identity transforms, the sigmas above, resolution 0.05, thickness 0.1, cfg's max_sensor_range */
+int eslam_scan_params_default(const eslam_config* cfg, eslam_scan_params* p);
+
+typedef struct eslam_laser_scan {          /* base::samples::LaserScan                         */
+    double start_angle, angular_resolution;    /* radians                                      */
+    uint32_t min_range, max_range;         /* millimetres                                      */
+    uint32_t n;
+    uint32_t pad;
+    const uint32_t* ranges;                /* n, millimetres (1..5: error codes)               */
+} eslam_laser_scan;
+
+typedef struct eslam_depth_image {         /* base::samples::DistanceImage                     */
+    uint32_t width, height;
+    double scale_x, scale_y, center_x, center_y;
+    const float* data;                     /* width * height, row-major, metres                */
+} eslam_depth_image;
+
+typedef struct eslam_scan_info {
+    uint64_t points;                       /* beams or pixels                                  */
+    uint64_t points_valid;                 /* points binned                                    */
+    uint64_t points_invalid;
+    uint64_t points_out_of_range;          /* valid readings beyond max_sensor_range           */
+    uint64_t cells;                        /* cells with a point                               */
+    uint64_t patches;
+} eslam_scan_info;
+
+/* Synchronous; the patches stay on the device with the context until the next build.  They need
+ * no map and no particles and change neither; on a sharded filter they are rank-local (every
+ * rank given the same reading holds the same patches).  A reading without a valid point
+ * succeeds with 0 patches.  ESLAM_ERR_INVALID_ARG (with a message): null pointers, non-finite
+ * transforms, orientations or sigmas, min_sigma, resolution, patch_thickness or
+ * max_sensor_range <= 0, a zero-size image, non-finite image scales, more than 2^30 points.
+ * info may be NULL.                                                                          */
+int eslam_gpu_scan_from_laser(eslam_ctx* ctx, const eslam_laser_scan* scan, const eslam_scan_params* params,
+                              eslam_scan_info* info);
+int eslam_gpu_scan_from_depth(eslam_ctx* ctx, const eslam_depth_image* image, const eslam_scan_params* params,
+                              eslam_scan_info* info);
+/* the last built scan: *count = its patches, the first min(capacity, *count) copied to out
+ * (out may be NULL with capacity 0)                                                          */
+int eslam_gpu_scan_patches(eslam_ctx* ctx, eslam_scan_patch* out, uint64_t capacity, uint64_t* count);
+
 /* ---- PoseParticle records with the debug fields (getParticles() for logging / viz) ------ */
 /* ContactPoint  src/PoseParticle.hpp:20-43: one contact point evaluatePose pushed           */
 typedef struct eslam_cpoint {

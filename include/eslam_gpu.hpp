@@ -656,6 +656,45 @@ struct ScanPatch {
     double stdev = 0.0;
 };
 
+// base::samples::LaserScan / base::samples::DistanceImage: the fields the scan MLS is built from
+// (DESIGN.md 5f), under their own names
+struct LaserScan {
+    double start_angle = 0;               // radians, the first beam
+    double angular_resolution = 0;        // radians between beams
+    std::vector<uint32_t> ranges;         // millimetres; 1..5 are error codes
+    uint32_t minRange = 0, maxRange = 0;  // millimetres
+};
+
+struct DistanceImage {
+    uint32_t width = 0, height = 0;
+    double scale_x = 1, scale_y = 1, center_x = 0, center_y = 0;   // x = (u scale_x + center_x) d
+    std::vector<float> data;              // width * height, row-major, metres
+};
+
+template <class LS> LaserScan toLaserScan(const LS& s)
+{
+    LaserScan o;
+    o.start_angle = s.start_angle;
+    o.angular_resolution = s.angular_resolution;
+    o.ranges.assign(s.ranges.begin(), s.ranges.end());
+    o.minRange = s.minRange;
+    o.maxRange = s.maxRange;
+    return o;
+}
+
+template <class DI> DistanceImage toDistanceImage(const DI& d)
+{
+    DistanceImage o;
+    o.width = d.width;
+    o.height = d.height;
+    o.scale_x = d.scale_x;
+    o.scale_y = d.scale_y;
+    o.center_x = d.center_x;
+    o.center_y = d.center_y;
+    o.data.assign(d.data.begin(), d.data.end());
+    return o;
+}
+
 struct SurfaceHash {                      // src/SurfaceHash.hpp:155-231: built on the device
     SurfaceHashConfig config;
     void setConfiguration(const SurfaceHashConfig& c) { config = c; }
@@ -733,6 +772,74 @@ public:
         eslam_shared_merge_info info;
         check(ctx_, eslam_gpu_shared_map_update(ctx_, p.data(), (uint32_t)p.size(), maxRecords, &info));
         return info;
+    }
+
+    // The scan's MLS from a sensor reading, built on the device (eslam_gpu_scan_from_laser /
+    // eslam_gpu_scan_from_depth): what the reference's ScanMeshing /
+    // DistanceGridToPointcloud and MLSProjection hand to processMap.  sensor2body is laser2body
+    // or camera2body, orientation the body's (body2odometry's rotation); the grid's resolution,
+    // the patch thickness and the range come from the Configuration, the sigmas are the
+    // reference's (src/EmbodiedSlamFilter.cpp:280-296, 322-336).
+    eslam_scan_params scanParams(const Affine3d& sensor2body, const Quaterniond& orientation) const
+    {
+        eslam_scan_params p;
+        const eslam_config c = config_.toC();
+        eslam_scan_params_default(&c, &p);
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) p.sensor2body[4 * r + k] = sensor2body.linear()(r, k);
+            p.sensor2body[4 * r + 3] = sensor2body.translation()[r];
+        }
+        p.orientation[0] = orientation.w(); p.orientation[1] = orientation.x();
+        p.orientation[2] = orientation.y(); p.orientation[3] = orientation.z();
+        p.resolution = config_.gridResolution;
+        p.patch_thickness = config_.gridPatchThickness;
+        p.max_sensor_range = config_.maxSensorRange;
+        return p;
+    }
+    std::vector<ScanPatch> scanFromLaser(const LaserScan& scan, const Affine3d& laser2body, const Quaterniond& orientation,
+                                         eslam_scan_info* info = nullptr)
+    {
+        const eslam_scan_params p = scanParams(laser2body, orientation);
+        eslam_laser_scan s;
+        std::memset(&s, 0, sizeof(s));
+        s.start_angle = scan.start_angle;
+        s.angular_resolution = scan.angular_resolution;
+        s.min_range = scan.minRange;
+        s.max_range = scan.maxRange;
+        s.n = (uint32_t)scan.ranges.size();
+        s.ranges = scan.ranges.data();
+        check(ctx_, eslam_gpu_scan_from_laser(ctx_, &s, &p, info));
+        return lastScan();
+    }
+    std::vector<ScanPatch> scanFromDistanceImage(const DistanceImage& image, const Affine3d& camera2body,
+                                                 const Quaterniond& orientation, eslam_scan_info* info = nullptr)
+    {
+        if (image.data.size() != (size_t)image.width * image.height)
+            throw std::runtime_error("DistanceImage: data does not hold width * height pixels");
+        const eslam_scan_params p = scanParams(camera2body, orientation);
+        eslam_depth_image d;
+        std::memset(&d, 0, sizeof(d));
+        d.width = image.width;
+        d.height = image.height;
+        d.scale_x = image.scale_x; d.scale_y = image.scale_y;
+        d.center_x = image.center_x; d.center_y = image.center_y;
+        d.data = image.data.data();
+        check(ctx_, eslam_gpu_scan_from_depth(ctx_, &d, &p, info));
+        return lastScan();
+    }
+    // the last built scan's patches (eslam_gpu_scan_patches)
+    std::vector<ScanPatch> lastScan()
+    {
+        uint64_t n = 0;
+        check(ctx_, eslam_gpu_scan_patches(ctx_, nullptr, 0, &n));
+        std::vector<eslam_scan_patch> raw(n);
+        if (n) check(ctx_, eslam_gpu_scan_patches(ctx_, raw.data(), n, &n));
+        std::vector<ScanPatch> out(raw.size());
+        for (size_t k = 0; k < raw.size(); ++k) {
+            out[k].position = Vector3d(raw[k].position[0], raw[k].position[1], raw[k].position[2]);
+            out[k].stdev = raw[k].stdev;
+        }
+        return out;
     }
 
     // init(numParticles, hash)  src/PoseEstimator.cpp:75-86 (the hash is built on the device
@@ -1056,6 +1163,7 @@ public:
         const double q[4] = {pose.orientation.w(), pose.orientation.x(), pose.orientation.y(), pose.orientation.z()};
         check(filter_->handle(), eslam_gpu_init_pose(filter_->handle(), p, q));
         update_idx_ = 0;
+        resetMappingPoses();
     }
 
     // update(body2odometry, bs, ltc)  src/EmbodiedSlamFilter.cpp:353-369: odometry.update,
@@ -1077,6 +1185,37 @@ public:
         return updated != 0;
     }
 
+    // update(body2odometry, scan, laser2body)  src/EmbodiedSlamFilter.cpp:311-351: when the laser
+    // has moved past mappingThreshold since the last mapped scan (mapPose), the scan's MLS is
+    // built on the device (PoseEstimator::scanFromLaser) and goes through
+    // processMap(scan, useVisualUpdate, !sharedMap) -- with the shared map the laser only matches,
+    // it does not merge
+    bool update(const Affine3d& body2odometry, const LaserScan& scan, const Affine3d& laser2body)
+    {
+        if (!eslamConfig_.mappingThreshold.test(mapPose_.inverse() * body2odometry * laser2body)) return false;
+        const Quaterniond orientation(body2odometry.linear());
+        const std::vector<ScanPatch> scanMap = estimator().scanFromLaser(scan, laser2body, orientation, &lastScanInfo_);
+        processMap(scanMap, eslamConfig_.useVisualUpdate, !sharedMap_);
+        mapPose_ = body2odometry * laser2body;
+        return true;
+    }
+
+    // update(body2odometry, dimage, camera2body)  src/EmbodiedSlamFilter.cpp:239-309: gated by
+    // mappingCameraThreshold on stereoPose; the image's MLS always merges
+    // (processMap(scan, false, true)), into the shared grid or into every particle's map.  The
+    // texture image of the reference's signature is not taken.
+    bool update(const Affine3d& body2odometry, const DistanceImage& dimage, const Affine3d& camera2body)
+    {
+        if (!eslamConfig_.mappingCameraThreshold.test(stereoPose_.inverse() * body2odometry * camera2body)) return false;
+        const Quaterniond orientation(body2odometry.linear());
+        const std::vector<ScanPatch> scanMap = estimator().scanFromDistanceImage(dimage, camera2body, orientation, &lastScanInfo_);
+        processMap(scanMap, false, true);
+        stereoPose_ = body2odometry * camera2body;
+        return true;
+    }
+    // the counters of the last scan one of the two overloads above built
+    const eslam_scan_info& lastScanInfo() const { return lastScanInfo_; }
+
     // processMap(scanMap, match, update)  src/EmbodiedSlamFilter.cpp:179-232 with the scan's
     // MLS as patches: match weights every particle against its map first -- the shared grid
     // (useSharedMap = true: the laser path's match-only call, :342-344) or its own map (the
@@ -1097,6 +1236,8 @@ public:
     // eslam_gpu.h: particles, RNG, grid, pose hash, per-particle maps).  loadState works on a
     // filter that was only constructed (init() not called; hashConfig as init() would get it) and
     // replaces what an initialised one holds; the two configurations are this filter's own.
+    // mapPose and stereoPose (the gates of the laser and camera updates) are not carried: after
+    // loadState they read as after init, so the next scan and the next image map.
     // Failures are exceptions (std::runtime_error with the library's message).
     void saveState(std::ostream& os, uint64_t chunkBytes = 0)
     {
@@ -1138,6 +1279,7 @@ public:
         update_idx_ = idx;
         last_state_ = ls;
         last_orientation_ = lo;
+        resetMappingPoses();              // not in the state: the next scan and image map, as after init
     }
 
     std::vector<PoseParticle>& getParticles() { return estimator().getParticles(); }
@@ -1200,8 +1342,18 @@ private:
         is.read(static_cast<char*>(data), (std::streamsize)bytes);
         return is ? 0 : 1;
     }
+    // udPose = mapPose = stereoPose = Translation(1000, 0, 0)  src/EmbodiedSlamFilter.cpp:128 (udPose
+    // lives in the library): the first scan and the first image always map
+    void resetMappingPoses()
+    {
+        mapPose_ = stereoPose_ = Affine3d::Identity();
+        mapPose_.translation() = stereoPose_.translation() = Vector3d(1000, 0, 0);
+        std::memset(&lastScanInfo_, 0, sizeof(lastScanInfo_));
+    }
     Configuration eslamConfig_;
     SurfaceHashConfig hashConfig_;
+    Affine3d mapPose_, stereoPose_;
+    eslam_scan_info lastScanInfo_ = {};
     FootContact odometry_;
     int device_;
     Holder filter_;

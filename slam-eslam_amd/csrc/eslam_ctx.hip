@@ -76,6 +76,12 @@ extern "C" hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl*
                                             const SmScratch* s, hipStream_t stream);
 extern "C" hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl* ctl, const SmRun* run, const SmGrid* cur,
                                             const SmGrid* next, const SmScratch* s, hipStream_t stream);
+extern "C" size_t eslam_scan_work_bytes(uint64_t n, void* mem, ScanWork* w);
+extern "C" hipError_t eslam_launch_scan_order(const dm_scan_frame* f, const ScanReading* rd, const ScanWork* w, hipStream_t stream);
+extern "C" hipError_t eslam_launch_scan_count(const dm_scan_frame* f, const ScanWork* w, uint32_t nheads, uint32_t nbinned,
+                                              hipStream_t stream);
+extern "C" hipError_t eslam_launch_scan_emit(const dm_scan_frame* f, const ScanWork* w, uint32_t nheads, uint32_t nbinned,
+                                             eslam_scan_patch* out, hipStream_t stream);
 extern "C" hipError_t eslam_launch_weight_stats(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, Shard* shards,
                                                 hipStream_t stream);
 extern "C" hipError_t eslam_launch_finalize(Shard* recs, int nrec, Ctl* ctl, const FinParams* fp, hipStream_t stream);
@@ -344,6 +350,13 @@ struct eslam_ctx {
     // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
     void* sm_mem = nullptr;
     uint64_t sm_bytes = 0;
+    // eslam_gpu_scan_from_laser / _depth: the build's scratch (ScanWork) and the last
+    // built scan's patches, both kept between calls
+    void* scan_mem = nullptr;
+    uint64_t scan_bytes = 0;
+    eslam_scan_patch* scan_out = nullptr;
+    uint64_t scan_out_cap = 0;               // patches scan_out has room for
+    uint64_t scan_count = 0;                 // patches of the last built scan
     // eslam_gpu_save / eslam_gpu_load: two pinned and two device staging slots of
     // snap_cap bytes with their events, and the census scratch (dropped with the local maps)
     void* snap_host[2] = {nullptr, nullptr};
@@ -765,6 +778,7 @@ extern "C" void eslam_gpu_destroy(eslam_ctx* ctx)
     (void)hipFree(ctx->d_hash); (void)hipFree(ctx->d_hash_blist); (void)hipFree(ctx->d_sort); (void)hipFree(ctx->sort_tmp); (void)hipFree(ctx->d_draws);
     (void)hipFree(ctx->hsend); (void)hipFree(ctx->hrecv); (void)hipFree(ctx->hsort);
     (void)hipFree(ctx->sm_mem);
+    (void)hipFree(ctx->scan_mem); (void)hipFree(ctx->scan_out);
     for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ring) if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->mring) if (e) (void)hipEventDestroy(e);
@@ -2203,6 +2217,169 @@ extern "C" int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* me
     if (patch_height) {
         if (ctx->d_height) HIPCHK(ctx, hipMemcpy(patch_height, ctx->d_height, np * 4, hipMemcpyDeviceToHost));
         else memset(patch_height, 0, np * 4);
+    }
+    return ESLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the scan MLS from a sensor reading (kernels in eslam_scan.hip)
+// ---------------------------------------------------------------------------------------
+extern "C" int eslam_scan_params_default(const eslam_config* cfg, eslam_scan_params* p)
+{
+    if (!p) return ESLAM_ERR_INVALID_ARG;
+    memset(p, 0, sizeof(*p));
+    p->sensor2body[0] = p->sensor2body[5] = p->sensor2body[10] = 1.0;
+    p->orientation[0] = 1.0;
+    p->sensor_rot_sigma[0] = 5.0 / 180.0 * M_PI;       // scanAngleSigma  src/EmbodiedSlamFilter.cpp:281, 323
+    p->body_rot_sigma[0] = p->body_rot_sigma[1] = 3.0 / 180.0 * M_PI;   // pitchRollSigma  :290, 332
+    p->min_sigma = 1e-3;                               // :124
+    p->resolution = 0.05;                              // Configuration::gridResolution
+    p->patch_thickness = 0.1;                          // Configuration::gridPatchThickness
+    p->max_sensor_range = cfg ? cfg->max_sensor_range : 3.0;
+    return ESLAM_OK;
+}
+
+// the frame of a build from the caller's parameters (reach: see dm_scan_frame_init)
+static int scan_frame(eslam_ctx* ctx, const eslam_scan_params* p, double ray, dm_scan_frame* f)
+{
+    bool fin = true;
+    for (int i = 0; i < 12; ++i) fin = fin && dm_isfinite(p->sensor2body[i]);
+    for (int i = 0; i < 4; ++i) fin = fin && dm_isfinite(p->orientation[i]);
+    for (int i = 0; i < 3; ++i) fin = fin && dm_isfinite(p->sensor_rot_sigma[i]) && dm_isfinite(p->body_rot_sigma[i]);
+    fin = fin && dm_isfinite(p->min_sigma) && dm_isfinite(p->resolution) && dm_isfinite(p->patch_thickness) &&
+          dm_isfinite(p->max_sensor_range) && dm_isfinite(ray);
+    if (!fin) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: transforms, sigmas and sizes must be finite");
+    if (!(p->min_sigma > 0.0)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: min_sigma must be positive");
+    if (!(p->resolution > 0.0) || !(p->patch_thickness > 0.0) || !(p->max_sensor_range > 0.0))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: resolution, patch_thickness and max_sensor_range must be positive");
+    // R_w = removeYaw(orientation), as fill_step_params compensates the feet
+    double yc[4], Rw[9];
+    remove_yaw(p->orientation, yc);
+    q_to_mat(yc, Rw);
+    if (!dm_scan_frame_init(f, p->sensor2body, Rw, p->sensor_rot_sigma, p->body_rot_sigma, p->min_sigma, p->resolution,
+                            p->patch_thickness, p->max_sensor_range, p->max_sensor_range * ray))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: the scan grid would pass 2^32 - 1 cells (resolution too fine for the range)");
+    return ESLAM_OK;
+}
+
+// a buffer of at least `bytes`: the new one exists before the old one goes, so a failed
+// allocation leaves the context with what it had
+static int scan_grow(eslam_ctx* ctx, void** buf, uint64_t* cap, uint64_t bytes, uint64_t unit, const char* what)
+{
+    if (bytes <= *cap * unit) return ESLAM_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t want = bytes + bytes / 4;
+    want = (want + unit - 1) / unit;
+    void* nb = nullptr;
+    if (hipMalloc(&nb, want * unit) != hipSuccess) {
+        (void)hipGetLastError();
+        want = (bytes + unit - 1) / unit;
+        if (hipMalloc(&nb, want * unit) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, what);
+        }
+    }
+    (void)hipFree(*buf);
+    *buf = nb;
+    *cap = want;
+    return ESLAM_OK;
+}
+
+static int scan_build(eslam_ctx* ctx, const dm_scan_frame* f, ScanReading* rd, const void* host_raw, eslam_scan_info* info)
+{
+    const uint64_t n = rd->n;
+    ctx->scan_count = 0;
+    if (info) info->points = n;
+    if (!n) return ESLAM_OK;
+    const uint64_t need = eslam_scan_work_bytes(n, nullptr, nullptr);
+    if (const int rc_ = scan_grow(ctx, &ctx->scan_mem, &ctx->scan_bytes, need, 1, "scan: no device memory for the build's scratch"))
+        return rc_;
+    ScanWork w;
+    (void)eslam_scan_work_bytes(n, ctx->scan_mem, &w);
+    HIPCHK(ctx, hipMemcpyAsync(w.raw, host_raw, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    rd->raw = w.raw;
+    HIPCHK(ctx, eslam_launch_scan_order(f, rd, &w, ctx->stream));
+    uint64_t cnt[kScanCounters] = {};
+    uint32_t nheads = 0, total = 0;
+    HIPCHK(ctx, hipMemcpyAsync(cnt, w.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&nheads, w.b + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `host_raw` is the caller's
+    const uint64_t binned = n - cnt[kScanInvalid] - cnt[kScanOutOfRange];
+    if (info) {
+        info->points_valid = binned;
+        info->points_invalid = cnt[kScanInvalid];
+        info->points_out_of_range = cnt[kScanOutOfRange];
+        info->cells = nheads;
+    }
+    if (!nheads) return ESLAM_OK;
+    HIPCHK(ctx, eslam_launch_scan_count(f, &w, nheads, (uint32_t)binned, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&total, w.a + nheads, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc_ = scan_grow(ctx, (void**)&ctx->scan_out, &ctx->scan_out_cap, (uint64_t)total * sizeof(eslam_scan_patch),
+                                  sizeof(eslam_scan_patch), "scan: no device memory for the patches"))
+        return rc_;
+    HIPCHK(ctx, eslam_launch_scan_emit(f, &w, nheads, (uint32_t)binned, ctx->scan_out, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->scan_count = total;
+    if (info) info->patches = total;
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_scan_from_laser(eslam_ctx* ctx, const eslam_laser_scan* scan, const eslam_scan_params* params,
+                                         eslam_scan_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (!scan || !params || (scan->n && !scan->ranges)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: null argument");
+    if (!dm_isfinite(scan->start_angle) || !dm_isfinite(scan->angular_resolution))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: the angles must be finite");
+    if (scan->n > kScanMaxPoints) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: more than 2^30 beams");
+    dm_scan_frame f;
+    if (const int rc_ = scan_frame(ctx, params, 1.0, &f)) return rc_;
+    ScanReading rd = {};
+    rd.depth = 0;
+    rd.n = scan->n;
+    rd.start_angle = scan->start_angle;
+    rd.angular_resolution = scan->angular_resolution;
+    rd.min_range = scan->min_range;
+    rd.max_range = scan->max_range;
+    rd.width = 1;
+    return scan_build(ctx, &f, &rd, scan->ranges, info);
+}
+
+extern "C" int eslam_gpu_scan_from_depth(eslam_ctx* ctx, const eslam_depth_image* image, const eslam_scan_params* params,
+                                         eslam_scan_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (!image || !params || !image->data) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: null argument");
+    if (!image->width || !image->height) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: a zero-size image");
+    if ((uint64_t)image->width * image->height > kScanMaxPoints)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: more than 2^30 pixels");
+    if (!dm_isfinite(image->scale_x) || !dm_isfinite(image->scale_y) || !dm_isfinite(image->center_x) ||
+        !dm_isfinite(image->center_y))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: the image's scales and centres must be finite");
+    dm_scan_frame f;
+    const double ray = dm_scan_depth_ray(image->width, image->height, image->scale_x, image->scale_y, image->center_x,
+                                         image->center_y);
+    if (const int rc_ = scan_frame(ctx, params, ray, &f)) return rc_;
+    ScanReading rd = {};
+    rd.depth = 1;
+    rd.n = image->width * image->height;
+    rd.width = image->width;
+    rd.sx = image->scale_x; rd.sy = image->scale_y; rd.cx = image->center_x; rd.cy = image->center_y;
+    return scan_build(ctx, &f, &rd, image->data, info);
+}
+
+extern "C" int eslam_gpu_scan_patches(eslam_ctx* ctx, eslam_scan_patch* out, uint64_t capacity, uint64_t* count)
+{
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (!count || (!out && capacity)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_patches: null argument");
+    *count = ctx->scan_count;
+    const uint64_t m = capacity < ctx->scan_count ? capacity : ctx->scan_count;
+    if (m) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpy(out, ctx->scan_out, m * sizeof(eslam_scan_patch), hipMemcpyDeviceToHost));
     }
     return ESLAM_OK;
 }

@@ -421,6 +421,37 @@ struct SmScratch {
 enum SmCounter : uint32_t { kSmFused = 0, kSmAbsorbed, kSmInserted, kSmTouched, kSmRunPlaced, kSmCounters = 8 };
 constexpr uint64_t kSmDefaultRecords = 1ull << 21;   // max_records = 0: 64 MiB of scratch
 
+// ---- the scan MLS from a sensor reading (eslam_gpu_scan_from_*, eslam_scan.hip) --
+// the reading: a laser scan (ranges) or a depth image (float bits), n points
+struct ScanReading {
+    uint32_t depth;                      // 0: laser, 1: depth image
+    uint32_t n;
+    const uint32_t* raw;                 // device: ranges (mm) or the image's float words
+    double start_angle, angular_resolution;
+    uint32_t min_range, max_range;
+    uint32_t width, pad;
+    double sx, sy, cx, cy;
+};
+// the scratch of a build, carved from one allocation of the context (scan_work_bytes); the u32
+// arrays have n + 1 words and are reused from stage to stage as eslam_scan.hip lists
+struct ScanWork {
+    uint32_t* a;                         // the points' cells (ncell: not binned); later the clusters per segment
+    uint32_t* b;                         // their z keys; the cells in z order; the head flags and their scan
+    uint32_t* c;                         // the point indices; after the second sort, the points in canonical order
+    uint32_t* d;                         // sorted keys of both sorts (the cells, in the end)
+    uint32_t* e;                         // the points in z order; later the segments' first positions
+    double* pz;                          // per point: height and its variance
+    double* var;
+    double* sz;                          // the same in canonical order
+    double* sv;
+    uint64_t* cnt;                       // kScanInvalid, kScanOutOfRange
+    uint32_t* raw;                       // the reading
+    void* sort_tmp;
+    size_t sort_tmp_bytes;
+};
+enum ScanCounter : uint32_t { kScanInvalid = 0, kScanOutOfRange, kScanCounters = 4 };
+constexpr uint64_t kScanMaxPoints = 1ull << 30;
+
 // ---- snapshots (eslam_gpu_save / eslam_gpu_load, eslam_snapshot.hip) ---------
 // the census of a save: the live tables and pages and their compact ids in canonical order
 struct SnapCensus {

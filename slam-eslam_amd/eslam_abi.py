@@ -142,6 +142,83 @@ class SharedMergeInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ScanParams(C.Structure):
+    """eslam_scan_params: how a sensor reading becomes the scan MLS"""
+    _fields_ = [
+        ("sensor2body", C.c_double * 12),
+        ("orientation", C.c_double * 4),
+        ("sensor_rot_sigma", C.c_double * 3),
+        ("body_rot_sigma", C.c_double * 3),
+        ("min_sigma", C.c_double),
+        ("resolution", C.c_double),
+        ("patch_thickness", C.c_double),
+        ("max_sensor_range", C.c_double),
+    ]
+
+
+class LaserScan(C.Structure):
+    """eslam_laser_scan: base::samples::LaserScan (ranges in millimetres)"""
+    _fields_ = [
+        ("start_angle", C.c_double),
+        ("angular_resolution", C.c_double),
+        ("min_range", C.c_uint32),
+        ("max_range", C.c_uint32),
+        ("n", C.c_uint32),
+        ("pad", C.c_uint32),
+        ("ranges", C.POINTER(C.c_uint32)),
+    ]
+
+
+class DepthImage(C.Structure):
+    """eslam_depth_image: base::samples::DistanceImage (row-major float metres)"""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("scale_x", C.c_double),
+        ("scale_y", C.c_double),
+        ("center_x", C.c_double),
+        ("center_y", C.c_double),
+        ("data", C.POINTER(C.c_float)),
+    ]
+
+
+class ScanInfo(C.Structure):
+    """eslam_scan_info: the counters of eslam_gpu_scan_from_laser / _depth"""
+    _fields_ = [
+        ("points", C.c_uint64),
+        ("points_valid", C.c_uint64),
+        ("points_invalid", C.c_uint64),
+        ("points_out_of_range", C.c_uint64),
+        ("cells", C.c_uint64),
+        ("patches", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+def laser_scan(ranges, start_angle, angular_resolution, min_range, max_range):
+    """(eslam_laser_scan, the uint32 array it points into -- keep it alive)"""
+    import numpy as np
+    r = np.ascontiguousarray(ranges, dtype=np.uint32)
+    s = LaserScan()
+    s.start_angle, s.angular_resolution = float(start_angle), float(angular_resolution)
+    s.min_range, s.max_range, s.n = int(min_range), int(max_range), int(r.size)
+    s.ranges = r.ctypes.data_as(C.POINTER(C.c_uint32))
+    return s, r
+
+
+def depth_image(data, scale_x, scale_y, center_x, center_y):
+    """(eslam_depth_image of a (height, width) float array, the float32 array it points into)"""
+    import numpy as np
+    d = np.ascontiguousarray(data, dtype=np.float32)
+    im = DepthImage()
+    im.height, im.width = (int(d.shape[0]), int(d.shape[1])) if d.ndim == 2 else (0, 0)
+    im.scale_x, im.scale_y, im.center_x, im.center_y = float(scale_x), float(scale_y), float(center_x), float(center_y)
+    im.data = d.ctypes.data_as(C.POINTER(C.c_float))
+    return im, d
+
+
 class CPoint(C.Structure):
     """eslam_cpoint: ContactPoint (src/PoseParticle.hpp:20-43)"""
     _fields_ = [

@@ -74,6 +74,11 @@ def load_library(path=LIB_PATH):
                                          C.POINTER(C.c_int)]
         L.eslam_gpu_get_map.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.c_uint64]
+    if hasattr(L, "eslam_gpu_scan_from_laser"):          # absent from older builds (A/B runs)
+        L.eslam_scan_params_default.argtypes = [C.POINTER(A.Config), C.POINTER(A.ScanParams)]
+        L.eslam_gpu_scan_from_laser.argtypes = [vp, C.POINTER(A.LaserScan), C.POINTER(A.ScanParams), C.POINTER(A.ScanInfo)]
+        L.eslam_gpu_scan_from_depth.argtypes = [vp, C.POINTER(A.DepthImage), C.POINTER(A.ScanParams), C.POINTER(A.ScanInfo)]
+        L.eslam_gpu_scan_patches.argtypes = [vp, C.POINTER(A.ScanPatch), C.c_uint64, C.POINTER(C.c_uint64)]
     L.eslam_gpu_set_particle_maps.argtypes = [vp, C.c_int]
     L.eslam_gpu_get_particle_map.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]
@@ -232,6 +237,41 @@ class GpuFilter:
             e.info = info
             raise e
         return info
+
+    def scan_params(self):
+        """eslam_scan_params_default for this filter's configuration (A.ScanParams)"""
+        p = A.ScanParams()
+        self.L.eslam_scan_params_default(C.byref(self.cfg), C.byref(p))
+        return p
+
+    def scan_patches(self):
+        """eslam_gpu_scan_patches: the last built scan (a ctypes array of eslam_scan_patch, as the
+        map updates take it)"""
+        n = C.c_uint64()
+        self._check(self.L.eslam_gpu_scan_patches(self.h, None, 0, C.byref(n)))
+        out = (A.ScanPatch * n.value)()
+        if n.value:
+            self._check(self.L.eslam_gpu_scan_patches(self.h, out, n.value, C.byref(n)))
+        return out
+
+    def scan_from_laser(self, ranges, start_angle, angular_resolution, min_range, max_range, params=None):
+        """eslam_gpu_scan_from_laser: the scan MLS of a laser scan (ranges: uint32 millimetres),
+        built on the device; returns (ScanPatch array, ScanInfo).  params: A.ScanParams
+        (default: scan_params())."""
+        s, _keep = A.laser_scan(ranges, start_angle, angular_resolution, min_range, max_range)
+        p = params if params is not None else self.scan_params()
+        info = A.ScanInfo()
+        self._check(self.L.eslam_gpu_scan_from_laser(self.h, C.byref(s), C.byref(p), C.byref(info)))
+        return self.scan_patches(), info
+
+    def scan_from_depth(self, data, scale_x, scale_y, center_x, center_y, params=None):
+        """eslam_gpu_scan_from_depth: the scan MLS of a distance image (data: (height, width)
+        float metres), built on the device; returns (ScanPatch array, ScanInfo)."""
+        im, _keep = A.depth_image(data, scale_x, scale_y, center_x, center_y)
+        p = params if params is not None else self.scan_params()
+        info = A.ScanInfo()
+        self._check(self.L.eslam_gpu_scan_from_depth(self.h, C.byref(im), C.byref(p), C.byref(info)))
+        return self.scan_patches(), info
 
     def get_map(self):
         """eslam_gpu_get_map: the shared grid as the device holds it (GridArrays with the
