@@ -155,7 +155,9 @@ typedef struct eslam_step_input {
     double position_error_zz;
     double sample_mean[3];
     double sample_cov[9];
-    uint32_t n_contacts;
+    uint32_t n_contacts;                   /* contacts[] entries used; a value above
+                                            * ESLAM_MAX_CONTACTS is clamped to it (the step
+                                            * equals the one given ESLAM_MAX_CONTACTS)       */
     uint32_t ltc_count;                    /* terrain classifications given (gate only)      */
     eslam_contact_point contacts[ESLAM_MAX_CONTACTS];
 } eslam_step_input;

@@ -1426,6 +1426,15 @@ static int or_update_weights(or_filter* f, const eslam_step_input* in, or_phase*
             double zvar = f->zs[OD(i)] * f->zs[OD(i)];
             or_cm_update_z(&cm, &f->z[OD(i)], &zvar);
             f->zs[OD(i)] = sqrt(zvar);
+            if (!f->literal && cm.ncp == 0) {
+                /* accepted without a contact point (minContacts = 0): delta = 0 * (1 / 0) and
+                 * poseVar = 0 / 0, so zPos and zSigma are NaN.  The sign and payload of a NaN
+                 * that an invalid operation generates, and which of two NaN operands an add
+                 * returns, belong to the processor and the compiler, not to the reference:
+                 * the contract stores the canonical quiet NaN */
+                f->z[OD(i)] = dm_from_bits(0x7ff8000000000000ull);
+                f->zs[OD(i)] = dm_from_bits(0x7ff8000000000000ull);
+            }
             const double weight = cm.weight;
             f->w[OD(i)] *= weight;
             f->mprob[OD(i)] = weight;

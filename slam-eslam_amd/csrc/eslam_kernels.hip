@@ -1164,6 +1164,13 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
                     zvar = pose_var + delta_var;
                 }
                 zs = dm_sqrt_fast(zvar);
+                if (r.ncp == 0u) {
+                    // accepted without a contact point (minContacts = 0): delta = 0 * (1 / 0) and
+                    // poseVar = 0 / 0 make zPos and zSigma NaN; the contract stores the canonical
+                    // quiet NaN (a generated NaN's sign and payload are the processor's)
+                    z = dm_from_bits(0x7ff8000000000000ull);
+                    zs = dm_from_bits(0x7ff8000000000000ull);
+                }
                 w *= r.weight;
                 mprob = r.weight;
                 floating = 0;
