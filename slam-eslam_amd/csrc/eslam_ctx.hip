@@ -23,107 +23,11 @@
 #include <vector>
 
 #include "eslam_internal.h"
+#include "eslam_launch.h"
+#include "eslam_buf.h"
 
 using namespace eslam_dev;
-
-extern "C" hipError_t eslam_launch_contact_records(DevState s0, DevState s1, const MapView* map, const StepParams* p, Ctl* ctl,
-                                                   const DebugRec* d, const LocalMaps* store, hipStream_t stream);
-extern "C" hipError_t eslam_launch_store_init(uint32_t* sid, const LocalMaps* lm, uint64_t n, uint64_t pool, hipStream_t stream);
-extern "C" hipError_t eslam_launch_store_refs(SidRef sid, uint64_t n, uint64_t pool, const CowScratch* cs, const GatherView* gv,
-                                              uint32_t* tgen, hipStream_t stream);
-extern "C" hipError_t eslam_launch_store_receive(SidRef sid, Ctl* ctl, const LocalMaps* lm, const MergeParams* mp, uint64_t n,
-                                                 const CowScratch* cs, const void* hdr, uint64_t nrecv, uint32_t* hoff,
-                                                 uint32_t* head, const void* pay, uint32_t* pgc, hipStream_t stream);
-extern "C" hipError_t eslam_launch_map_plan(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                            const MergeParams* mp, uint32_t* pgc, hipStream_t stream);
-extern "C" hipError_t eslam_launch_map_match(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                             const MatchParams* mp, hipStream_t stream);
-extern "C" hipError_t eslam_launch_map_merge(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                             const MergeParams* mp, hipStream_t stream);
-extern "C" hipError_t eslam_launch_pay_hdr(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend,
-                                           uint64_t gbase, const LocalMaps* lm, const PaySeg* seg, void* hdr, uint32_t* off,
-                                           hipStream_t stream);
-extern "C" hipError_t eslam_launch_pay_pack(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend,
-                                            uint64_t gbase, const LocalMaps* lm, const void* hdr, const uint32_t* off, void* pay,
-                                            hipStream_t stream);
-extern "C" hipError_t eslam_launch_pack_records(DevState s0, DevState s1, const Ctl* ctl, uint64_t first, uint64_t stride,
-                                                uint64_t count, uint64_t gbase, const uint32_t* anc, const DebugRec* d,
-                                                eslam_particle_record* out, eslam_cpoint* cps, uint32_t max_cp,
-                                                const uint64_t* slot, const double* remote, hipStream_t stream);
-extern "C" hipError_t eslam_launch_gather_records(const uint32_t* req, uint64_t nreq, uint64_t gbase, const DebugRec* d,
-                                                  double* items, hipStream_t stream);
-extern "C" hipError_t eslam_launch_centroid_chunks(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl,
-                                                   double* chunk_out, hipStream_t stream);
-extern "C" hipError_t eslam_launch_centroid_tree(double* a, double* b, uint64_t m, double* out, hipStream_t stream);
-extern "C" hipError_t eslam_launch_hash_candidates(const uint32_t* keys, const uint32_t* order, uint64_t cnt, uint64_t gbase,
-                                                   int nranks, void* send, hipStream_t stream);
-extern "C" hipError_t eslam_launch_hash_unpack(const void* recv, uint64_t m, uint32_t* keys, uint32_t* vals, hipStream_t stream);
-extern "C" hipError_t eslam_launch_hash_replace_global(DevState s0, DevState s1, const Ctl* ctl, const uint32_t* gorder,
-                                                       const uint32_t* draws, uint64_t k, uint64_t gbase, uint64_t n,
-                                                       const uint32_t* blist, uint32_t bstart, const double* hx,
-                                                       const double* hy, const double* hth, const double* hz, double weight,
-                                                       hipStream_t stream);
-extern "C" hipError_t eslam_radix_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_out, uint32_t* order, uint64_t n,
-                                             void* tmp, size_t* tmp_bytes, hipStream_t stream);
-extern "C" hipError_t eslam_launch_project_weight(int project, int weight, int maxp, DevState s0, DevState s1,
-                                                  const MapView* map, const StepParams* p, Ctl* ctl, Shard* shards,
-                                                  const GatherView* gv, const LocalMaps* store, hipStream_t stream,
-                                                  const ChunkSel* sel, double* bspill);
-extern "C" hipError_t eslam_launch_commit(Ctl* ctl, hipStream_t stream);
-// eslam_shared_map.hip
-extern "C" size_t eslam_sm_sort_bytes(uint64_t records);
-extern "C" hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const SmRun* run,
-                                            const SmScratch* s, hipStream_t stream);
-extern "C" hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl* ctl, const SmRun* run, const SmGrid* cur,
-                                            const SmGrid* next, const SmScratch* s, hipStream_t stream);
-extern "C" size_t eslam_scan_work_bytes(uint64_t n, void* mem, ScanWork* w);
-extern "C" hipError_t eslam_launch_scan_order(const dm_scan_frame* f, const ScanReading* rd, const ScanWork* w, hipStream_t stream);
-extern "C" hipError_t eslam_launch_scan_count(const dm_scan_frame* f, const ScanWork* w, uint32_t nheads, uint32_t nbinned,
-                                              hipStream_t stream);
-extern "C" hipError_t eslam_launch_scan_emit(const dm_scan_frame* f, const ScanWork* w, uint32_t nheads, uint32_t nbinned,
-                                             eslam_scan_patch* out, hipStream_t stream);
-extern "C" hipError_t eslam_launch_weight_stats(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, Shard* shards,
-                                                hipStream_t stream);
-extern "C" hipError_t eslam_launch_finalize(Shard* recs, int nrec, Ctl* ctl, const FinParams* fp, hipStream_t stream);
-extern "C" hipError_t eslam_launch_normalize_scan(DevState s0, DevState s1, const ScanParams* sp, Ctl* ctl, uint64_t* tile_sum,
-                                                  uint64_t* total, const FusedFin* ff, hipStream_t stream);
-extern "C" hipError_t eslam_launch_normalize_segments(DevState s0, DevState s1, const ScanParams* sp, Ctl* ctl,
-                                                      uint64_t* tile_pub, uint32_t* marks, uint32_t* tile_first,
-                                                      const uint32_t* jt, const FusedFin* ff, hipStream_t stream);
-extern "C" hipError_t eslam_launch_resample_gather(DevState s0, DevState s1, uint64_t n, uint64_t gbase, Ctl* ctl,
-                                                   const GatherView* gv, uint32_t aux, hipStream_t stream);
-extern "C" hipError_t eslam_launch_segments_multi(DevState s0, DevState s1, const ScanParams* sp, const PlanParams* pp, Ctl* ctl,
-                                                  const uint64_t* tile_prefix, uint32_t* marks, uint32_t* tile_first,
-                                                  const uint64_t* totals, const uint32_t* jt, uint2* range, uint64_t* first_last,
-                                                  uint64_t* host_out, uint64_t* host_epoch, uint64_t epoch,
-                                                  hipStream_t stream);
-extern "C" hipError_t eslam_launch_pack(DevState s0, DevState s1, Ctl* ctl, const PlanParams* pp, const uint2* range,
-                                        const uint64_t* first_last, uint64_t nsend, void* send, hipStream_t stream);
-extern "C" hipError_t eslam_launch_expand(const void* recv, uint64_t nrecv, uint64_t W0, uint32_t* marks, uint32_t* row_first,
-                                          hipStream_t stream);
-extern "C" uint64_t eslam_record_bytes(void);
-extern "C" hipError_t eslam_launch_hash_sweep(const dm_hash_grid* g, const double* pts, const double* orient, uint32_t steps,
-                                              int32_t* out, hipStream_t stream);
-extern "C" hipError_t eslam_launch_hash_poses(const dm_hash_grid* g, const double* pts, const double* orient, const uint64_t* ids,
-                                              uint64_t count, double* hx, double* hy, double* hth, double* hz,
-                                              hipStream_t stream);
-extern "C" hipError_t eslam_launch_init_from_hash(DevState s0, const uint32_t* idx, uint64_t n, const double* hx,
-                                                  const double* hy, const double* hth, const double* hz, hipStream_t stream);
-extern "C" hipError_t eslam_hash_sort(DevState s0, DevState s1, const Ctl* ctl, uint64_t n, uint32_t* keys, uint32_t* vals,
-                                      uint32_t* keys_out, uint32_t* order, void* tmp, size_t* tmp_bytes, hipStream_t stream);
-extern "C" hipError_t eslam_launch_hash_replace(DevState s0, DevState s1, const Ctl* ctl, const uint32_t* order,
-                                                const uint32_t* draws, uint64_t k, const uint32_t* blist, uint32_t bstart,
-                                                const double* hx, const double* hy, const double* hth, const double* hz,
-                                                double weight, hipStream_t stream);
-extern "C" hipError_t eslam_launch_init_gaussian(DevState s0, uint64_t n, uint64_t gbase, uint64_t seed, uint64_t ev,
-                                                 const double mu[3], const double sigma[3], double zpos, double zsigma,
-                                                 hipStream_t stream);
-extern "C" hipError_t eslam_launch_selftest_math(int fn, const double* x, const double* y, double* out, uint64_t n,
-                                                 hipStream_t stream);
-extern "C" hipError_t eslam_launch_best_index(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint64_t* out2,
-                                              hipStream_t stream);
-extern "C" hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* out,
-                                            hipStream_t stream);
+using namespace eslam_buf;
 
 // ---------------------------------------------------------------------------------------
 // small Eigen / base-types restatements (host, per step)
@@ -278,94 +182,112 @@ static ProcessStatics& process_statics()
 // their respawns and hash indices would disagree (eslam_gpu_set_comm refuses a second one)
 static std::atomic<int> g_statics_sharded{0};
 
+// The owners of the context's device and pinned memory, grouped by what drops them together:
+// assigning an empty group over one frees its buffers (free_particles, free_local_maps,
+// free_debug, free_map).  The structs kernels take by value are filled from these.
+struct ParticleBufs {                        // alloc_particles
+    Dev<void> state_mem;
+    Dev<uint32_t> marks, anc;
+    Dev<uint32_t> tile_first;                // row_first: source of every 64-output row's first output
+    Dev<uint64_t> tile_sum;                  // per scan tile: exact fixed-point weight total (sharded K3a), or
+                                             // one GPU: tag << 61 | total published by K3 (zeroed at allocation)
+    Dev<uint2> range;                        // per particle: [lo, hi) of its global outputs
+    Dev<uint32_t> sid_mem;                   // 2 x cap: DevState::sid of both state buffers
+    Dev<uint32_t> cow;                       // owner, counts, free and sharing lists + the copy count
+    Dev<uint64_t> merge_cnt;                 // the map merge's statistics slots (2 x kMergeCounterSlots) and
+                                             // the copy-on-write copies since the last merge
+};
+struct LocalMapBufs {                        // local_maps_reset
+    Dev<int2> ctr;                           // the arrays of LocalMaps
+    Dev<float2> page;
+    Dev<uint64_t> owner;
+    Dev<uint32_t> slot, tgen, frees;
+    Dev<uint8_t> mark;
+    Dev<uint32_t> off;                       // per particle: its first page in its plan block (MergeParams::off)
+    Dev<MergeJob> job;                       // per particle: the plan's record (MergeParams::job)
+    Dev<uint16_t> codes;                     // per particle: the plan's cell codes (MergeParams::codes): a small
+                                             //   part's stride, grown for a large part's
+    Dev<uint32_t> poff;                      // per merge block: page offsets (+ total)
+    Dev<uint32_t> pgc;                       // the page collection's compaction counts
+    Dev<ScanPatch> match_sp;                 // processMap match: the sampled scan patches
+    Dev<void> census;                        // a snapshot's census: first, trank, tlist, firstref, prank, plist
+    Dev<uint32_t> counts;                    // the census' tile counts
+};
+struct DebugBufs {                           // the arrays of DebugRec
+    Dev<double> meas, cp;
+    Dev<uint8_t> ncp;
+    Dev<uint32_t> resampled;
+};
+struct GridBufs {                            // the shared grid's arrays (MapView, SmGrid)
+    Dev<uint32_t> cells, occ;
+    Dev<float2> patch;
+    Dev<float> height;                       // empty: all horizontal
+    Dev<uint4> cell_tab;
+    SmGrid view() const { return SmGrid{cells, patch, height, occ, cell_tab}; }
+};
+
 struct eslam_ctx {
     eslam_config cfg;
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;            // destroyed (if owned) after every member below is gone
     bool own_stream = false;
     // particles
     uint64_t n = 0, cap = 0;
     uint64_t gbase = 0, n_global = 0;
     DevState st[2] = {};
-    void* state_mem = nullptr;
-    uint32_t* marks = nullptr;
-    uint32_t* tile_first = nullptr;         // row_first: source of every 64-output row's first output
+    ParticleBufs pt;
     uint64_t* fin_word = nullptr;           // the fused finalize's epoch word (after the tile words)
     uint32_t pub_stride = 0;                // ScanParams::pub_stride
     uint64_t fin_epoch = 0;                 // fused finalize launches so far
-    uint64_t* tile_sum = nullptr;           // per scan tile: exact fixed-point weight total (sharded K3a), or
-                                            // one GPU: tag << 61 | total published by K3 (zeroed at allocation)
     uint32_t scan_tag = 0;                  // the last K3 launch's tag (1..7)
-    uint32_t* anc = nullptr;
     bool has_anc = false;
     // per-particle maps (ESLAM_FLAG_PARTICLE_MAPS): the tables, pages and the copy-on-write scratch
     LocalMaps lm = {};
+    LocalMapBufs lmb;
     bool lm_ready = false;                   // lm sized for the current map and particle count
-    uint32_t* sid_mem = nullptr;             // 2 x cap: DevState::sid of both state buffers
-    uint32_t* cow = nullptr;                 // owner, counts, free and sharing lists + the copy count
-    uint32_t* lm_off = nullptr;              // per particle: its first page in its plan block (MergeParams::off)
-    void* lm_job = nullptr;                  // per particle: the plan's record (MergeParams::job)
-    uint16_t* lm_codes = nullptr;            // per particle: the plan's cell codes (MergeParams::codes)
-    uint64_t lm_codes_cap = 0;               //   bytes (a small part's stride; grown for a large part's)
     // the scan of a map update on the device (MergeParams::sp): two slots, each staged through
     // pinned host memory; an update waits for the update before last to have read its slot
-    void* scan_host[2] = {nullptr, nullptr};
-    void* scan_dev[2] = {nullptr, nullptr};
-    uint64_t scan_host_cap[2] = {0, 0}, scan_dev_cap[2] = {0, 0};
-    hipEvent_t scan_ev[2] = {nullptr, nullptr};
+    Pinned<ScanPatch> scan_host[2];
+    Dev<ScanPatch> scan_dev[2];
+    Event scan_ev[2];
     uint32_t scan_slot = 0;
-    uint32_t* lm_poff = nullptr;             // per merge block: page offsets (+ total)
-    uint32_t* lm_pgc = nullptr;              // the page collection's compaction counts
-    void* match_sp = nullptr;                // processMap match: the sampled scan patches (device)
-    uint64_t match_cap = 0;
-    uint64_t* merge_cnt = nullptr;           // the map merge's statistics slots (2 x kMergeCounterSlots) and
-                                             // the copy-on-write copies since the last merge
     // logDebug records of the last update (ESLAM_FLAG_RECORD_CONTACTS / log_debug)
     DebugRec dbg = {};
+    DebugBufs dbgb;
     uint64_t dbg_cap = 0;
     bool dbg_valid = false;
     // statistics and control
-    Shard* shards = nullptr;
-    Ctl* ctl = nullptr;
-    Ctl* ctl_host = nullptr;    // pinned
-    uint32_t* fault_host = nullptr;         // host-mapped: kFaultTimeout when a device wait gave up
+    Dev<Shard> shards;
+    Dev<Ctl> ctl;
+    Pinned<Ctl> ctl_host;
+    Pinned<uint32_t> fault_host;            // host-mapped: kFaultTimeout when a device wait gave up
     bool poisoned = false;                  // the particle set is undefined until re-initialised
     bool poison_pages = false;              // ... because the map pages ran out (kFaultPages)
     uint32_t spin_limit = kSpinLimit;       // polls of K3's cross-block waits (debug: 0 gives up at once)
-    uint32_t* jump = nullptr;
+    Dev<uint32_t> jump;
     uint32_t jump_n = 1;                    // A^n_global, cached
     uint64_t jump_n_for = 0;
-    double* scratch = nullptr;  // small device scratch (centroid, best index)
-    double* scratch_host = nullptr;
+    Dev<double> scratch;                    // small device scratch (centroid, best index)
+    Pinned<double> scratch_host;
     // map
     bool has_map = false;
     MapView map = {};
-    uint32_t* d_cells = nullptr;
-    float2* d_patch = nullptr;
-    float* d_height = nullptr;
-    uint32_t* d_occ = nullptr;               // MapView::occ
-    uint4* d_cell_tab = nullptr;             // MapView::cell_tab
+    GridBufs grid;
     uint64_t map_np = 0;                     // patches of the grid (cell_start[width * height])
-    uint64_t map_np_cap = 0;                 // patches d_patch / d_height have room for
+    uint64_t map_np_cap = 0;                 // patches grid.patch / grid.height have room for
     // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
-    void* sm_mem = nullptr;
-    uint64_t sm_bytes = 0;
+    Dev<void> sm_mem;
     // eslam_gpu_scan_from_laser / _depth: the build's scratch (ScanWork) and the last
-    // built scan's patches, both kept between calls
-    void* scan_mem = nullptr;
-    uint64_t scan_bytes = 0;
-    eslam_scan_patch* scan_out = nullptr;
-    uint64_t scan_out_cap = 0;               // patches scan_out has room for
+    // built scan's patches (capacity in patches), both kept between calls
+    Dev<void> scan_mem;
+    Dev<eslam_scan_patch> scan_out;
     uint64_t scan_count = 0;                 // patches of the last built scan
     // eslam_gpu_save / eslam_gpu_load: two pinned and two device staging slots of
-    // snap_cap bytes with their events, and the census scratch (dropped with the local maps)
-    void* snap_host[2] = {nullptr, nullptr};
-    void* snap_dev[2] = {nullptr, nullptr};
+    // snap_cap bytes with their events (the census scratch is dropped with the local maps)
+    Pinned<void> snap_host[2];
+    Dev<void> snap_dev[2];
     uint64_t snap_cap = 0;
-    hipEvent_t snap_ev[2] = {nullptr, nullptr};
-    void* snap_census = nullptr;             // first, trank, tlist, firstref, prank, plist
-    uint32_t* snap_counts = nullptr;         // the census' tile counts
-    uint64_t snap_counts_cap = 0;
+    Event snap_ev[2];
     uint32_t maxp = 4;
     // host-side filter state
     uint64_t proj_event = 0, init_event = 0, hash_event = 0;
@@ -376,26 +298,21 @@ struct eslam_ctx {
     bool statics_sharded = false;            // counted in g_statics_sharded
     eslam_comm comm = {};
     std::vector<uint64_t> gall;             // first global index of every rank (+ n_global)
-    Shard* recs = nullptr;                  // gathered records of all ranks
-    uint64_t* mg = nullptr;                 // MgBlock (device)
+    Dev<Shard> recs;                        // gathered records of all ranks
+    Dev<uint64_t> mg;                       // MgBlock (device)
     void* rccl = nullptr;                   // ncclComm_t of eslam_gpu_set_comm_rccl (owned)
-    uint64_t* mg_host = nullptr;            // pinned, host-mapped (k_segments_multi writes the totals there)
+    Pinned<uint64_t> mg_host;               // host-mapped (k_segments_multi writes the totals there)
     uint64_t seg_epoch = 0;                 // the last k_segments_multi launch's epoch (mg_host[kHostEpoch])
-    uint2* range = nullptr;                 // per particle: [lo, hi) of its global outputs
-    void* sendbuf = nullptr; uint64_t send_cap = 0;
-    void* recvbuf = nullptr; uint64_t recv_cap = 0;
+    Dev<void> sendbuf, recvbuf;
     // per-particle maps on a sharded filter: the migrated particles' maps (a MapPayHdr per
     // record, then their pages as MapPayPage, in the records' order) and whether their tables
     // are still owed to them
-    void* sendpay = nullptr; uint64_t sendpay_cap = 0;
-    void* sendhdr = nullptr; uint64_t sendhdr_cap = 0;
-    void* recvhdr = nullptr; uint64_t recvhdr_cap = 0;
-    uint32_t* payoff = nullptr; uint64_t payoff_cap = 0;   // header prefix (send side, then receive side)
-    uint32_t* rhead = nullptr; uint64_t rhead_cap = 0;     // received records: the record carrying each one's map
+    Dev<void> sendpay, recvpay, sendhdr, recvhdr;
+    Dev<uint32_t> payoff;                    // header prefix (send side, then receive side)
+    Dev<uint32_t> rhead;                     // received records: the record carrying each one's map
     uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
-    double* cent = nullptr; uint64_t cent_bytes = 0;   // sharded getCentroid's chunk records (set_comm)
-    double* bspill = nullptr; uint64_t bspill_cap = 0;  // K1's parked per-bucket sums (k1_bspill_bytes)
-    void* recvpay = nullptr; uint64_t recvpay_cap = 0;
+    Dev<double> cent;                        // sharded getCentroid's chunk records (set_comm)
+    Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)
     bool cow_pending = false;
     // a sharded update's exchange left for the next call: the segments kernel's
     // epoch and plan; the next step runs its own-output chunks before it completes it
@@ -403,15 +320,15 @@ struct eslam_ctx {
     uint64_t xpend_epoch = 0;
     PlanParams xpend_pp = {};
     hipStream_t xstream = nullptr;           // the deferred exchange's stream (overlaps the own chunks)
-    hipEvent_t ev_seg = nullptr;             // recorded after the segments kernel
-    hipEvent_t ev_x = nullptr;               // recorded after the exchange's expand
-    void* stage = nullptr; uint64_t stage_cap = 0;   // pinned staging (host-memory comm)
+    Event ev_seg;                            // recorded after the segments kernel
+    Event ev_x;                              // recorded after the exchange's expand
+    Pinned<void> stage;                      // pinned staging (host-memory comm)
     // SurfaceHash (useHash)
     double map_scale[2] = {1, 1};
     bool has_hash = false;
     uint64_t hash_n = 0;
-    double* d_hash = nullptr;                // 4 x hash_n: x, y, theta, z
-    uint32_t* d_hash_blist = nullptr;        // pose indices grouped by bucket, sweep order
+    Dev<double> d_hash;                      // 4 x hash_n: x, y, theta, z
+    Dev<uint32_t> d_hash_blist;              // pose indices grouped by bucket, sweep order
     std::vector<uint32_t> hash_bstart;       // bins^2 + 1
     std::vector<int32_t> hash_bucket;        // per pose (sweep order)
     dm_libc_rand_state libc;                 // rand() of SurfaceHash::sample (glibc, seed 1)
@@ -419,25 +336,19 @@ struct eslam_ctx {
     // (ESLAM_FLAG_PROCESS_STATICS: the reference's function statics, Q11)
     uint64_t* hash_ev = nullptr;
     dm_libc_rand_state* libcp = nullptr;
-    void* hsend = nullptr; uint64_t hsend_cap = 0;   // sharded respawn: candidate pairs out / in
-    void* hrecv = nullptr; uint64_t hrecv_cap = 0;
-    void* hsort = nullptr; uint64_t hsort_cap = 0;   // their keys, vals, sorted keys, order + sort scratch
-    uint32_t* d_sort = nullptr;              // keys, vals, keys_out, order (4 x cap)
+    Dev<void> hsend, hrecv, hsort;           // sharded respawn: candidate pairs out / in; their sort's arrays + scratch
+    Dev<uint32_t> d_sort;                    // keys, vals, keys_out, order (4 x sort_cap)
     uint64_t sort_cap = 0;
-    void* sort_tmp = nullptr;
+    Dev<void> sort_tmp;
     size_t sort_tmp_bytes = 0;
-    uint32_t* d_draws = nullptr;
-    uint64_t draws_cap = 0;
+    Dev<uint32_t> d_draws;
     // diagnostics
     std::string err;
     bool timing = false;
-    hipEvent_t ev[5] = {};                  // events of the step being recorded
-    std::vector<hipEvent_t> ring;           // 5 events per recorded step (timing mode)
-    uint32_t ring_steps = 0;
-    std::vector<hipEvent_t> mring;          // 5 events per recorded map update (timing mode)
-    uint32_t mring_steps = 0;
-    std::vector<hipEvent_t> xring;          // 2 events per recorded map match (timing mode)
-    uint32_t xring_steps = 0;
+    Event ev[5];                            // events of the step being recorded
+    EventRing ring{5, 4};                   // 5 events per recorded step (timing mode)
+    EventRing mring{5, 4};                  // 5 events per recorded map update (timing mode)
+    EventRing xring{2, 1};                  // 2 events per recorded map match (timing mode)
     eslam_kernel_times times = {};
 };
 
@@ -449,8 +360,6 @@ struct eslam_ctx {
             return ESLAM_ERR_HIP;                                                            \
         }                                                                                    \
     } while (0)
-
-static constexpr uint32_t kRingSteps = 2048;
 
 static int settle(eslam_ctx* ctx);       // completes a deferred sharded exchange (run_update_tail_multi)
 
@@ -473,45 +382,12 @@ constexpr int kChunks = kHostEpoch + 1;                     // [2] own-output ch
 constexpr int kWords = kChunks + 2;
 }  // namespace mg
 
-// timing mode: event k (0..4) of the current step, kept in a ring so a whole timed region
-// of back-to-back steps is measured without synchronising between steps
-static void rec(eslam_ctx* ctx, int k)
-{
-    if (!ctx->timing) return;
-    if (ctx->ring.empty()) {
-        ctx->ring.resize(5 * kRingSteps);
-        for (auto& e : ctx->ring) (void)hipEventCreate(&e);   // timing is diagnostic: best effort
-    }
-    if (ctx->ring_steps >= kRingSteps) return;
-    (void)hipEventRecord(ctx->ring[5 * ctx->ring_steps + k], ctx->stream);
-    if (k == 4) ctx->ring_steps++;
-}
-
-// timing mode: event k (0..3) of the current map update (start, gather, copy on write, merge)
-static void mrec(eslam_ctx* ctx, int k)
-{
-    if (!ctx->timing) return;
-    if (ctx->mring.empty()) {
-        ctx->mring.resize(5 * kRingSteps);
-        for (auto& e : ctx->mring) (void)hipEventCreate(&e);
-    }
-    if (ctx->mring_steps >= kRingSteps) return;
-    (void)hipEventRecord(ctx->mring[5 * ctx->mring_steps + k], ctx->stream);
-    if (k == 4) ctx->mring_steps++;
-}
-
-// timing mode: event k (0: start, 1: end) of the current map match
-static void xrec(eslam_ctx* ctx, int k)
-{
-    if (!ctx->timing) return;
-    if (ctx->xring.empty()) {
-        ctx->xring.resize(2 * kRingSteps);
-        for (auto& e : ctx->xring) (void)hipEventCreate(&e);
-    }
-    if (ctx->xring_steps >= kRingSteps) return;
-    (void)hipEventRecord(ctx->xring[2 * ctx->xring_steps + k], ctx->stream);
-    if (k == 1) ctx->xring_steps++;
-}
+// timing mode (EventRing): event k (0..4) of the current step; event k (0..4) of the current map
+// update (start, gather, copy on write, plan, merge); event k (0: start, 1: end) of the current
+// map match
+static void rec(eslam_ctx* ctx, int k) { ctx->ring.record(ctx->timing, k, ctx->stream); }
+static void mrec(eslam_ctx* ctx, int k) { ctx->mring.record(ctx->timing, k, ctx->stream); }
+static void xrec(eslam_ctx* ctx, int k) { ctx->xring.record(ctx->timing, k, ctx->stream); }
 
 static int fail(eslam_ctx* ctx, int code, const char* msg)
 {
@@ -590,7 +466,7 @@ static int poison_fail(eslam_ctx* ctx)
 static int check_poisoned(eslam_ctx* ctx)
 {
     if (!ctx->poisoned) {
-        const uint32_t f = __atomic_load_n(ctx->fault_host, __ATOMIC_ACQUIRE);
+        const uint32_t f = __atomic_load_n(ctx->fault_host.get(), __ATOMIC_ACQUIRE);
         if (f & (kFaultTimeout | kFaultPages)) {
             ctx->poisoned = true;
             ctx->poison_pages = (f & kFaultPages) != 0;
@@ -629,13 +505,13 @@ extern "C" int eslam_gpu_create(const eslam_config* cfg, int device, eslam_ctx**
         if (e != hipSuccess) { ctx->err = std::string("hipSetDevice: ") + hipGetErrorString(e); rc = ESLAM_ERR_HIP; break; }
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(ctx, ESLAM_ERR_HIP, "stream"); break; }
         ctx->own_stream = true;
-        if (hipMalloc(&ctx->shards, sizeof(Shard) * kNShard) != hipSuccess ||
-            hipMalloc(&ctx->ctl, sizeof(Ctl)) != hipSuccess ||
-            hipHostMalloc(&ctx->ctl_host, sizeof(Ctl)) != hipSuccess ||
-            hipMalloc(&ctx->jump, sizeof(uint32_t) * (2048 + 2048 + 1024)) != hipSuccess ||
-            hipMalloc(&ctx->scratch, 4096) != hipSuccess ||
-            hipHostMalloc(&ctx->scratch_host, 4096) != hipSuccess ||
-            hipHostMalloc(&ctx->fault_host, 64) != hipSuccess) {
+        if (ctx->shards.alloc(sizeof(Shard) * kNShard) != hipSuccess ||
+            ctx->ctl.alloc(sizeof(Ctl)) != hipSuccess ||
+            ctx->ctl_host.alloc(sizeof(Ctl)) != hipSuccess ||
+            ctx->jump.alloc(sizeof(uint32_t) * (2048 + 2048 + 1024)) != hipSuccess ||
+            ctx->scratch.alloc(4096) != hipSuccess ||
+            ctx->scratch_host.alloc(4096) != hipSuccess ||
+            ctx->fault_host.alloc(64) != hipSuccess) {
             rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "device allocation failed");
             break;
         }
@@ -674,7 +550,7 @@ extern "C" int eslam_gpu_create(const eslam_config* cfg, int device, eslam_ctx**
             break;
         }
         bool ev_ok = true;
-        for (auto& e2 : ctx->ev) ev_ok &= hipEventCreate(&e2) == hipSuccess;
+        for (auto& e2 : ctx->ev) ev_ok &= e2.create(true) == hipSuccess;
         if (!ev_ok) { rc = fail(ctx, ESLAM_ERR_HIP, "event create"); break; }
         if (hipDeviceSynchronize() != hipSuccess) { rc = fail(ctx, ESLAM_ERR_HIP, "device synchronize"); break; }
     } while (0);
@@ -700,7 +576,7 @@ static bool keep_ancestors(const eslam_ctx* ctx)
 
 static void free_debug(eslam_ctx* ctx)
 {
-    (void)hipFree(ctx->dbg.meas); (void)hipFree(ctx->dbg.ncp); (void)hipFree(ctx->dbg.cp); (void)hipFree(ctx->dbg.resampled);
+    ctx->dbgb = DebugBufs{};
     ctx->dbg = DebugRec{};
     ctx->dbg_cap = 0;
     ctx->dbg_valid = false;
@@ -712,13 +588,8 @@ static const LocalMaps* store_of(const eslam_ctx* ctx) { return particle_maps(ct
 
 static void free_local_maps(eslam_ctx* ctx)
 {
-    (void)hipFree(ctx->lm.ctr); (void)hipFree(ctx->lm.slot); (void)hipFree(ctx->lm.page); (void)hipFree(ctx->lm.tgen);
-    (void)hipFree(ctx->lm.owner); (void)hipFree(ctx->lm.frees); (void)hipFree(ctx->lm.mark);
-    (void)hipFree(ctx->lm_off); (void)hipFree(ctx->lm_job); (void)hipFree(ctx->lm_codes); ctx->lm_codes_cap = 0; (void)hipFree(ctx->lm_poff); (void)hipFree(ctx->lm_pgc); (void)hipFree(ctx->match_sp);
-    (void)hipFree(ctx->snap_census); (void)hipFree(ctx->snap_counts);
-    ctx->snap_census = nullptr; ctx->snap_counts = nullptr; ctx->snap_counts_cap = 0;
+    ctx->lmb = LocalMapBufs{};
     ctx->lm = LocalMaps{};
-    ctx->lm_off = nullptr; ctx->lm_job = nullptr; ctx->lm_codes = nullptr; ctx->lm_poff = nullptr; ctx->lm_pgc = nullptr; ctx->match_sp = nullptr; ctx->match_cap = 0;
     ctx->lm_ready = false;
 }
 
@@ -726,27 +597,15 @@ static void free_particles(eslam_ctx* ctx)
 {
     free_debug(ctx);
     free_local_maps(ctx);
-    (void)hipFree(ctx->sid_mem); (void)hipFree(ctx->cow); (void)hipFree(ctx->merge_cnt);
-    ctx->merge_cnt = nullptr;
-    ctx->sid_mem = nullptr;
-    ctx->cow = nullptr;
+    ctx->pt = ParticleBufs{};
     ctx->st[0].sid = ctx->st[1].sid = nullptr;
-    (void)hipFree(ctx->state_mem); ctx->state_mem = nullptr;
-    (void)hipFree(ctx->marks); ctx->marks = nullptr;
-    (void)hipFree(ctx->tile_first); ctx->tile_first = nullptr;
-    (void)hipFree(ctx->tile_sum); ctx->tile_sum = nullptr;
-    (void)hipFree(ctx->anc); ctx->anc = nullptr;
-    (void)hipFree(ctx->range); ctx->range = nullptr;
     ctx->n = ctx->cap = 0;
     ctx->has_anc = false;
 }
 
 static void free_map(eslam_ctx* ctx)
 {
-    (void)hipFree(ctx->d_cells); (void)hipFree(ctx->d_patch); (void)hipFree(ctx->d_height); (void)hipFree(ctx->d_occ);
-    (void)hipFree(ctx->d_cell_tab);
-    ctx->d_cells = nullptr; ctx->d_patch = nullptr; ctx->d_height = nullptr; ctx->d_occ = nullptr;
-    ctx->d_cell_tab = nullptr;
+    ctx->grid = GridBufs{};
     ctx->map_np = ctx->map_np_cap = 0;
     ctx->has_map = false;
 }
@@ -764,37 +623,11 @@ extern "C" void eslam_gpu_destroy(eslam_ctx* ctx)
     ctx->statics_sharded = false;
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->xstream) { (void)hipStreamSynchronize(ctx->xstream); (void)hipStreamDestroy(ctx->xstream); }
-    if (ctx->ev_seg) (void)hipEventDestroy(ctx->ev_seg);
-    if (ctx->ev_x) (void)hipEventDestroy(ctx->ev_x);
     rccl_release(ctx);
-    free_particles(ctx);
-    free_map(ctx);
-    (void)hipFree(ctx->shards); (void)hipFree(ctx->ctl); (void)hipHostFree(ctx->ctl_host); (void)hipFree(ctx->jump);
-    (void)hipFree(ctx->scratch); (void)hipHostFree(ctx->scratch_host); (void)hipHostFree(ctx->fault_host);
-    (void)hipFree(ctx->recs); (void)hipFree(ctx->mg); (void)hipHostFree(ctx->mg_host);
-    (void)hipFree(ctx->sendbuf); (void)hipFree(ctx->recvbuf); (void)hipHostFree(ctx->stage);
-    (void)hipFree(ctx->sendpay); (void)hipFree(ctx->recvpay); (void)hipFree(ctx->cent); (void)hipFree(ctx->bspill);
-    (void)hipFree(ctx->sendhdr); (void)hipFree(ctx->recvhdr); (void)hipFree(ctx->payoff); (void)hipFree(ctx->rhead);
-    (void)hipFree(ctx->d_hash); (void)hipFree(ctx->d_hash_blist); (void)hipFree(ctx->d_sort); (void)hipFree(ctx->sort_tmp); (void)hipFree(ctx->d_draws);
-    (void)hipFree(ctx->hsend); (void)hipFree(ctx->hrecv); (void)hipFree(ctx->hsort);
-    (void)hipFree(ctx->sm_mem);
-    (void)hipFree(ctx->scan_mem); (void)hipFree(ctx->scan_out);
-    for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ring) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->mring) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->xring) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->scan_ev[k]) (void)hipEventDestroy(ctx->scan_ev[k]);
-        (void)hipHostFree(ctx->scan_host[k]);
-        (void)hipFree(ctx->scan_dev[k]);
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->snap_ev[k]) (void)hipEventDestroy(ctx->snap_ev[k]);
-        (void)hipHostFree(ctx->snap_host[k]);
-        (void)hipFree(ctx->snap_dev[k]);
-    }
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    // every buffer and event goes with the context, the context's own stream after them
+    hipStream_t own = ctx->own_stream ? ctx->stream : nullptr;
     delete ctx;
+    if (own) (void)hipStreamDestroy(own);
 }
 
 // collective on a sharded filter (every rank calls it at the same point): completes the last
@@ -831,41 +664,41 @@ static int alloc_particles(eslam_ctx* ctx, uint64_t n)
     const uint64_t cap = n ? n : 1;
     auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
     const uint64_t per = 7 * al(cap * 8) + al(cap);
-    HIPCHK(ctx, hipMalloc(&ctx->state_mem, 2 * per));
+    HIPCHK(ctx, ctx->pt.state_mem.alloc(2 * per));
     for (int k = 0; k < 2; ++k) {
-        char* p = (char*)ctx->state_mem + k * per;
+        char* p = ctx->pt.state_mem.as<char>() + k * per;
         DevState& s = ctx->st[k];
         double** f[7] = {&s.x, &s.y, &s.th, &s.z, &s.zs, &s.w, &s.mprob};
         for (int j = 0; j < 7; ++j) { *f[j] = (double*)p; p += al(cap * 8); }
         s.flags = (uint8_t*)p;
     }
     const uint64_t ntiles = (cap + kBlock - 1) / kBlock;                // the smallest scan tile (scan_items)
-    HIPCHK(ctx, hipMalloc(&ctx->marks, cap * 4));
-    HIPCHK(ctx, hipMalloc(&ctx->tile_first, ((cap + kRow - 1) / kRow) * 4));
+    HIPCHK(ctx, ctx->pt.marks.alloc(cap * 4));
+    HIPCHK(ctx, ctx->pt.tile_first.alloc(((cap + kRow - 1) / kRow) * 4));
     // the tile words, then (in a line of its own) the fused finalize's epoch word
     // K3's kPubReplicas copies of the tile words (4 KB-aligned regions, 256 B apart beyond
     // that, so the copies fall on different memory channels), then the epoch word's line
     ctx->pub_stride = (uint32_t)(((ntiles + 511) & ~511ull) + 32);
     const uint64_t fin_at = (uint64_t)kPubReplicas * ctx->pub_stride;
-    HIPCHK(ctx, hipMalloc(&ctx->tile_sum, (fin_at + 16) * 8));
-    HIPCHK(ctx, hipMemset(ctx->tile_sum, 0, (fin_at + 16) * 8));          // tag / epoch 0: never published
-    ctx->fin_word = ctx->tile_sum + fin_at;
-    HIPCHK(ctx, hipMemset(ctx->marks, 0, cap * 4));
-    if (keep_ancestors(ctx)) HIPCHK(ctx, hipMalloc(&ctx->anc, cap * 4));
+    HIPCHK(ctx, ctx->pt.tile_sum.alloc((fin_at + 16) * 8));
+    HIPCHK(ctx, hipMemset(ctx->pt.tile_sum, 0, (fin_at + 16) * 8));          // tag / epoch 0: never published
+    ctx->fin_word = ctx->pt.tile_sum + fin_at;
+    HIPCHK(ctx, hipMemset(ctx->pt.marks, 0, cap * 4));
+    if (keep_ancestors(ctx)) HIPCHK(ctx, ctx->pt.anc.alloc(cap * 4));
     if (particle_maps(ctx)) {
         // the table names of both state buffers; the tables and pages come with the map
         // (local_maps_reset: their window size follows the map's cell size)
-        HIPCHK(ctx, hipMalloc(&ctx->sid_mem, 2 * cap * 4));
-        ctx->st[0].sid = ctx->sid_mem;
-        ctx->st[1].sid = ctx->sid_mem + cap;
-        HIPCHK(ctx, hipMalloc(&ctx->cow, cow_words(cap) * 4));
-        HIPCHK(ctx, hipMalloc(&ctx->merge_cnt, kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
-        HIPCHK(ctx, hipMemset(ctx->merge_cnt, 0, kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
+        HIPCHK(ctx, ctx->pt.sid_mem.alloc(2 * cap * 4));
+        ctx->st[0].sid = ctx->pt.sid_mem;
+        ctx->st[1].sid = ctx->pt.sid_mem + cap;
+        HIPCHK(ctx, ctx->pt.cow.alloc(cow_words(cap) * 4));
+        HIPCHK(ctx, ctx->pt.merge_cnt.alloc(kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
+        HIPCHK(ctx, hipMemset(ctx->pt.merge_cnt, 0, kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
     }
     ctx->n = n;
     ctx->cap = cap;
     if (ctx->sharded) {
-        HIPCHK(ctx, hipMalloc(&ctx->range, cap * sizeof(uint2)));
+        HIPCHK(ctx, ctx->pt.range.alloc(cap * sizeof(uint2)));
     } else {
         ctx->n_global = n;
         ctx->gbase = 0;
@@ -886,6 +719,7 @@ static int local_maps_reset(eslam_ctx* ctx)
     const double r = ctx->cfg.max_sensor_range;
     if (!(r == r) || r < 0.0 || r > 1e6) return fail(ctx, ESLAM_ERR_INVALID_ARG, "max_sensor_range must be finite and >= 0");
     LocalMaps& lm = ctx->lm;
+    LocalMapBufs& b = ctx->lmb;
     lm.hx = dm_lm_half(r, ctx->map_scale[0]);
     lm.hy = dm_lm_half(r, ctx->map_scale[1]);
     lm.wx = 2 * lm.hx + 1;
@@ -905,20 +739,19 @@ static int local_maps_reset(eslam_ctx* ctx)
     lm.npages = cap * per;
     if (lm.npages >= 0xffffffffull) return fail(ctx, ESLAM_ERR_INVALID_ARG, "per-particle map pool: at most 2^32 - 1 pages");
     const uint64_t ptiles = (lm.npages + kCompactTileItems - 1) / kCompactTileItems;
-    HIPCHK(ctx, hipMalloc(&lm.ctr, pool * sizeof(int2)));
-    HIPCHK(ctx, hipMalloc(&lm.slot, pool * lm.S * 4));
-    HIPCHK(ctx, hipMalloc(&lm.tgen, pool * 4));
-    HIPCHK(ctx, hipMalloc(&lm.page, lm.npages * DM_LM_PAGE_CELLS * sizeof(float2)));
-    HIPCHK(ctx, hipMalloc(&lm.owner, lm.npages * 8));
-    HIPCHK(ctx, hipMalloc(&lm.frees, lm.npages * 4));
-    HIPCHK(ctx, hipMalloc(&lm.mark, ((lm.npages + 15) / 16) * 16));
-    HIPCHK(ctx, hipMalloc(&ctx->lm_off, cap * 4));
-    HIPCHK(ctx, hipMalloc(&ctx->lm_job, cap * sizeof(MergeJob)));
-    ctx->lm_codes_cap = cap * 2 * kScanPartSmall;
-    HIPCHK(ctx, hipMalloc(&ctx->lm_codes, ctx->lm_codes_cap));
-    HIPCHK(ctx, hipMalloc(&ctx->lm_poff, ((cap + kLmBlock - 1) / kLmBlock + 1) * 4));
-    HIPCHK(ctx, hipMalloc(&ctx->lm_pgc, (ptiles + 1) * 4));
-    HIPCHK(ctx, eslam_launch_store_init(ctx->sid_mem, &lm, cap, pool, ctx->stream));
+    HIPCHK(ctx, b.ctr.alloc(pool * sizeof(int2), &lm.ctr));
+    HIPCHK(ctx, b.slot.alloc(pool * lm.S * 4, &lm.slot));
+    HIPCHK(ctx, b.tgen.alloc(pool * 4, &lm.tgen));
+    HIPCHK(ctx, b.page.alloc(lm.npages * DM_LM_PAGE_CELLS * sizeof(float2), &lm.page));
+    HIPCHK(ctx, b.owner.alloc(lm.npages * 8, &lm.owner));
+    HIPCHK(ctx, b.frees.alloc(lm.npages * 4, &lm.frees));
+    HIPCHK(ctx, b.mark.alloc(((lm.npages + 15) / 16) * 16, &lm.mark));
+    HIPCHK(ctx, b.off.alloc(cap * 4));
+    HIPCHK(ctx, b.job.alloc(cap * sizeof(MergeJob)));
+    HIPCHK(ctx, b.codes.alloc(cap * 2 * kScanPartSmall));
+    HIPCHK(ctx, b.poff.alloc(((cap + kLmBlock - 1) / kLmBlock + 1) * 4));
+    HIPCHK(ctx, b.pgc.alloc((ptiles + 1) * 4));
+    HIPCHK(ctx, eslam_launch_store_init(ctx->pt.sid_mem, &lm, cap, pool, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // the free list holds every page (k_store_init: frees[p] = p)
     int rc = read_ctl(ctx);
@@ -936,21 +769,11 @@ static int local_maps_reset(eslam_ctx* ctx)
 // ---------------------------------------------------------------------------------------
 // multi-GPU plumbing: the three exchanges of an update go through the user's collectives
 // ---------------------------------------------------------------------------------------
-static int grow(eslam_ctx* ctx, void** buf, uint64_t* cap, uint64_t bytes, bool pinned)
+// a buffer of at least `bytes`, contents not kept (Buf::grow: the old block is freed first)
+template <typename B>
+static int grow(eslam_ctx* ctx, B& buf, uint64_t bytes)
 {
-    if (bytes <= *cap) return ESLAM_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t want = bytes + bytes / 4 + 4096;
-    if (pinned) {
-        (void)hipHostFree(*buf);
-        *buf = nullptr; *cap = 0;
-        HIPCHK(ctx, hipHostMalloc(buf, want));
-    } else {
-        (void)hipFree(*buf);
-        *buf = nullptr; *cap = 0;
-        HIPCHK(ctx, hipMalloc(buf, want));
-    }
-    *cap = want;
+    HIPCHK(ctx, buf.grow(bytes, ctx->stream));
     return ESLAM_OK;
 }
 
@@ -963,9 +786,9 @@ static int comm_allgather(eslam_ctx* ctx, const void* dsend, void* drecv, uint64
             return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
         return ESLAM_OK;
     }
-    int rc = grow(ctx, &ctx->stage, &ctx->stage_cap, bytes * (c.nranks + 1), true);
+    int rc = grow(ctx, ctx->stage, bytes * (c.nranks + 1));
     if (rc) return rc;
-    char* h = (char*)ctx->stage;
+    char* h = ctx->stage.as<char>();
     HIPCHK(ctx, hipMemcpyAsync(h, dsend, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (c.allgather(c.user, h, h + bytes, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
@@ -986,9 +809,9 @@ static int comm_alltoallv(eslam_ctx* ctx, const void* dsend, const uint64_t* sb,
     }
     uint64_t ts = 0, tr = 0;
     for (int r = 0; r < c.nranks; ++r) { ts += sb[r]; tr += rb[r]; }
-    int rc = grow(ctx, &ctx->stage, &ctx->stage_cap, ts + tr + 64, true);
+    int rc = grow(ctx, ctx->stage, ts + tr + 64);
     if (rc) return rc;
-    char* h = (char*)ctx->stage;
+    char* h = ctx->stage.as<char>();
     char* hr = h + ((ts + 63) & ~63ull);
     if (ts) HIPCHK(ctx, hipMemcpyAsync(h, dsend, ts, hipMemcpyDeviceToHost, stream));
     HIPCHK(ctx, hipStreamSynchronize(stream));
@@ -1056,9 +879,9 @@ extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64
             return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: shard starts must be multiples of the summation chunk");
     }
     if (!ctx->mg) {
-        HIPCHK(ctx, hipMalloc(&ctx->recs, sizeof(Shard) * kNShard * kMaxRanks));
-        HIPCHK(ctx, hipMalloc(&ctx->mg, mg::kWords * 8));
-        HIPCHK(ctx, hipHostMalloc(&ctx->mg_host, mg::kWords * 8));
+        HIPCHK(ctx, ctx->recs.alloc(sizeof(Shard) * kNShard * kMaxRanks));
+        HIPCHK(ctx, ctx->mg.alloc(mg::kWords * 8));
+        HIPCHK(ctx, ctx->mg_host.alloc(mg::kWords * 8));
         HIPCHK(ctx, hipMemset(ctx->recs, 0, sizeof(Shard) * kNShard * kMaxRanks));
         HIPCHK(ctx, hipMemset(ctx->mg, 0, mg::kWords * 8));
     }
@@ -1066,13 +889,7 @@ extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64
         // getCentroid's buffer (centroid_bytes): sized by the shard table, allocated here so
         // the per-step getCentroid of a Rock task allocates nothing
         const uint64_t need = centroid_bytes(shard_gbase, comm->nranks, dm_chunk_rows_cfg(n_global, ctx->cfg.sum_chunk_rows));
-        if (need > ctx->cent_bytes) {
-            (void)hipFree(ctx->cent);
-            ctx->cent = nullptr;
-            ctx->cent_bytes = 0;
-            HIPCHK(ctx, hipMalloc(&ctx->cent, need));
-            ctx->cent_bytes = need;
-        }
+        if (need > ctx->cent.cap()) HIPCHK(ctx, ctx->cent.alloc(need));
     }
     if ((ctx->cfg.flags & ESLAM_FLAG_PROCESS_STATICS) && comm->nranks > 1) {
         if (g_statics_sharded.fetch_add(1) != 0) {
@@ -1229,13 +1046,13 @@ extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
     const uint64_t np = g->n_patches ? g->n_patches : 1;
     std::vector<float2> patch(np);
     for (uint64_t k = 0; k < g->n_patches; ++k) patch[k] = make_float2(g->patch_mean[k], g->patch_stdev[k]);
-    HIPCHK(ctx, hipMalloc(&ctx->d_cells, (ncell + 1) * 4));
-    HIPCHK(ctx, hipMalloc(&ctx->d_patch, np * sizeof(float2)));
-    HIPCHK(ctx, hipMemcpy(ctx->d_cells, g->cell_start, (ncell + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->d_patch, patch.data(), np * sizeof(float2), hipMemcpyHostToDevice));
+    HIPCHK(ctx, ctx->grid.cells.alloc((ncell + 1) * 4));
+    HIPCHK(ctx, ctx->grid.patch.alloc(np * sizeof(float2)));
+    HIPCHK(ctx, hipMemcpy(ctx->grid.cells, g->cell_start, (ncell + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->grid.patch, patch.data(), np * sizeof(float2), hipMemcpyHostToDevice));
     if (g->patch_height) {
-        HIPCHK(ctx, hipMalloc(&ctx->d_height, np * 4));
-        HIPCHK(ctx, hipMemcpy(ctx->d_height, g->patch_height, g->n_patches * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->grid.height.alloc(np * 4));
+        HIPCHK(ctx, hipMemcpy(ctx->grid.height, g->patch_height, g->n_patches * 4, hipMemcpyHostToDevice));
     }
     {
         // one bit per cell: the shared grid holds patches there (the map merge's per-patch test
@@ -1243,8 +1060,8 @@ extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
         std::vector<uint32_t> occ((ncell + 31) / 32, 0u);
         for (uint64_t c = 0; c < ncell; ++c)
             if (g->cell_start[c] != g->cell_start[c + 1]) occ[c >> 5] |= 1u << (c & 31);
-        HIPCHK(ctx, hipMalloc(&ctx->d_occ, occ.size() * 4));
-        HIPCHK(ctx, hipMemcpy(ctx->d_occ, occ.data(), occ.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->grid.occ.alloc(occ.size() * 4));
+        HIPCHK(ctx, hipMemcpy(ctx->grid.occ, occ.data(), occ.size() * 4, hipMemcpyHostToDevice));
     }
     {
         // MapView::cell_tab: the cell's range and first patch in one 16-byte record
@@ -1257,16 +1074,16 @@ extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
             memcpy(&fs, &f.y, 4);
             tab[c] = make_uint4(fm, fs, b, e - b);
         }
-        HIPCHK(ctx, hipMalloc(&ctx->d_cell_tab, ncell * sizeof(uint4)));
-        HIPCHK(ctx, hipMemcpy(ctx->d_cell_tab, tab.data(), ncell * sizeof(uint4), hipMemcpyHostToDevice));
+        HIPCHK(ctx, ctx->grid.cell_tab.alloc(ncell * sizeof(uint4)));
+        HIPCHK(ctx, hipMemcpy(ctx->grid.cell_tab, tab.data(), ncell * sizeof(uint4), hipMemcpyHostToDevice));
     }
     MapView& m = ctx->map;
-    m.cell_start = ctx->d_cells;
-    m.occ = ctx->d_occ;
-    m.cell_tab = ctx->d_cell_tab;
-    m.patch = ctx->d_patch;
-    m.height = ctx->d_height;
-    m.has_height = ctx->d_height ? 1u : 0u;
+    m.cell_start = ctx->grid.cells;
+    m.occ = ctx->grid.occ;
+    m.cell_tab = ctx->grid.cell_tab;
+    m.patch = ctx->grid.patch;
+    m.height = ctx->grid.height;
+    m.has_height = ctx->grid.height ? 1u : 0u;
     ctx->map_np = g->n_patches;
     ctx->map_np_cap = np;
     m.width = g->width;
@@ -1296,8 +1113,8 @@ static int reset_ctl_for_new_particles(eslam_ctx* ctx, int wexp)
         // a poisoned filter starts over: the fault cleared, no partial segment marks left
         ctx->ctl_host->err &= ~(uint64_t)(kFaultTimeout | kFaultPages);
         ctx->poison_pages = false;
-        __atomic_store_n(ctx->fault_host, 0u, __ATOMIC_RELAXED);
-        HIPCHK(ctx, hipMemsetAsync(ctx->marks, 0, ctx->cap * 4, ctx->stream));
+        __atomic_store_n(ctx->fault_host.get(), 0u, __ATOMIC_RELAXED);
+        HIPCHK(ctx, hipMemsetAsync(ctx->pt.marks, 0, ctx->cap * 4, ctx->stream));
         ctx->poisoned = false;
     }
     ctx->ctl_host->base = 0;
@@ -1358,8 +1175,8 @@ static dm_hash_grid hash_grid(eslam_ctx* ctx)
 {
     dm_hash_grid g;
     memset(&g, 0, sizeof(g));
-    g.cell_start = ctx->d_cells;
-    g.mean = reinterpret_cast<const float*>(ctx->d_patch);   // float2 {mean, stdev}
+    g.cell_start = ctx->grid.cells;
+    g.mean = ctx->grid.patch.as<const float>();   // float2 {mean, stdev}
     g.mean_stride = 2;
     g.width = ctx->map.width;
     g.height = ctx->map.height_cells;
@@ -1386,60 +1203,48 @@ extern "C" int eslam_gpu_hash_create(eslam_ctx* ctx)
     std::vector<double> pts(8 * steps), orient(steps);
     dm_hash_segments(steps, g.g2w, pts.data(), orient.data());
     const uint64_t cells = (uint64_t)g.width * g.height, total = cells * steps;
-    double* d_seg = nullptr;
-    int32_t* d_out = nullptr;
-    uint64_t* d_ids = nullptr;
+    Dev<double> d_seg;
+    Dev<int32_t> d_out;
+    Dev<uint64_t> d_ids;
     std::vector<int32_t> out(total);
-    int rc = ESLAM_OK;
-    do {
-        if (hipMalloc(&d_seg, sizeof(double) * 9 * steps) != hipSuccess ||
-            hipMalloc(&d_out, sizeof(int32_t) * (total ? total : 1)) != hipSuccess) {
-            rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash sweep buffers");
-            break;
-        }
-        if (hipMemcpy(d_seg, pts.data(), sizeof(double) * 8 * steps, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_seg + 8 * steps, orient.data(), sizeof(double) * steps, hipMemcpyHostToDevice) != hipSuccess ||
-            eslam_launch_hash_sweep(&g, d_seg, d_seg + 8 * steps, steps, d_out, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(out.data(), d_out, sizeof(int32_t) * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = fail(ctx, ESLAM_ERR_HIP, "hash sweep");
-            break;
-        }
-        // compact in sweep order; bucket lists by a stable counting sort
-        std::vector<uint64_t> ids;
-        ctx->hash_bucket.clear();
-        for (uint64_t id = 0; id < total; ++id)
-            if (out[id] >= 0) { ids.push_back(id); ctx->hash_bucket.push_back(out[id]); }
-        const uint64_t n = ids.size();
-        const uint32_t nb = bins * bins;
-        ctx->hash_bstart.assign(nb + 1, 0);
-        for (uint64_t i = 0; i < n; ++i) ctx->hash_bstart[ctx->hash_bucket[i] + 1]++;
-        for (uint32_t b = 0; b < nb; ++b) ctx->hash_bstart[b + 1] += ctx->hash_bstart[b];
-        std::vector<uint32_t> blist(n ? n : 1), fill(ctx->hash_bstart.begin(), ctx->hash_bstart.end() - 1);
-        for (uint64_t i = 0; i < n; ++i) blist[fill[ctx->hash_bucket[i]]++] = (uint32_t)i;
-        (void)hipFree(ctx->d_hash); ctx->d_hash = nullptr;
-        (void)hipFree(ctx->d_hash_blist); ctx->d_hash_blist = nullptr;
-        const uint64_t cap = n ? n : 1;
-        if (hipMalloc(&ctx->d_hash, sizeof(double) * 4 * cap) != hipSuccess ||
-            hipMalloc(&ctx->d_hash_blist, sizeof(uint32_t) * cap) != hipSuccess ||
-            hipMalloc(&d_ids, sizeof(uint64_t) * cap) != hipSuccess) {
-            rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash pose buffers");
-            break;
-        }
-        double* hx = ctx->d_hash;
-        if ((n && hipMemcpy(d_ids, ids.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice) != hipSuccess) ||
-            (n && hipMemcpy(ctx->d_hash_blist, blist.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) ||
-            eslam_launch_hash_poses(&g, d_seg, d_seg + 8 * steps, d_ids, n, hx, hx + cap, hx + 2 * cap, hx + 3 * cap,
-                                    ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = fail(ctx, ESLAM_ERR_HIP, "hash poses");
-            break;
-        }
-        ctx->hash_n = n;
-        ctx->has_hash = true;
-    } while (0);
-    (void)hipFree(d_seg); (void)hipFree(d_out); (void)hipFree(d_ids);
-    return rc;
+    if (d_seg.alloc(sizeof(double) * 9 * steps) != hipSuccess ||
+        d_out.alloc(sizeof(int32_t) * (total ? total : 1)) != hipSuccess)
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash sweep buffers");
+    if (hipMemcpy(d_seg, pts.data(), sizeof(double) * 8 * steps, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_seg + 8 * steps, orient.data(), sizeof(double) * steps, hipMemcpyHostToDevice) != hipSuccess ||
+        eslam_launch_hash_sweep(&g, d_seg, d_seg + 8 * steps, steps, d_out, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(out.data(), d_out, sizeof(int32_t) * total, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(ctx, ESLAM_ERR_HIP, "hash sweep");
+    // compact in sweep order; bucket lists by a stable counting sort
+    std::vector<uint64_t> ids;
+    ctx->hash_bucket.clear();
+    for (uint64_t id = 0; id < total; ++id)
+        if (out[id] >= 0) { ids.push_back(id); ctx->hash_bucket.push_back(out[id]); }
+    const uint64_t n = ids.size();
+    const uint32_t nb = bins * bins;
+    ctx->hash_bstart.assign(nb + 1, 0);
+    for (uint64_t i = 0; i < n; ++i) ctx->hash_bstart[ctx->hash_bucket[i] + 1]++;
+    for (uint32_t b = 0; b < nb; ++b) ctx->hash_bstart[b + 1] += ctx->hash_bstart[b];
+    std::vector<uint32_t> blist(n ? n : 1), fill(ctx->hash_bstart.begin(), ctx->hash_bstart.end() - 1);
+    for (uint64_t i = 0; i < n; ++i) blist[fill[ctx->hash_bucket[i]]++] = (uint32_t)i;
+    ctx->d_hash.reset();
+    ctx->d_hash_blist.reset();
+    const uint64_t cap = n ? n : 1;
+    if (ctx->d_hash.alloc(sizeof(double) * 4 * cap) != hipSuccess ||
+        ctx->d_hash_blist.alloc(sizeof(uint32_t) * cap) != hipSuccess ||
+        d_ids.alloc(sizeof(uint64_t) * cap) != hipSuccess)
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash pose buffers");
+    double* hx = ctx->d_hash;
+    if ((n && hipMemcpy(d_ids, ids.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice) != hipSuccess) ||
+        (n && hipMemcpy(ctx->d_hash_blist, blist.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice) != hipSuccess) ||
+        eslam_launch_hash_poses(&g, d_seg, d_seg + 8 * steps, d_ids, n, hx, hx + cap, hx + 2 * cap, hx + 3 * cap,
+                                ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(ctx, ESLAM_ERR_HIP, "hash poses");
+    ctx->hash_n = n;
+    ctx->has_hash = true;
+    return ESLAM_OK;
 }
 
 static const double* hash_field(eslam_ctx* ctx, int f)
@@ -1463,14 +1268,13 @@ extern "C" int eslam_gpu_init_hash(eslam_ctx* ctx, uint64_t n)
         const uint32_t v = (uint32_t)((uint64_t)(uint32_t)dm_libc_rand(ctx->libcp) % ctx->hash_n);
         if (gi >= skip && gi < skip + n) idx[gi - skip] = v;
     }
-    uint32_t* d_idx = nullptr;
-    HIPCHK(ctx, hipMalloc(&d_idx, sizeof(uint32_t) * (n ? n : 1)));
+    Dev<uint32_t> d_idx;
+    HIPCHK(ctx, d_idx.alloc(sizeof(uint32_t) * (n ? n : 1)));
     hipError_t e = hipMemcpy(d_idx, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = eslam_launch_init_from_hash(ctx->st[0], d_idx, n, hash_field(ctx, 0), hash_field(ctx, 1), hash_field(ctx, 2),
                                         hash_field(ctx, 3), ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_idx);
     HIPCHK(ctx, e);
     return ESLAM_OK;
 }
@@ -1669,7 +1473,7 @@ constexpr uint64_t kRecRemote = 1ull << 63;     // k_pack_records: a slot naming
 // this rank, or kRecRemote | its item in *d_remote.  Every rank takes part; one whose own part
 // failed (rc) sends counts that make every rank fail, so no rank is left waiting.
 static int fetch_remote_records(eslam_ctx* ctx, int rc, uint64_t first, uint64_t stride, uint64_t count,
-                                std::vector<uint64_t>& slot, double** d_remote)
+                                std::vector<uint64_t>& slot, Dev<double>* d_remote)
 {
     const int G = ctx->comm.nranks, me = ctx->comm.rank;
     const uint64_t gb = ctx->gbase, item = 8ull * (5 + 6ull * (ctx->dbg.maxc ? ctx->dbg.maxc : 1));
@@ -1682,7 +1486,7 @@ static int fetch_remote_records(eslam_ctx* ctx, int rc, uint64_t first, uint64_t
         std::vector<uint32_t> anc;
         if (resampled) {
             anc.resize(ctx->n);
-            HIPCHK(ctx, hipMemcpy(anc.data(), ctx->anc, ctx->n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(ctx, hipMemcpy(anc.data(), ctx->pt.anc, ctx->n * 4, hipMemcpyDeviceToHost));
         }
         slot.resize(count);
         for (uint64_t k = 0; k < count; ++k) {
@@ -1725,32 +1529,25 @@ static int fetch_remote_records(eslam_ctx* ctx, int rc, uint64_t first, uint64_t
     std::vector<uint32_t> hreq;
     hreq.reserve(tout);
     for (int d = 0; d < G; ++d) hreq.insert(hreq.end(), req[d].begin(), req[d].end());
-    uint32_t *d_out = nullptr, *d_in = nullptr;
-    double* d_items = nullptr;
-    int out = ESLAM_OK;
-    auto exchange = [&]() -> int {
-        HIPCHK(ctx, hipMalloc(&d_out, (tout + 1) * 4));
-        HIPCHK(ctx, hipMalloc(&d_in, (tin + 1) * 4));
-        HIPCHK(ctx, hipMalloc(&d_items, (tin + 1) * item));
-        HIPCHK(ctx, hipMalloc(d_remote, (tout + 1) * item));
-        if (tout) HIPCHK(ctx, hipMemcpy(d_out, hreq.data(), tout * 4, hipMemcpyHostToDevice));
-        uint64_t sb[kMaxRanks], rb[kMaxRanks];
-        for (int r = 0; r < G; ++r) { sb[r] = 4 * req[r].size(); rb[r] = 4 * nin[r]; }
-        int e = comm_alltoallv(ctx, d_out, sb, d_in, rb);
-        if (e) return e;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (tin && ctx->dbg_valid) HIPCHK(ctx, eslam_launch_gather_records(d_in, tin, gb, &ctx->dbg, d_items, ctx->stream));
-        else if (tin) HIPCHK(ctx, hipMemsetAsync(d_items, 0, tin * item, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        for (int r = 0; r < G; ++r) { sb[r] = item * nin[r]; rb[r] = item * req[r].size(); }
-        e = comm_alltoallv(ctx, d_items, sb, *d_remote, rb);
-        if (e) return e;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        return ESLAM_OK;
-    };
-    out = exchange();
-    (void)hipFree(d_out); (void)hipFree(d_in); (void)hipFree(d_items);
-    if (out) return out;
+    Dev<uint32_t> d_out, d_in;
+    Dev<double> d_items;
+    HIPCHK(ctx, d_out.alloc((tout + 1) * 4));
+    HIPCHK(ctx, d_in.alloc((tin + 1) * 4));
+    HIPCHK(ctx, d_items.alloc((tin + 1) * item));
+    HIPCHK(ctx, d_remote->alloc((tout + 1) * item));
+    if (tout) HIPCHK(ctx, hipMemcpy(d_out, hreq.data(), tout * 4, hipMemcpyHostToDevice));
+    uint64_t sb[kMaxRanks], rb[kMaxRanks];
+    for (int r = 0; r < G; ++r) { sb[r] = 4 * req[r].size(); rb[r] = 4 * nin[r]; }
+    int e = comm_alltoallv(ctx, d_out, sb, d_in, rb);
+    if (e) return e;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tin && ctx->dbg_valid) HIPCHK(ctx, eslam_launch_gather_records(d_in, tin, gb, &ctx->dbg, d_items, ctx->stream));
+    else if (tin) HIPCHK(ctx, hipMemsetAsync(d_items, 0, tin * item, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < G; ++r) { sb[r] = item * nin[r]; rb[r] = item * req[r].size(); }
+    e = comm_alltoallv(ctx, d_items, sb, d_remote->get(), rb);
+    if (e) return e;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // the fetched items in rank order: rank o's start off[o]
     uint64_t r = 0;
     for (uint64_t k = 0; k < slot.size(); ++k)
@@ -1775,40 +1572,33 @@ extern "C" int eslam_gpu_download_records(eslam_ctx* ctx, uint64_t first, uint64
     if (!rc && check_poisoned(ctx)) rc = ESLAM_ERR_HIP;
     if (!rc) rc = materialize(ctx);               // the pending gather writes the ancestors too
     std::vector<uint64_t> slot;
-    double* d_remote = nullptr;
+    Dev<double> d_remote;
     if (coll) {
         const int frc = fetch_remote_records(ctx, rc, first, stride, count, slot, &d_remote);
         if (!rc) rc = frc;
     }
-    if (rc || !count) {
-        (void)hipFree(d_remote);
-        return rc;
-    }
+    if (rc || !count) return rc;
     if (!cpoints) max_cpoints = 0;
     const DebugRec none = {};
     const DebugRec& d = ctx->dbg_valid ? ctx->dbg : none;
-    eslam_particle_record* d_out = nullptr;
-    eslam_cpoint* d_cp = nullptr;
-    uint64_t* d_slot = nullptr;
-    hipError_t e = hipMalloc(&d_out, count * sizeof(eslam_particle_record));
+    Dev<eslam_particle_record> d_out;
+    Dev<eslam_cpoint> d_cp;
+    Dev<uint64_t> d_slot;
+    hipError_t e = d_out.alloc(count * sizeof(eslam_particle_record));
     if (e == hipSuccess && max_cpoints) {
-        e = hipMalloc(&d_cp, count * max_cpoints * sizeof(eslam_cpoint));
+        e = d_cp.alloc(count * max_cpoints * sizeof(eslam_cpoint));
         if (e == hipSuccess) e = hipMemsetAsync(d_cp, 0, count * max_cpoints * sizeof(eslam_cpoint), ctx->stream);
     }
     if (e == hipSuccess && !slot.empty()) {
-        e = hipMalloc(&d_slot, count * 8);
+        e = d_slot.alloc(count * 8);
         if (e == hipSuccess) e = hipMemcpy(d_slot, slot.data(), count * 8, hipMemcpyHostToDevice);
     }
     if (e == hipSuccess)
-        e = eslam_launch_pack_records(ctx->st[0], ctx->st[1], ctx->ctl, first, stride, count, ctx->gbase, ctx->anc, &d, d_out,
+        e = eslam_launch_pack_records(ctx->st[0], ctx->st[1], ctx->ctl, first, stride, count, ctx->gbase, ctx->pt.anc, &d, d_out,
                                       d_cp, max_cpoints, d_slot, d_remote, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d_out, count * sizeof(eslam_particle_record), hipMemcpyDeviceToHost);
     if (e == hipSuccess && max_cpoints) e = hipMemcpy(cpoints, d_cp, count * max_cpoints * sizeof(eslam_cpoint), hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
-    (void)hipFree(d_cp);
-    (void)hipFree(d_slot);
-    (void)hipFree(d_remote);
     if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, (std::string("download_records: ") + hipGetErrorString(e)).c_str());
     return ESLAM_OK;
 }
@@ -1821,13 +1611,13 @@ static MergeParams merge_params(eslam_ctx* ctx, const CowScratch& cs)
 {
     MergeParams mp;
     memset(&mp, 0, sizeof(mp));
-    mp.cnt = ctx->merge_cnt;
+    mp.cnt = ctx->pt.merge_cnt;
     mp.ref = cs.ref;
     mp.frees = cs.frees;
-    mp.off = ctx->lm_off;
-    mp.job = (MergeJob*)ctx->lm_job;
-    mp.codes = ctx->lm_codes;
-    mp.poff = ctx->lm_poff;
+    mp.off = ctx->lmb.off;
+    mp.job = ctx->lmb.job;
+    mp.codes = ctx->lmb.codes;
+    mp.poff = ctx->lmb.poff;
     mp.fault = ctx->fault_host;
     mp.n = ctx->n;
     return mp;
@@ -1860,16 +1650,16 @@ extern "C" int eslam_gpu_map_update(eslam_ctx* ctx, const eslam_scan_patch* patc
     mrec(ctx, 1);
     // the scan on the device: this update's slot is free once the update before last is done
     const uint32_t slot = ctx->scan_slot ^= 1u;
-    if (!ctx->scan_ev[slot]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->scan_ev[slot], hipEventDisableTiming));
+    if (!ctx->scan_ev[slot]) HIPCHK(ctx, ctx->scan_ev[slot].create(false));
     else HIPCHK(ctx, hipEventSynchronize(ctx->scan_ev[slot]));
     const uint64_t sbytes = (uint64_t)(count ? count : 1) * sizeof(ScanPatch);
-    int rc = grow(ctx, &ctx->scan_host[slot], &ctx->scan_host_cap[slot], sbytes, true);
-    if (!rc) rc = grow(ctx, &ctx->scan_dev[slot], &ctx->scan_dev_cap[slot], sbytes, false);
+    int rc = grow(ctx, ctx->scan_host[slot], sbytes);
+    if (!rc) rc = grow(ctx, ctx->scan_dev[slot], sbytes);
     // a scan of more than kScanPartSmall patches merges in parts of kScanPartLarge
     const uint32_t part = count <= kScanPartSmall ? kScanPartSmall : kScanPartLarge;
-    if (!rc && part == kScanPartLarge) rc = grow(ctx, (void**)&ctx->lm_codes, &ctx->lm_codes_cap, ctx->cap * 2 * kScanPartLarge, false);
+    if (!rc && part == kScanPartLarge) rc = grow(ctx, ctx->lmb.codes, ctx->cap * 2 * kScanPartLarge);
     if (rc) return rc;
-    ScanPatch* sh = (ScanPatch*)ctx->scan_host[slot];
+    ScanPatch* sh = ctx->scan_host[slot];
     for (uint32_t k = 0; k < count; ++k)
         sh[k] = ScanPatch{patches[k].position[0], patches[k].position[1], patches[k].position[2], patches[k].stdev};
     if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->scan_dev[slot], sh, sbytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1878,7 +1668,7 @@ extern "C" int eslam_gpu_map_update(eslam_ctx* ctx, const eslam_scan_patch* patc
     for (uint32_t c0 = 0; c0 == 0 || c0 < count; c0 += part) {
         const uint32_t cm = count - c0 < part ? count - c0 : part;
         const SidRef sr{ctx->st[0].sid, ctx->st[1].sid, ctx->ctl};
-        const CowScratch cs = cow_layout(ctx->cow, ctx->cap);
+        const CowScratch cs = cow_layout(ctx->pt.cow, ctx->cap);
         HIPCHK(ctx, eslam_launch_store_refs(sr, ctx->n, store_pool(ctx->cap), &cs, fuse ? &gv : nullptr, ctx->lm.tgen,
                                             ctx->stream));
         if (!c0) mrec(ctx, 2);
@@ -1890,9 +1680,9 @@ extern "C" int eslam_gpu_map_update(eslam_ctx* ctx, const eslam_scan_patch* patc
         mp.aux = (ctx->cfg.flags & ESLAM_FLAG_NO_AUX_GATHER) ? 0u : 1u;
         mp.acc = c0 ? 1u : 0u;
         mp.m = cm;
-        mp.sp = (const ScanPatch*)ctx->scan_dev[slot] + c0;
-        mp.codes = ctx->lm_codes;
-        HIPCHK(ctx, eslam_launch_map_plan(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &ctx->lm, &mp, ctx->lm_pgc, ctx->stream));
+        mp.sp = ctx->scan_dev[slot] + c0;
+        mp.codes = ctx->lmb.codes;
+        HIPCHK(ctx, eslam_launch_map_plan(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &ctx->lm, &mp, ctx->lmb.pgc, ctx->stream));
         if (!c0) mrec(ctx, 3);
         HIPCHK(ctx, eslam_launch_map_merge(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &ctx->lm, &mp, ctx->stream));
         if (fuse) {
@@ -1932,10 +1722,10 @@ extern "C" int eslam_gpu_map_match(eslam_ctx* ctx, const eslam_scan_patch* patch
     if (inline_sp) {
         for (size_t k = 0; k < s.size(); ++k) mp.spi[k] = s[k];
     } else {
-        rc = grow(ctx, &ctx->match_sp, &ctx->match_cap, s.size() * sizeof(ScanPatch), false);
+        rc = grow(ctx, ctx->lmb.match_sp, s.size() * sizeof(ScanPatch));
         if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->match_sp, s.data(), s.size() * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
-        mp.sp = (const ScanPatch*)ctx->match_sp;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->lmb.match_sp, s.data(), s.size() * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
+        mp.sp = ctx->lmb.match_sp;
     }
     HIPCHK(ctx, eslam_launch_map_match(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, store_of(ctx), &mp, ctx->stream));
     xrec(ctx, 1);
@@ -2007,26 +1797,18 @@ extern "C" int eslam_gpu_get_particle_map(eslam_ctx* ctx, uint64_t index, uint32
 // ---------------------------------------------------------------------------------------
 // the shared map: processMap's merge into the one grid (eslam_shared_map.hip)
 // ---------------------------------------------------------------------------------------
-static void sm_free_grid(SmGrid* g)
-{
-    (void)hipFree(g->cell_start); (void)hipFree(g->patch); (void)hipFree(g->height); (void)hipFree(g->occ);
-    (void)hipFree(g->cell_tab);
-    *g = SmGrid{};
-}
-
 // a second set of the grid's arrays with room for `cap` patches; false (nothing held) when
 // the device has no room
-static bool sm_alloc_grid(SmGrid* g, uint64_t ncell, uint64_t cap, bool heights)
+static bool sm_alloc_grid(GridBufs* g, uint64_t ncell, uint64_t cap, bool heights)
 {
-    *g = SmGrid{};
+    *g = GridBufs{};
     const uint64_t c = cap ? cap : 1;
-    bool ok = hipMalloc(&g->cell_start, (ncell + 1) * 4) == hipSuccess && hipMalloc(&g->patch, c * sizeof(float2)) == hipSuccess &&
-              hipMalloc(&g->occ, ((ncell + 31) / 32) * 4) == hipSuccess &&
-              hipMalloc(&g->cell_tab, ncell * sizeof(uint4)) == hipSuccess;
-    if (ok && heights) ok = hipMalloc(&g->height, c * 4) == hipSuccess;
+    bool ok = g->cells.alloc((ncell + 1) * 4) == hipSuccess && g->patch.alloc(c * sizeof(float2)) == hipSuccess &&
+              g->occ.alloc(((ncell + 31) / 32) * 4) == hipSuccess && g->cell_tab.alloc(ncell * sizeof(uint4)) == hipSuccess;
+    if (ok && heights) ok = g->height.alloc(c * 4) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        sm_free_grid(g);
+        *g = GridBufs{};
     }
     return ok;
 }
@@ -2041,19 +1823,14 @@ static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t sca
                    off_seg = off_add + up(ncell * 4), off_tch = off_seg + up(ncell * 4), off_cnt = off_tch + up(ncell * 4),
                    off_sort = off_cnt + up(kSmCounters * 8), off_sp = off_sort + up(sort_bytes),
                    total = off_sp + up(scan_patches * sizeof(ScanPatch));
-    if (total > ctx->sm_bytes) {
+    if (total > ctx->sm_mem.cap()) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->sm_mem);
-        ctx->sm_mem = nullptr;
-        ctx->sm_bytes = 0;
-        if (hipMalloc(&ctx->sm_mem, total) != hipSuccess) {
+        if (ctx->sm_mem.alloc(total) != hipSuccess) {
             (void)hipGetLastError();
-            ctx->sm_mem = nullptr;
             return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the run scratch (lower max_records)");
         }
-        ctx->sm_bytes = total;
     }
-    char* m = (char*)ctx->sm_mem;
+    char* m = ctx->sm_mem.as<char>();
     s->keys = (uint32_t*)(m + off_keys);
     s->vals = (uint32_t*)(m + off_vals);
     s->keys_out = (uint32_t*)(m + off_ko);
@@ -2107,7 +1884,7 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
     HIPCHK(ctx, hipMemsetAsync(sc.cnt, 0, kSmCounters * 8, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(sc.touched, 0, ncell * 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // `patches` is the caller's
-    SmGrid spare = {};
+    GridBufs spare;
     uint64_t spare_cap = 0;
     uint64_t cnt[kSmCounters] = {};
     uint64_t done = 0, runs = 0, placed_all = 0;
@@ -2132,43 +1909,35 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
                 rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: the grid would pass 2^32 - 1 patches");
                 break;
             }
-            if (!spare.cell_start || spare_cap < need) {
-                sm_free_grid(&spare);
+            if (!spare.cells || spare_cap < need) {
                 uint64_t want = need + need / 4;
                 want = want > 0xffffffffull ? 0xffffffffull : want;
-                spare_cap = want;
-                if (!sm_alloc_grid(&spare, ncell, want, ctx->d_height != nullptr)) {
-                    spare_cap = need;
-                    if (!sm_alloc_grid(&spare, ncell, need, ctx->d_height != nullptr)) {
-                        spare_cap = 0;
-                        rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
-                        break;
-                    }
+                const bool h = ctx->grid.height != nullptr;
+                spare_cap = sm_alloc_grid(&spare, ncell, want, h) ? want : sm_alloc_grid(&spare, ncell, need, h) ? need : 0;
+                if (!spare_cap) {
+                    rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
+                    break;
                 }
             }
-            const SmGrid cur{ctx->d_cells, ctx->d_patch, ctx->d_height, ctx->d_occ, ctx->d_cell_tab};
-            if ((he = eslam_launch_sm_merge(ctx->st[0], ctx->st[1], ctx->ctl, &run, &cur, &spare, &sc, ctx->stream)) != hipSuccess) break;
+            const SmGrid cur = ctx->grid.view(), next = spare.view();
+            if ((he = eslam_launch_sm_merge(ctx->st[0], ctx->st[1], ctx->ctl, &run, &cur, &next, &sc, ctx->stream)) != hipSuccess) break;
             uint32_t total = 0;
-            if ((he = hipMemcpyAsync(&total, spare.cell_start + ncell, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
+            if ((he = hipMemcpyAsync(&total, next.cell_start + ncell, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
             if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
             // the swap: every later launch takes the grid from ctx->map (K1's window staging, the
             // match, the hash build and get_map read these pointers at their call)
-            const uint64_t old_cap = ctx->map_np_cap;
-            ctx->d_cells = spare.cell_start; ctx->d_patch = spare.patch; ctx->d_height = spare.height;
-            ctx->d_occ = spare.occ; ctx->d_cell_tab = spare.cell_tab;
+            std::swap(ctx->grid, spare);                          // the next run rebuilds into the old arrays
+            std::swap(ctx->map_np_cap, spare_cap);
             ctx->map_np = total;
-            ctx->map_np_cap = spare_cap;
-            ctx->map.cell_start = ctx->d_cells; ctx->map.patch = ctx->d_patch; ctx->map.height = ctx->d_height;
-            ctx->map.occ = ctx->d_occ; ctx->map.cell_tab = ctx->d_cell_tab;
-            spare = cur;                                          // the next run rebuilds into the old arrays
-            spare_cap = old_cap;
+            ctx->map.cell_start = ctx->grid.cells; ctx->map.patch = ctx->grid.patch; ctx->map.height = ctx->grid.height;
+            ctx->map.occ = ctx->grid.occ; ctx->map.cell_tab = ctx->grid.cell_tab;
         }
         placed_all += placed;
         done = i0 + run.R / P;
         ++runs;
     }
     if (he == hipSuccess) he = hipMemcpy(cnt, sc.cnt, sizeof(cnt), hipMemcpyDeviceToHost);
-    sm_free_grid(&spare);                                        // (hipFree waits for the device)
+    spare = GridBufs{};                                          // (hipFree waits for the device)
     if (info) {
         info->particles_done = done;
         info->patches_placed = placed_all;
@@ -2194,7 +1963,7 @@ extern "C" int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* hei
     if (width) *width = ctx->map.width;
     if (height) *height = ctx->map.height_cells;
     if (n_patches) *n_patches = ctx->map_np;
-    if (has_height) *has_height = ctx->d_height ? 1 : 0;
+    if (has_height) *has_height = ctx->grid.height ? 1 : 0;
     return ESLAM_OK;
 }
 
@@ -2206,16 +1975,16 @@ extern "C" int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* me
     const uint64_t np = ctx->map_np, ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
     if (patch_capacity < np) return fail(ctx, ESLAM_ERR_INVALID_ARG, "get_map: patch_capacity is below the grid's patch count (eslam_gpu_map_size)");
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(cell_start, ctx->d_cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(cell_start, ctx->grid.cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
     if (!np) return ESLAM_OK;
     std::vector<float2> patch(np);
-    HIPCHK(ctx, hipMemcpy(patch.data(), ctx->d_patch, np * sizeof(float2), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(patch.data(), ctx->grid.patch, np * sizeof(float2), hipMemcpyDeviceToHost));
     for (uint64_t k = 0; k < np; ++k) {
         mean[k] = patch[k].x;
         stdev[k] = patch[k].y;
     }
     if (patch_height) {
-        if (ctx->d_height) HIPCHK(ctx, hipMemcpy(patch_height, ctx->d_height, np * 4, hipMemcpyDeviceToHost));
+        if (ctx->grid.height) HIPCHK(ctx, hipMemcpy(patch_height, ctx->grid.height, np * 4, hipMemcpyDeviceToHost));
         else memset(patch_height, 0, np * 4);
     }
     return ESLAM_OK;
@@ -2264,24 +2033,13 @@ static int scan_frame(eslam_ctx* ctx, const eslam_scan_params* p, double ray, dm
 
 // a buffer of at least `bytes`: the new one exists before the old one goes, so a failed
 // allocation leaves the context with what it had
-static int scan_grow(eslam_ctx* ctx, void** buf, uint64_t* cap, uint64_t bytes, uint64_t unit, const char* what)
+template <typename B>
+static int scan_grow(eslam_ctx* ctx, B& buf, uint64_t bytes, uint64_t unit, const char* what)
 {
-    if (bytes <= *cap * unit) return ESLAM_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t want = bytes + bytes / 4;
-    want = (want + unit - 1) / unit;
-    void* nb = nullptr;
-    if (hipMalloc(&nb, want * unit) != hipSuccess) {
-        (void)hipGetLastError();
-        want = (bytes + unit - 1) / unit;
-        if (hipMalloc(&nb, want * unit) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, what);
-        }
-    }
-    (void)hipFree(*buf);
-    *buf = nb;
-    *cap = want;
+    hipError_t he = hipSuccess;
+    const int rc = buf.grow_keep(bytes, unit, ctx->stream, &he);
+    if (rc == ESLAM_ERR_OUT_OF_MEMORY) return fail(ctx, rc, what);
+    HIPCHK(ctx, he);
     return ESLAM_OK;
 }
 
@@ -2292,7 +2050,7 @@ static int scan_build(eslam_ctx* ctx, const dm_scan_frame* f, ScanReading* rd, c
     if (info) info->points = n;
     if (!n) return ESLAM_OK;
     const uint64_t need = eslam_scan_work_bytes(n, nullptr, nullptr);
-    if (const int rc_ = scan_grow(ctx, &ctx->scan_mem, &ctx->scan_bytes, need, 1, "scan: no device memory for the build's scratch"))
+    if (const int rc_ = scan_grow(ctx, ctx->scan_mem, need, 1, "scan: no device memory for the build's scratch"))
         return rc_;
     ScanWork w;
     (void)eslam_scan_work_bytes(n, ctx->scan_mem, &w);
@@ -2315,7 +2073,7 @@ static int scan_build(eslam_ctx* ctx, const dm_scan_frame* f, ScanReading* rd, c
     HIPCHK(ctx, eslam_launch_scan_count(f, &w, nheads, (uint32_t)binned, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&total, w.a + nheads, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (const int rc_ = scan_grow(ctx, (void**)&ctx->scan_out, &ctx->scan_out_cap, (uint64_t)total * sizeof(eslam_scan_patch),
+    if (const int rc_ = scan_grow(ctx, ctx->scan_out, (uint64_t)total * sizeof(eslam_scan_patch),
                                   sizeof(eslam_scan_patch), "scan: no device memory for the patches"))
         return rc_;
     HIPCHK(ctx, eslam_launch_scan_emit(f, &w, nheads, (uint32_t)binned, ctx->scan_out, ctx->stream));
@@ -2392,10 +2150,10 @@ static GatherView gather_view(eslam_ctx* ctx)
 {
     GatherView gv;
     memset(&gv, 0, sizeof(gv));
-    gv.marks = ctx->marks;
-    gv.row_first = ctx->tile_first;
-    gv.anc = ctx->anc;
-    gv.recs = ctx->sharded ? (const Rec*)ctx->recvbuf : nullptr;
+    gv.marks = ctx->pt.marks;
+    gv.row_first = ctx->pt.tile_first;
+    gv.anc = ctx->pt.anc;
+    gv.recs = ctx->sharded ? ctx->recvbuf.as<const Rec>() : nullptr;
     gv.record = keep_ancestors(ctx) ? 1u : 0u;
     gv.multi = ctx->sharded ? 1u : 0u;
     return gv;
@@ -2410,14 +2168,14 @@ static GatherView gather_view(eslam_ctx* ctx)
 static int store_receive(eslam_ctx* ctx)
 {
     const SidRef sr{ctx->st[0].sid, ctx->st[1].sid, ctx->ctl};
-    const CowScratch cs = cow_layout(ctx->cow, ctx->cap);
+    const CowScratch cs = cow_layout(ctx->pt.cow, ctx->cap);
     HIPCHK(ctx, eslam_launch_store_refs(sr, ctx->n, store_pool(ctx->cap), &cs, nullptr, ctx->lm.tgen, ctx->stream));
-    int rc = grow(ctx, (void**)&ctx->payoff, &ctx->payoff_cap, (ctx->nrecv_maps + 1) * 4, false);
-    if (!rc) rc = grow(ctx, (void**)&ctx->rhead, &ctx->rhead_cap, (ctx->nrecv_maps + 1) * 4, false);
+    int rc = grow(ctx, ctx->payoff, (ctx->nrecv_maps + 1) * 4);
+    if (!rc) rc = grow(ctx, ctx->rhead, (ctx->nrecv_maps + 1) * 4);
     if (rc) return rc;
     const MergeParams mp = merge_params(ctx, cs);
     HIPCHK(ctx, eslam_launch_store_receive(sr, ctx->ctl, &ctx->lm, &mp, ctx->n, &cs, ctx->recvhdr, ctx->nrecv_maps, ctx->payoff,
-                                           ctx->rhead, ctx->recvpay, ctx->lm_pgc, ctx->stream));
+                                           ctx->rhead, ctx->recvpay, ctx->lmb.pgc, ctx->stream));
     ctx->cow_pending = false;
     return ESLAM_OK;
 }
@@ -2562,7 +2320,7 @@ static FinParams fin_params(eslam_ctx* ctx, uint32_t mode)
 static int abort_pending_gather(eslam_ctx* ctx, hipError_t e, int rc = ESLAM_ERR_HIP)
 {
     if (e != hipSuccess) fail(ctx, ESLAM_ERR_HIP, (std::string("sharded resample: ") + hipGetErrorString(e)).c_str());
-    (void)hipMemsetAsync(ctx->marks, 0, ctx->cap * 4, ctx->stream);
+    (void)hipMemsetAsync(ctx->pt.marks, 0, ctx->cap * 4, ctx->stream);
     (void)hipMemsetAsync(&ctx->ctl->flip, 0, sizeof(uint32_t), ctx->stream);
     (void)hipMemsetAsync(&ctx->ctl->gather, 0, sizeof(uint32_t), ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
@@ -2583,9 +2341,9 @@ static int exchange_maps(eslam_ctx* ctx, uint64_t nsend, uint64_t nrecv, const u
 {
     const int G = ctx->comm.nranks, me = ctx->comm.rank;
     const uint64_t R = eslam_record_bytes(), H = sizeof(MapPayHdr), P = sizeof(MapPayPage);
-    int rc = grow(ctx, &ctx->sendhdr, &ctx->sendhdr_cap, (nsend ? nsend : 1) * H, false);
-    if (!rc) rc = grow(ctx, &ctx->recvhdr, &ctx->recvhdr_cap, (nrecv ? nrecv : 1) * H, false);
-    if (!rc) rc = grow(ctx, (void**)&ctx->payoff, &ctx->payoff_cap, (nsend + nrecv + 2) * 4, false);
+    int rc = grow(ctx, ctx->sendhdr, (nsend ? nsend : 1) * H);
+    if (!rc) rc = grow(ctx, ctx->recvhdr, (nrecv ? nrecv : 1) * H);
+    if (!rc) rc = grow(ctx, ctx->payoff, (nsend + nrecv + 2) * 4);
     if (rc) return rc;
     PaySeg seg;
     memset(&seg, 0, sizeof(seg));
@@ -2607,8 +2365,8 @@ static int exchange_maps(eslam_ctx* ctx, uint64_t nsend, uint64_t nrecv, const u
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpy(&h[mg::kCountsAll], ctx->mg + mg::kCountsAll, 8ull * G * G, hipMemcpyDeviceToHost));
     for (int r = 0; r < G; ++r) { rpg[r] = h[mg::kCountsAll + r * G + me]; totr += rpg[r]; }
-    rc = grow(ctx, &ctx->sendpay, &ctx->sendpay_cap, ((uint64_t)bound[G] + 1) * P, false);
-    if (!rc) rc = grow(ctx, &ctx->recvpay, &ctx->recvpay_cap, (totr + 1) * P, false);
+    rc = grow(ctx, ctx->sendpay, ((uint64_t)bound[G] + 1) * P);
+    if (!rc) rc = grow(ctx, ctx->recvpay, (totr + 1) * P);
     if (rc) return rc;
     HIPCHK(ctx, eslam_launch_pay_pack(ctx->st[0], ctx->st[1], ctx->ctl, ctx->sendbuf, nsend, ctx->gbase, &ctx->lm, ctx->sendhdr,
                                       ctx->payoff, ctx->sendpay, xs));
@@ -2645,7 +2403,7 @@ static int run_update_tail_multi(eslam_ctx* ctx, uint32_t mode, bool timed)
     sp.multi = 1;
     sp.tag = ctx->scan_tag = ctx->scan_tag % 7u + 1u;         // differs from the previous launch's
     const FusedFin ff{ctx->recs, fp, ctx->fin_word, ++ctx->fin_epoch, G * kNShard};
-    HIPCHK(ctx, eslam_launch_normalize_scan(ctx->st[0], ctx->st[1], &sp, ctx->ctl, ctx->tile_sum, ctx->mg + mg::kTotal,
+    HIPCHK(ctx, eslam_launch_normalize_scan(ctx->st[0], ctx->st[1], &sp, ctx->ctl, ctx->pt.tile_sum, ctx->mg + mg::kTotal,
                                             fused ? &ff : nullptr, ctx->stream));
     rc = comm_allgather(ctx, ctx->mg + mg::kTotal, ctx->mg + mg::kTotals, 8);
     if (rc) return rc;
@@ -2655,8 +2413,8 @@ static int run_update_tail_multi(eslam_ctx* ctx, uint32_t mode, bool timed)
     // then the launch's epoch (system-scope release)
     PlanParams pp = plan_params(ctx);
     const uint64_t epoch = ++ctx->seg_epoch;
-    HIPCHK(ctx, eslam_launch_segments_multi(ctx->st[0], ctx->st[1], &sp, &pp, ctx->ctl, ctx->tile_sum, ctx->marks,
-                                            ctx->tile_first, ctx->mg + mg::kTotals, ctx->jump, ctx->range,
+    HIPCHK(ctx, eslam_launch_segments_multi(ctx->st[0], ctx->st[1], &sp, &pp, ctx->ctl, ctx->pt.tile_sum, ctx->pt.marks,
+                                            ctx->pt.tile_first, ctx->mg + mg::kTotals, ctx->jump, ctx->pt.range,
                                             ctx->mg + mg::kFirstLast, h + mg::kTotals, h + mg::kHostEpoch, epoch,
                                             ctx->stream));
     if (timed) rec(ctx, 3);
@@ -2668,8 +2426,8 @@ static int run_update_tail_multi(eslam_ctx* ctx, uint32_t mode, bool timed)
         if (G > 1) {                         // one rank exchanges nothing: no side stream
             if (!ctx->xstream) {
                 HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->xstream, hipStreamNonBlocking));
-                HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_seg, hipEventDisableTiming));
-                HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_x, hipEventDisableTiming));
+                HIPCHK(ctx, ctx->ev_seg.create(false));
+                HIPCHK(ctx, ctx->ev_x.create(false));
             }
             HIPCHK(ctx, hipEventRecord(ctx->ev_seg, ctx->stream));
         }
@@ -2766,13 +2524,13 @@ static int exchange_tail(eslam_ctx* ctx, uint64_t epoch, PlanParams& pp, uint64_
         }
         if (any) {
             const bool maps = particle_maps(ctx);
-            rc = grow(ctx, &ctx->sendbuf, &ctx->send_cap, nsend * R, false);
-            if (!rc) rc = grow(ctx, &ctx->recvbuf, &ctx->recv_cap, nrecv * R, false);
+            rc = grow(ctx, ctx->sendbuf, nsend * R);
+            if (!rc) rc = grow(ctx, ctx->recvbuf, nrecv * R);
             if (rc) return abort_pending_gather(ctx, hipSuccess, rc);
             // a side stream starts after the segments kernel (its records and ranges)
             if (xs != ctx->stream) HIPCHK(ctx, hipStreamWaitEvent(xs, ctx->ev_seg, 0));
             if (queued) *queued = true;
-            const hipError_t e = eslam_launch_pack(ctx->st[0], ctx->st[1], ctx->ctl, &pp, ctx->range, ctx->mg + mg::kFirstLast,
+            const hipError_t e = eslam_launch_pack(ctx->st[0], ctx->st[1], ctx->ctl, &pp, ctx->pt.range, ctx->mg + mg::kFirstLast,
                                                    nsend, ctx->sendbuf, xs);
             if (e != hipSuccess) return abort_pending_gather(ctx, e);
             rc = comm_alltoallv(ctx, ctx->sendbuf, sb, ctx->recvbuf, rb, xs);
@@ -2792,7 +2550,7 @@ static int exchange_tail(eslam_ctx* ctx, uint64_t epoch, PlanParams& pp, uint64_
         own_chunks(O0, O1, ctx->gbase, ctx->n, pp.J, own_lo, own_hi);
     }
     // marks of the migrated outputs; the gather is fused into the next k_project_weight
-    HIPCHK(ctx, eslam_launch_expand(ctx->recvbuf, nrecv, ctx->gbase, ctx->marks, ctx->tile_first, xs));
+    HIPCHK(ctx, eslam_launch_expand(ctx->recvbuf, nrecv, ctx->gbase, ctx->pt.marks, ctx->pt.tile_first, xs));
     return ESLAM_OK;
 }
 
@@ -2817,8 +2575,8 @@ static int run_update_tail(eslam_ctx* ctx, uint32_t mode, bool timed)
     ScanParams sp = scan_params(ctx, mode == FIN_UPDATE, mode == FIN_UPDATE || mode == FIN_NORMALIZE, false);
     sp.tag = ctx->scan_tag = ctx->scan_tag % 7u + 1u;         // differs from the previous launch's
     FusedFin ff{ctx->shards, fp, ctx->fin_word, ++ctx->fin_epoch, kNShard};
-    HIPCHK(ctx, eslam_launch_normalize_segments(ctx->st[0], ctx->st[1], &sp, ctx->ctl, ctx->tile_sum, ctx->marks,
-                                                ctx->tile_first, ctx->jump, fused ? &ff : nullptr, ctx->stream));
+    HIPCHK(ctx, eslam_launch_normalize_segments(ctx->st[0], ctx->st[1], &sp, ctx->ctl, ctx->pt.tile_sum, ctx->pt.marks,
+                                                ctx->pt.tile_first, ctx->jump, fused ? &ff : nullptr, ctx->stream));
     if (timed) rec(ctx, 3);
     // the gather itself is fused into the next k_project_weight (or materialize())
     if (timed) rec(ctx, 4);
@@ -2853,13 +2611,13 @@ static int sample_from_hash(eslam_ctx* ctx, const eslam_step_input* in, const St
     const double weight = ((S / (double)N) * ctx->cfg.hash_avg_factor) * rel;   // getWeightAvg() * avgFactor * rel
     const uint64_t n = ctx->n;
     if (ctx->sort_cap < n) {
-        (void)hipFree(ctx->d_sort); ctx->d_sort = nullptr; ctx->sort_cap = 0;
-        (void)hipFree(ctx->sort_tmp); ctx->sort_tmp = nullptr; ctx->sort_tmp_bytes = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_sort, sizeof(uint32_t) * 4 * n));
+        ctx->d_sort.reset(); ctx->sort_cap = 0;
+        ctx->sort_tmp.reset(); ctx->sort_tmp_bytes = 0;
+        HIPCHK(ctx, ctx->d_sort.alloc(sizeof(uint32_t) * 4 * n));
         size_t bytes = 0;
         HIPCHK(ctx, eslam_hash_sort(ctx->st[0], ctx->st[1], ctx->ctl, n, nullptr, nullptr, nullptr, nullptr, nullptr, &bytes,
                                     ctx->stream));
-        HIPCHK(ctx, hipMalloc(&ctx->sort_tmp, bytes ? bytes : 1));
+        HIPCHK(ctx, ctx->sort_tmp.alloc(bytes ? bytes : 1));
         ctx->sort_tmp_bytes = bytes;
         ctx->sort_cap = n;
     }
@@ -2883,16 +2641,16 @@ static int sample_from_hash(eslam_ctx* ctx, const eslam_step_input* in, const St
             total += cnt[r];
         }
         for (int d = 0; d < G; ++d) { sb[d] = cnt[me] * 8; rb[d] = cnt[d] * 8; }
-        rc = grow(ctx, &ctx->hsend, &ctx->hsend_cap, G * cnt[me] * 8 + 8, false);
-        if (!rc) rc = grow(ctx, &ctx->hrecv, &ctx->hrecv_cap, total * 8 + 8, false);
+        rc = grow(ctx, ctx->hsend, G * cnt[me] * 8 + 8);
+        if (!rc) rc = grow(ctx, ctx->hrecv, total * 8 + 8);
         size_t sbytes = 0;
         (void)eslam_radix_sort_pairs(nullptr, nullptr, nullptr, nullptr, total, nullptr, &sbytes, ctx->stream);
-        if (!rc) rc = grow(ctx, &ctx->hsort, &ctx->hsort_cap, 16 * (total + 1) + sbytes, false);
+        if (!rc) rc = grow(ctx, ctx->hsort, 16 * (total + 1) + sbytes);
         if (rc) return rc;
         HIPCHK(ctx, eslam_launch_hash_candidates(keys_out, order, cnt[me], ctx->gbase, G, ctx->hsend, ctx->stream));
         rc = comm_alltoallv(ctx, ctx->hsend, sb.data(), ctx->hrecv, rb.data());
         if (rc) return rc;
-        uint32_t* ck = (uint32_t*)ctx->hsort;
+        uint32_t* ck = ctx->hsort.as<uint32_t>();
         uint32_t* cv = ck + total + 1;
         uint32_t* sk = cv + total + 1;
         uint32_t* so = sk + total + 1;
@@ -2902,11 +2660,7 @@ static int sample_from_hash(eslam_ctx* ctx, const eslam_step_input* in, const St
     }
     std::vector<uint32_t> draws(k);
     for (uint64_t j = 0; j < k; ++j) draws[j] = (uint32_t)((uint64_t)(uint32_t)dm_libc_rand(ctx->libcp) % bsize);
-    if (ctx->draws_cap < k) {
-        (void)hipFree(ctx->d_draws); ctx->d_draws = nullptr; ctx->draws_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->d_draws, sizeof(uint32_t) * k));
-        ctx->draws_cap = k;
-    }
+    if (ctx->d_draws.cap() < sizeof(uint32_t) * k) HIPCHK(ctx, ctx->d_draws.alloc(sizeof(uint32_t) * k));
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_draws, draws.data(), sizeof(uint32_t) * k, hipMemcpyHostToDevice, ctx->stream));
     if (ctx->sharded)
         HIPCHK(ctx, eslam_launch_hash_replace_global(ctx->st[0], ctx->st[1], ctx->ctl, gorder, ctx->d_draws, k, ctx->gbase,
@@ -2990,10 +2744,10 @@ static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project,
         const uint32_t maxc = p.m ? p.m : 1u;
         if (ctx->dbg_cap < ctx->n || ctx->dbg.maxc < maxc) {
             free_debug(ctx);
-            HIPCHK(ctx, hipMalloc(&ctx->dbg.meas, ctx->cap * 32));
-            HIPCHK(ctx, hipMalloc(&ctx->dbg.ncp, ctx->cap));
-            HIPCHK(ctx, hipMalloc(&ctx->dbg.cp, ctx->cap * 48ull * maxc));
-            HIPCHK(ctx, hipMalloc(&ctx->dbg.resampled, 4));
+            HIPCHK(ctx, ctx->dbgb.meas.alloc(ctx->cap * 32, &ctx->dbg.meas));
+            HIPCHK(ctx, ctx->dbgb.ncp.alloc(ctx->cap, &ctx->dbg.ncp));
+            HIPCHK(ctx, ctx->dbgb.cp.alloc(ctx->cap * 48ull * maxc, &ctx->dbg.cp));
+            HIPCHK(ctx, ctx->dbgb.resampled.alloc(4, &ctx->dbg.resampled));
             ctx->dbg.maxc = maxc;
             ctx->dbg_cap = ctx->cap;
         }
@@ -3003,7 +2757,7 @@ static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project,
     if (weight) {
         // K1's parked per-bucket sums (K1Args::bspill): one slot per chunk of this context
         const uint64_t csz = 64ull * p.J;
-        const int rc = grow(ctx, (void**)&ctx->bspill, &ctx->bspill_cap, k1_bspill_bytes((ctx->n + csz - 1) / csz), false);
+        const int rc = grow(ctx, ctx->bspill, k1_bspill_bytes((ctx->n + csz - 1) / csz));
         if (rc) return rc;
     }
     rec(ctx, 0);
@@ -3137,50 +2891,25 @@ extern "C" int eslam_gpu_sync(eslam_ctx* ctx, eslam_update_info* info)
         info->map_tiles_evicted = c.map_evicted;
         info->map_pages_free = c.pg_nfree > c.pg_cursor ? c.pg_nfree - c.pg_cursor : 0;
     }
-    if (ctx->timing && ctx->ring_steps) {
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (uint32_t k = 0; k < ctx->ring_steps; ++k) {
-            hipEvent_t* e = &ctx->ring[5 * k];
-            float ms;
-            for (int j = 0; j < 4; ++j) { ms = 0; (void)hipEventElapsedTime(&ms, e[j], e[j + 1]); acc[j] += ms; }
-            ms = 0; (void)hipEventElapsedTime(&ms, e[0], e[4]); acc[4] += ms;
-        }
-        eslam_kernel_times& t = ctx->times;
-        const double inv = 1.0 / ctx->ring_steps;
+    double acc[5];
+    eslam_kernel_times& t = ctx->times;
+    if (const uint32_t steps = ctx->timing ? ctx->ring.sums(acc) : 0) {
+        const double inv = 1.0 / steps;
         t.project_weight_ms = (float)(acc[0] * inv);
         t.finalize_ms = (float)(acc[1] * inv);
         t.normalize_scan_ms = (float)(acc[2] * inv);
         t.resample_ms = (float)(acc[3] * inv);
         t.total_ms = (float)(acc[4] * inv);
-        ctx->ring_steps = 0;
     }
-    if (ctx->timing && ctx->mring_steps) {
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (uint32_t k = 0; k < ctx->mring_steps; ++k) {
-            hipEvent_t* e = &ctx->mring[5 * k];
-            float ms;
-            for (int j = 0; j < 4; ++j) { ms = 0; (void)hipEventElapsedTime(&ms, e[j], e[j + 1]); acc[j] += ms; }
-            ms = 0; (void)hipEventElapsedTime(&ms, e[0], e[4]); acc[4] += ms;
-        }
-        eslam_kernel_times& t = ctx->times;
-        const double inv = 1.0 / ctx->mring_steps;
+    if (const uint32_t steps = ctx->timing ? ctx->mring.sums(acc) : 0) {
+        const double inv = 1.0 / steps;
         t.map_gather_ms = (float)(acc[0] * inv);
         t.map_cow_ms = (float)(acc[1] * inv);
         t.map_plan_ms = (float)(acc[2] * inv);
         t.map_merge_ms = (float)(acc[3] * inv);
         t.map_total_ms = (float)(acc[4] * inv);
-        ctx->mring_steps = 0;
     }
-    if (ctx->timing && ctx->xring_steps) {
-        double acc = 0;
-        for (uint32_t k = 0; k < ctx->xring_steps; ++k) {
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ctx->xring[2 * k], ctx->xring[2 * k + 1]);
-            acc += ms;
-        }
-        ctx->times.map_match_ms = (float)(acc / ctx->xring_steps);
-        ctx->xring_steps = 0;
-    }
+    if (const uint32_t steps = ctx->timing ? ctx->xring.sums(acc) : 0) t.map_match_ms = (float)(acc[0] / steps);
     return take_update_error(ctx);
 }
 
@@ -3241,11 +2970,11 @@ extern "C" int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index
     if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
     if (!ctx->n) { *index = 0; return ESLAM_OK; }
     if (const int rc0 = materialize(ctx)) return rc0;
-    uint64_t* out = reinterpret_cast<uint64_t*>(ctx->scratch);
+    uint64_t* out = ctx->scratch.as<uint64_t>();
     HIPCHK(ctx, eslam_launch_best_index(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, out, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->scratch, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t* h = reinterpret_cast<const uint64_t*>(ctx->scratch_host);
+    const uint64_t* h = ctx->scratch_host.as<const uint64_t>();
     if (!ctx->sharded) {
         *index = h[1] == ~0ull ? 0 : h[1];
         return ESLAM_OK;
@@ -3293,7 +3022,7 @@ extern "C" int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double
             total += nch[r];
         }
         const uint64_t rec = 5 * sizeof(double);
-        if (centroid_bytes(ctx->gall.data(), G, J) > ctx->cent_bytes)
+        if (centroid_bytes(ctx->gall.data(), G, J) > ctx->cent.cap())
             return fail(ctx, ESLAM_ERR_HIP, "getCentroid: buffer not sized by set_comm");
         double* mine = ctx->cent;
         double* all = mine + maxch * 5;
@@ -3367,10 +3096,10 @@ extern "C" int eslam_gpu_get_ancestors(eslam_ctx* ctx, uint32_t* out, uint64_t n
 {
     if (!ctx || !out) return ESLAM_ERR_INVALID_ARG;
     if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!ctx->has_anc || !ctx->anc) return fail(ctx, ESLAM_ERR_INVALID_ARG, "no ancestors recorded (ESLAM_FLAG_RECORD_ANCESTORS)");
+    if (!ctx->has_anc || !ctx->pt.anc) return fail(ctx, ESLAM_ERR_INVALID_ARG, "no ancestors recorded (ESLAM_FLAG_RECORD_ANCESTORS)");
     if (const int rc = materialize(ctx)) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, ctx->anc, (n < ctx->n ? n : ctx->n) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, ctx->pt.anc, (n < ctx->n ? n : ctx->n) * 4, hipMemcpyDeviceToHost));
     return ESLAM_OK;
 }
 
@@ -3379,9 +3108,9 @@ extern "C" int eslam_gpu_enable_timing(eslam_ctx* ctx, int enable)
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->timing = enable != 0;
-    ctx->ring_steps = 0;
-    ctx->mring_steps = 0;
-    ctx->xring_steps = 0;
+    ctx->ring.clear();
+    ctx->mring.clear();
+    ctx->xring.clear();
     return ESLAM_OK;
 }
 
@@ -3392,20 +3121,17 @@ extern "C" int eslam_gpu_get_kernel_times(eslam_ctx* ctx, eslam_kernel_times* t)
     return ESLAM_OK;
 }
 
-extern "C" hipError_t eslam_launch_selftest_bm_radius(unsigned long long* bad, hipStream_t stream);
-
 extern "C" int eslam_gpu_selftest_bm_radius(int device, uint64_t* mismatches)
 {
     if (!mismatches) return ESLAM_ERR_INVALID_ARG;
     if (hipSetDevice(device) != hipSuccess) return ESLAM_ERR_HIP;
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, 8) != hipSuccess) return ESLAM_ERR_OUT_OF_MEMORY;
+    Dev<unsigned long long> d;
+    if (d.alloc(8) != hipSuccess) return ESLAM_ERR_OUT_OF_MEMORY;
     hipError_t e = hipMemset(d, 0, 8);
     if (e == hipSuccess) e = eslam_launch_selftest_bm_radius(d, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     unsigned long long h = 0;
     if (e == hipSuccess) e = hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     *mismatches = h;
     return e == hipSuccess ? ESLAM_OK : ESLAM_ERR_HIP;
 }
@@ -3418,48 +3144,36 @@ extern "C" int eslam_gpu_selftest_sort(int device, const uint32_t* keys, const u
     size_t bytes = 0;
     (void)eslam_radix_sort_pairs(nullptr, nullptr, nullptr, nullptr, n, nullptr, &bytes, nullptr);
     const uint64_t b = (n ? n : 1) * 4;
-    uint32_t* d = nullptr;
-    void* tmp = nullptr;
-    if (hipMalloc(&d, 4 * b) != hipSuccess || hipMalloc(&tmp, bytes) != hipSuccess) return ESLAM_ERR_OUT_OF_MEMORY;
+    Dev<uint32_t> d;
+    Dev<void> tmp;
+    if (d.alloc(4 * b) != hipSuccess || tmp.alloc(bytes) != hipSuccess) return ESLAM_ERR_OUT_OF_MEMORY;
     hipError_t e = hipMemcpy(d, keys, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + b / 4, vals, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = eslam_radix_sort_pairs(d, d + b / 4, d + 2 * b / 4, d + 3 * b / 4, n, tmp, &bytes, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(keys_out, d + 2 * b / 4, n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(vals_out, d + 3 * b / 4, n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    (void)hipFree(tmp);
     return e == hipSuccess ? ESLAM_OK : ESLAM_ERR_HIP;
 }
 
 extern "C" int eslam_gpu_selftest_math(int device, int fn, const double* x, const double* y, double* out, uint64_t n)
 {
     if (hipSetDevice(device) != hipSuccess) return ESLAM_ERR_HIP;
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    Dev<double> dx, dy, dout;
     const uint64_t b = (n ? n : 1) * 8;
-    if (hipMalloc(&dx, b) != hipSuccess || hipMalloc(&dy, b) != hipSuccess || hipMalloc(&dout, b) != hipSuccess)
+    if (dx.alloc(b) != hipSuccess || dy.alloc(b) != hipSuccess || dout.alloc(b) != hipSuccess)
         return ESLAM_ERR_OUT_OF_MEMORY;
     hipError_t e = n ? hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice) : hipSuccess;
     if (e == hipSuccess) e = (y && n) ? hipMemcpy(dy, y, n * 8, hipMemcpyHostToDevice) : hipMemset(dy, 0, b);
     if (e == hipSuccess) e = eslam_launch_selftest_math(fn, dx, dy, dout, n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
     return e == hipSuccess ? ESLAM_OK : ESLAM_ERR_HIP;
 }
 
 // ---------------------------------------------------------------------------------------
 // snapshots: eslam_gpu_save / eslam_gpu_load (kernels in eslam_snapshot.hip)
 // ---------------------------------------------------------------------------------------
-extern "C" hipError_t eslam_launch_snap_census_tables(const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t n,
-                                                      hipStream_t stream);
-extern "C" hipError_t eslam_launch_snap_census_pages(const LocalMaps* lm, const SnapCensus* c, uint64_t T, hipStream_t stream);
-extern "C" hipError_t eslam_launch_snap_pack(int what, const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t T,
-                                             uint64_t k0, uint64_t cnt, uint32_t rw, void* out, hipStream_t stream);
-extern "C" hipError_t eslam_launch_snap_unpack(int what, const LocalMaps* lm, uint64_t k0, uint64_t cnt, uint32_t rw, const void* in,
-                                               hipStream_t stream);
-extern "C" hipError_t eslam_launch_snap_finish(const LocalMaps* lm, uint64_t T, uint64_t P, hipStream_t stream);
-
 namespace {
 
 const char kSnapMagic[8] = {'E', 'S', 'L', 'A', 'M', 'S', 'N', 'P'};
@@ -3543,16 +3257,16 @@ struct SnapPlan {
 int snap_staging(eslam_ctx* ctx, uint64_t bytes)
 {
     for (int k = 0; k < 2; ++k)
-        if (!ctx->snap_ev[k]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->snap_ev[k], hipEventDisableTiming));
+        HIPCHK(ctx, ctx->snap_ev[k].create(false));
     if (bytes <= ctx->snap_cap) return ESLAM_OK;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 2; ++k) {
-        (void)hipHostFree(ctx->snap_host[k]); ctx->snap_host[k] = nullptr;
-        (void)hipFree(ctx->snap_dev[k]); ctx->snap_dev[k] = nullptr;
+        ctx->snap_host[k].reset();
+        ctx->snap_dev[k].reset();
     }
     ctx->snap_cap = 0;
     for (int k = 0; k < 2; ++k) {
-        if (hipHostMalloc(&ctx->snap_host[k], bytes) != hipSuccess || hipMalloc(&ctx->snap_dev[k], bytes) != hipSuccess) {
+        if (ctx->snap_host[k].alloc(bytes) != hipSuccess || ctx->snap_dev[k].alloc(bytes) != hipSuccess) {
             (void)hipGetLastError();
             return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no memory for the staging buffers (lower chunk_bytes)");
         }
@@ -3573,7 +3287,7 @@ uint64_t snap_tiles(uint64_t items) { return (items + kCompactTileItems - 1) / k
 
 int snap_read_count(eslam_ctx* ctx, const uint32_t* dev, uint64_t* out)
 {
-    uint32_t* h = reinterpret_cast<uint32_t*>(ctx->scratch_host);
+    uint32_t* h = ctx->scratch_host.as<uint32_t>();
     HIPCHK(ctx, hipMemcpyAsync(h, dev, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     *out = *h;
@@ -3588,14 +3302,12 @@ int snap_census(eslam_ctx* ctx, SnapPlan& pl)
     const uint64_t o_first = 0, o_trank = o_first + up(lm.ntables * 4), o_tlist = o_trank + up(lm.ntables * 4),
                    o_fref = o_tlist + up(ctx->cap * 4), o_prank = o_fref + up(lm.npages * 8), o_plist = o_prank + up(lm.npages * 4),
                    total = o_plist + up(lm.npages * 4);
-    if (!ctx->snap_census) {                 // kept until the maps are dropped (free_local_maps)
-        if (hipMalloc(&ctx->snap_census, total) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->snap_census = nullptr;
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the census");
-        }
+    // kept until the maps are dropped (free_local_maps)
+    if (!ctx->lmb.census && ctx->lmb.census.alloc(total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the census");
     }
-    char* m = (char*)ctx->snap_census;
+    char* m = ctx->lmb.census.as<char>();
     SnapCensus& c = pl.cen;
     c.first = (uint32_t*)(m + o_first);
     c.trank = (uint32_t*)(m + o_trank);
@@ -3604,18 +3316,18 @@ int snap_census(eslam_ctx* ctx, SnapPlan& pl)
     c.prank = (uint32_t*)(m + o_prank);
     c.plist = (uint32_t*)(m + o_plist);
     const uint64_t n = ctx->n, ttiles = snap_tiles(n);
-    int rc = grow(ctx, (void**)&ctx->snap_counts, &ctx->snap_counts_cap, (ttiles + 1) * 4, false);
+    int rc = grow(ctx, ctx->lmb.counts, (ttiles + 1) * 4);
     if (rc) return rc;
-    c.counts = ctx->snap_counts;
+    c.counts = ctx->lmb.counts;
     HIPCHK(ctx, eslam_launch_snap_census_tables(&lm, &c, pl.sid, n, ctx->stream));
     uint64_t T = 0, P = 0;
     rc = snap_read_count(ctx, c.counts + ttiles, &T);
     if (rc) return rc;
     const uint64_t ptiles = snap_tiles(T * (lm.wx * lm.wy + lm.V));
     if (ptiles >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: the page census has 2^32 tiles or more");
-    rc = grow(ctx, (void**)&ctx->snap_counts, &ctx->snap_counts_cap, (ptiles + 1) * 4, false);
+    rc = grow(ctx, ctx->lmb.counts, (ptiles + 1) * 4);
     if (rc) return rc;
-    c.counts = ctx->snap_counts;
+    c.counts = ctx->lmb.counts;
     HIPCHK(ctx, eslam_launch_snap_census_pages(&lm, &c, T, ctx->stream));
     rc = snap_read_count(ctx, c.counts + ptiles, &P);
     if (rc) return rc;
@@ -3653,7 +3365,7 @@ int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
     h.offset_y = ctx->map.offset_y;
     memcpy(h.g2l, ctx->map.g2l, sizeof(h.g2l));
     h.n_patches = ctx->map_np;
-    h.has_height = ctx->d_height ? 1u : 0u;
+    h.has_height = ctx->grid.height ? 1u : 0u;
     h.sections = (1u << kSecGrid) | (1u << kSecParticles) | (1u << kSecScalars);
     if (h.particle_maps) {
         h.hx = dm_lm_half(ctx->cfg.max_sensor_range, ctx->map_scale[0]);
@@ -3696,9 +3408,9 @@ int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
     std::vector<Piece>& p = pl.pieces;
     const uint64_t ncell = (uint64_t)h.width * h.height, n = h.n;
     p.push_back(Piece{PK_HOST, &pl.h, sizeof(SnapHeader), 1});
-    p.push_back(Piece{PK_DEV, ctx->d_cells, ncell + 1, 4});
-    p.push_back(Piece{PK_DEV, ctx->d_patch, h.n_patches, 8});
-    if (h.has_height) p.push_back(Piece{PK_DEV, ctx->d_height, h.n_patches, 4});
+    p.push_back(Piece{PK_DEV, ctx->grid.cells, ncell + 1, 4});
+    p.push_back(Piece{PK_DEV, ctx->grid.patch, h.n_patches, 8});
+    if (h.has_height) p.push_back(Piece{PK_DEV, ctx->grid.height, h.n_patches, 4});
     if (ctx->has_hash) {
         for (int f = 0; f < 4; ++f) p.push_back(Piece{PK_DEV, hash_field(ctx, f), h.hash_n, 8});
         p.push_back(Piece{PK_HOST, ctx->hash_bucket.data(), h.hash_n * 4, 1});
@@ -3797,7 +3509,7 @@ int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes
     auto issue = [&](const SnapChunk& c, uint32_t slot) -> int {
         const Piece& q = P[c.piece];
         const uint64_t bytes = c.cnt * q.unit, off = c.k0 * q.unit;
-        char* host = (char*)ctx->snap_host[slot];
+        char* host = ctx->snap_host[slot].as<char>();
         if (q.kind == PK_HOST) {
             memcpy(host, (const char*)q.src + off, bytes);
         } else if (q.kind == PK_DEV) {
@@ -3824,7 +3536,7 @@ int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes
         uint64_t bytes = cur.cnt * q.unit;
         if (cur.last) {                      // zeros up to the next 16-byte boundary
             const uint64_t all = q.count * q.unit, padded = pad16(all);
-            memset((char*)ctx->snap_host[slot] + bytes, 0, padded - all);
+            memset(ctx->snap_host[slot].as<char>() + bytes, 0, padded - all);
             bytes += padded - all;
         }
         if (w(user, ctx->snap_host[slot], bytes) != 0) {
@@ -3871,7 +3583,7 @@ int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit
         const uint32_t slot = rd.slot;
         rd.slot ^= 1u;
         HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));     // the slot's previous chunk has left it
-        char* host = (char*)ctx->snap_host[slot];
+        char* host = ctx->snap_host[slot].as<char>();
         if (rd.r(rd.user, host, bytes + (last ? tail : 0)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
         ++rd.chunks;
         if (check) {
@@ -4004,10 +3716,10 @@ int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known
     if (hash) {
         const uint64_t hn = h.hash_n, cap = hn ? hn : 1;
         const uint32_t nb = h.hash_bins * h.hash_bins;
-        (void)hipFree(ctx->d_hash); ctx->d_hash = nullptr;
-        (void)hipFree(ctx->d_hash_blist); ctx->d_hash_blist = nullptr;
+        ctx->d_hash.reset();
+        ctx->d_hash_blist.reset();
         ctx->hash_n = 0;
-        if (hipMalloc(&ctx->d_hash, sizeof(double) * 4 * cap) != hipSuccess || hipMalloc(&ctx->d_hash_blist, sizeof(uint32_t) * cap) != hipSuccess) {
+        if (ctx->d_hash.alloc(sizeof(double) * 4 * cap) != hipSuccess || ctx->d_hash_blist.alloc(sizeof(uint32_t) * cap) != hipSuccess) {
             (void)hipGetLastError();
             return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash pose buffers");
         }

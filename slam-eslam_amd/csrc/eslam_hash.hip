@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "eslam_internal.h"
+#include "eslam_launch.h"
 
 namespace eslam_dev {
 
@@ -212,8 +213,6 @@ __global__ void __launch_bounds__(kBlock) k_hash_replace_global(DevState s0, Dev
 using namespace eslam_dev;
 
 static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-extern "C" hipError_t eslam_launch_scan_excl(uint32_t* a, uint64_t m, hipStream_t stream);   // eslam_kernels.hip
 
 extern "C" hipError_t eslam_launch_hash_sweep(const dm_hash_grid* g, const double* pts, const double* orient, uint32_t steps,
                                               int32_t* out, hipStream_t stream)

@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include "eslam_internal.h"
+#include "eslam_launch.h"
 
 namespace eslam_dev {
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "eslam_internal.h"
+#include "eslam_launch.h"
 
 namespace eslam_dev {
 
@@ -208,11 +209,6 @@ __global__ void __launch_bounds__(kBlock) k_sm_rebuild(SmGrid o, SmGrid nw, cons
 using namespace eslam_dev;
 
 static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-extern "C" hipError_t eslam_launch_scan_excl(uint32_t* a, uint64_t m, hipStream_t stream);   // eslam_kernels.hip
-extern "C" hipError_t eslam_radix_sort_pairs_passes(uint32_t* keys, uint32_t* vals, uint32_t* keys_out, uint32_t* order,
-                                                    uint64_t n, void* tmp, size_t* tmp_bytes, int passes,
-                                                    hipStream_t stream);                      // eslam_hash.hip
 
 // 8-bit passes that order the keys 0 .. ncell
 static int sm_passes(uint32_t ncell)

@@ -12,10 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "eslam_internal.h"
+#include "eslam_launch.h"
 
 using namespace eslam_dev;
-
-extern "C" hipError_t eslam_launch_scan_excl(uint32_t* a, uint64_t m, hipStream_t stream);
 
 namespace {
 
