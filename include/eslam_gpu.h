@@ -504,6 +504,45 @@ int eslam_gpu_debug_set_spin_limit(eslam_ctx* ctx, uint32_t polls);
 int eslam_gpu_get_weights_sum(eslam_ctx* ctx, double* sum);          /* getWeightsSum :34-39     */
 int eslam_gpu_normalize_weights(eslam_ctx* ctx, double* effective);  /* normalizeWeights :46-70 */
 int eslam_gpu_resample(eslam_ctx* ctx);        /* resample() -> resample_stratified(N) :72-108 */
+/* resample_stratified(samples) :85-108 and resample_multinomial(samples) :120-148: resample the
+ * weights as they stand (as eslam_gpu_resample: a deferred exchange is settled and a pending
+ * gather run first, the contact records are invalidated) to `samples` particles.  Both use the
+ * fixed-point cumulative sum C_i and shift of eslam_gpu_resample (61 - (dm_weight_exp(S) + 1),
+ * S the exact weight sum) and move the minstd state on by exactly `samples` draws.
+ *   stratified   draw k < samples is T_k = fx((k + U_k) / samples); particle i fills the outputs
+ *                [#{T <= C_(i-1)}, #{T <= C_i}), the last particle every draw up to `samples`
+ *                (the Q5 clamp, counted in overruns); weights are carried (Q4).  samples == n is
+ *                eslam_gpu_resample, bit for bit.
+ *   multinomial  draw n is T_n = fx(U_n), U_n the boost uniform of the (n+1)-th minstd draw; its
+ *                ancestor is the first i with T_n <= C_i (the reference's r_n <= sum); a draw
+ *                with T_n > C_(N-1) is dropped and counted (unnormalised weights summing below 1);
+ *                the outputs keep draw order, n_after = samples - dropped, and every output's
+ *                weight is 1.0 / (double)n_before (:140, the old count).
+ * The outputs carry every field of their ancestor (mprob, floating, the contact count, also
+ * under ESLAM_FLAG_NO_AUX_GATHER when the count changes: a set of another size has no old
+ * values to keep); with
+ * ESLAM_FLAG_RECORD_ANCESTORS eslam_gpu_get_ancestors returns n_after ancestors in the old
+ * indexing.  Every later call works at n_after particles, the sum contract's chunk rows
+ * included, as in a filter initialised at that count.  Shrinking keeps the allocation; growing
+ * beyond it allocates the larger particle set before anything changes
+ * (ESLAM_ERR_OUT_OF_MEMORY: the filter is as it was).  Synchronous.
+ * Limits: samples == 0 or samples >= 2^32 - 1 is ESLAM_ERR_INVALID_ARG with nothing changed
+ * (deviation: the reference would empty the filter).  A multinomial call that drops every draw
+ * leaves no particles: later calls return ESLAM_ERR_NOT_INITIALISED as before init.  With
+ * ESLAM_FLAG_PARTICLE_MAPS, samples may not exceed the count the filter was initialised with
+ * (the tables and pages are sized then): ESLAM_ERR_UNSUPPORTED, nothing changed, the RNG not
+ * advanced; within it a copy names its ancestor's table and shares its pages until a map update
+ * writes them.  A sharded filter accepts only a stratified call with samples == n_global (the
+ * sharded eslam_gpu_resample); anything else is ESLAM_ERR_UNSUPPORTED on every rank, before any
+ * collective.  info may be NULL.                                                            */
+typedef struct {
+    uint64_t n_before;   /* particles before the call                                  */
+    uint64_t n_after;    /* particles after it                                         */
+    uint64_t overruns;   /* stratified: draws beyond the cumulative sum (clamped, Q5)  */
+    uint64_t dropped;    /* multinomial: draws with no particle (r_n > the weight sum) */
+} eslam_resample_info;
+int eslam_gpu_resample_stratified(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
+int eslam_gpu_resample_multinomial(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
 int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index);  /* :160-173 (Q16)  */
 /* PoseEstimator::getCentroid src/PoseEstimator.cpp:354-383 (normalises in place, Q15):
  * position[3] + quaternion (w,x,y,z)                                                        */

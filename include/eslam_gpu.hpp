@@ -901,6 +901,23 @@ public:
         invalidate();
         check(ctx_, eslam_gpu_resample(ctx_));
     }
+    // resample_stratified(samples) / resample_multinomial(samples)  src/ParticleFilter.hpp:85-148:
+    // to any count; getParticles() has the new size afterwards (eslam_gpu_resample_stratified /
+    // _multinomial: the limits with per-particle maps and sharded filters, and samples == 0, are
+    // errors there and exceptions here)
+    void resample_stratified(size_t samples)
+    {
+        flush();
+        invalidate();
+        check(ctx_, eslam_gpu_resample_stratified(ctx_, samples, &last_resample_));
+    }
+    void resample_multinomial(size_t samples)
+    {
+        flush();
+        invalidate();
+        check(ctx_, eslam_gpu_resample_multinomial(ctx_, samples, &last_resample_));
+    }
+    const eslam_resample_info& lastResample() const { return last_resample_; }
     size_t getBestParticleIndex() const
     {
         flush();
@@ -1130,6 +1147,7 @@ private:
     Configuration config_;
     eslam_ctx* ctx_ = nullptr;
     eslam_update_info last_ = {};
+    eslam_resample_info last_resample_ = {};
     mutable std::vector<Particle> view_;           // getParticles()
     mutable std::vector<Hot> shadow_;              // view_ as the device holds it
     mutable bool view_valid_ = false;

@@ -311,7 +311,7 @@ struct eslam_ctx {
     Dev<uint32_t> payoff;                    // header prefix (send side, then receive side)
     Dev<uint32_t> rhead;                     // received records: the record carrying each one's map
     uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
-    Dev<double> cent;                        // sharded getCentroid's chunk records (set_comm)
+    Dev<double> cent;                        // getCentroid's chunk records (sharded: sized by set_comm)
     Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)
     bool cow_pending = false;
     // a sharded update's exchange left for the next call: the segments kernel's
@@ -342,6 +342,9 @@ struct eslam_ctx {
     Dev<void> sort_tmp;
     size_t sort_tmp_bytes = 0;
     Dev<uint32_t> d_draws;
+    // eslam_gpu_resample_stratified / _multinomial to another count: the cumulative sum, its
+    // coarse level, the draws' ancestors and the compaction's counts (resample_to), kept between calls
+    Dev<char> rs_mem;
     // diagnostics
     std::string err;
     bool timing = false;
@@ -598,6 +601,7 @@ static void free_particles(eslam_ctx* ctx)
     free_debug(ctx);
     free_local_maps(ctx);
     ctx->pt = ParticleBufs{};
+    ctx->rs_mem.reset();                     // a resample to a count's scratch goes with the set it was sized for
     ctx->st[0].sid = ctx->st[1].sid = nullptr;
     ctx->n = ctx->cap = 0;
     ctx->has_anc = false;
@@ -654,7 +658,69 @@ extern "C" int eslam_gpu_set_stream(eslam_ctx* ctx, void* s)
     return ESLAM_OK;
 }
 
-// 256-byte aligned SoA carve-out: 7 fp64 arrays + 1 byte array, two copies
+// The particle buffers of one capacity and what points into them: the two state buffers'
+// arrays, the fused finalize's epoch word and the tile words' stride
+struct ParticleSet {
+    ParticleBufs pt;
+    DevState st[2] = {};
+    uint64_t* fin_word = nullptr;
+    uint32_t pub_stride = 0;
+};
+
+// 256-byte aligned SoA carve-out: 7 fp64 arrays + 1 byte array, two copies; and everything
+// else sized by the capacity.  Fills `ps` only: a failure leaves the context as it was.
+static hipError_t alloc_particle_set(const eslam_ctx* ctx, uint64_t cap, ParticleSet& ps)
+{
+#define ESLAM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
+    const uint64_t per = 7 * al(cap * 8) + al(cap);
+    ESLAM_TRY(ps.pt.state_mem.alloc(2 * per));
+    for (int k = 0; k < 2; ++k) {
+        char* p = ps.pt.state_mem.as<char>() + k * per;
+        DevState& s = ps.st[k];
+        double** f[7] = {&s.x, &s.y, &s.th, &s.z, &s.zs, &s.w, &s.mprob};
+        for (int j = 0; j < 7; ++j) { *f[j] = (double*)p; p += al(cap * 8); }
+        s.flags = (uint8_t*)p;
+    }
+    const uint64_t ntiles = (cap + kBlock - 1) / kBlock;                // the smallest scan tile (scan_items)
+    ESLAM_TRY(ps.pt.marks.alloc(cap * 4));
+    ESLAM_TRY(ps.pt.tile_first.alloc(((cap + kRow - 1) / kRow) * 4));
+    // the tile words, then (in a line of its own) the fused finalize's epoch word
+    // K3's kPubReplicas copies of the tile words (4 KB-aligned regions, 256 B apart beyond
+    // that, so the copies fall on different memory channels), then the epoch word's line
+    ps.pub_stride = (uint32_t)(((ntiles + 511) & ~511ull) + 32);
+    const uint64_t fin_at = (uint64_t)kPubReplicas * ps.pub_stride;
+    ESLAM_TRY(ps.pt.tile_sum.alloc((fin_at + 16) * 8));
+    ESLAM_TRY(hipMemset(ps.pt.tile_sum, 0, (fin_at + 16) * 8));          // tag / epoch 0: never published
+    ps.fin_word = ps.pt.tile_sum + fin_at;
+    ESLAM_TRY(hipMemset(ps.pt.marks, 0, cap * 4));
+    if (keep_ancestors(ctx)) ESLAM_TRY(ps.pt.anc.alloc(cap * 4));
+    if (particle_maps(ctx)) {
+        // the table names of both state buffers; the tables and pages come with the map
+        // (local_maps_reset: their window size follows the map's cell size)
+        ESLAM_TRY(ps.pt.sid_mem.alloc(2 * cap * 4));
+        ps.st[0].sid = ps.pt.sid_mem;
+        ps.st[1].sid = ps.pt.sid_mem + cap;
+        ESLAM_TRY(ps.pt.cow.alloc(cow_words(cap) * 4));
+        ESLAM_TRY(ps.pt.merge_cnt.alloc(kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
+        ESLAM_TRY(hipMemset(ps.pt.merge_cnt, 0, kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
+    }
+    if (ctx->sharded) ESLAM_TRY(ps.pt.range.alloc(cap * sizeof(uint2)));
+#undef ESLAM_TRY
+    return hipSuccess;
+}
+
+// the context takes a particle set over (whatever it held is freed)
+static void adopt_particle_set(eslam_ctx* ctx, ParticleSet& ps, uint64_t cap)
+{
+    ctx->pt = std::move(ps.pt);
+    ctx->st[0] = ps.st[0];
+    ctx->st[1] = ps.st[1];
+    ctx->fin_word = ps.fin_word;
+    ctx->pub_stride = ps.pub_stride;
+    ctx->cap = cap;
+}
+
 static int alloc_particles(eslam_ctx* ctx, uint64_t n)
 {
     if (n >= (1ull << 32) - 1) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle count must be < 2^32 - 1");
@@ -662,44 +728,11 @@ static int alloc_particles(eslam_ctx* ctx, uint64_t n)
         return fail(ctx, ESLAM_ERR_INVALID_ARG, "sharded context: particle count must equal this rank's shard size");
     free_particles(ctx);
     const uint64_t cap = n ? n : 1;
-    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-    const uint64_t per = 7 * al(cap * 8) + al(cap);
-    HIPCHK(ctx, ctx->pt.state_mem.alloc(2 * per));
-    for (int k = 0; k < 2; ++k) {
-        char* p = ctx->pt.state_mem.as<char>() + k * per;
-        DevState& s = ctx->st[k];
-        double** f[7] = {&s.x, &s.y, &s.th, &s.z, &s.zs, &s.w, &s.mprob};
-        for (int j = 0; j < 7; ++j) { *f[j] = (double*)p; p += al(cap * 8); }
-        s.flags = (uint8_t*)p;
-    }
-    const uint64_t ntiles = (cap + kBlock - 1) / kBlock;                // the smallest scan tile (scan_items)
-    HIPCHK(ctx, ctx->pt.marks.alloc(cap * 4));
-    HIPCHK(ctx, ctx->pt.tile_first.alloc(((cap + kRow - 1) / kRow) * 4));
-    // the tile words, then (in a line of its own) the fused finalize's epoch word
-    // K3's kPubReplicas copies of the tile words (4 KB-aligned regions, 256 B apart beyond
-    // that, so the copies fall on different memory channels), then the epoch word's line
-    ctx->pub_stride = (uint32_t)(((ntiles + 511) & ~511ull) + 32);
-    const uint64_t fin_at = (uint64_t)kPubReplicas * ctx->pub_stride;
-    HIPCHK(ctx, ctx->pt.tile_sum.alloc((fin_at + 16) * 8));
-    HIPCHK(ctx, hipMemset(ctx->pt.tile_sum, 0, (fin_at + 16) * 8));          // tag / epoch 0: never published
-    ctx->fin_word = ctx->pt.tile_sum + fin_at;
-    HIPCHK(ctx, hipMemset(ctx->pt.marks, 0, cap * 4));
-    if (keep_ancestors(ctx)) HIPCHK(ctx, ctx->pt.anc.alloc(cap * 4));
-    if (particle_maps(ctx)) {
-        // the table names of both state buffers; the tables and pages come with the map
-        // (local_maps_reset: their window size follows the map's cell size)
-        HIPCHK(ctx, ctx->pt.sid_mem.alloc(2 * cap * 4));
-        ctx->st[0].sid = ctx->pt.sid_mem;
-        ctx->st[1].sid = ctx->pt.sid_mem + cap;
-        HIPCHK(ctx, ctx->pt.cow.alloc(cow_words(cap) * 4));
-        HIPCHK(ctx, ctx->pt.merge_cnt.alloc(kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
-        HIPCHK(ctx, hipMemset(ctx->pt.merge_cnt, 0, kMergeCounters * kMergeCounterSlots * sizeof(uint64_t)));
-    }
+    ParticleSet ps;
+    HIPCHK(ctx, alloc_particle_set(ctx, cap, ps));
+    adopt_particle_set(ctx, ps, cap);
     ctx->n = n;
-    ctx->cap = cap;
-    if (ctx->sharded) {
-        HIPCHK(ctx, ctx->pt.range.alloc(cap * sizeof(uint2)));
-    } else {
+    if (!ctx->sharded) {
         ctx->n_global = n;
         ctx->gbase = 0;
     }
@@ -2964,6 +2997,124 @@ extern "C" int eslam_gpu_resample(eslam_ctx* ctx)
     return standalone(ctx, FIN_RESAMPLE);
 }
 
+// ParticleFilter<T>::resample_stratified(samples) / resample_multinomial(samples)
+// (src/ParticleFilter.hpp:85-108, 120-148): resample the weights as they stand to `samples`
+// particles (DESIGN.md 2 "Resample to a count").  A stratified call at the current count is
+// eslam_gpu_resample.  Otherwise (eslam_resample.hip): the exact weight sum fixes the shift, the
+// cumulative sum is written out, every draw searches its ancestor, and the gather runs at once
+// into the other state buffer, or, beyond the capacity, into a new particle set allocated before
+// anything changes.
+static int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (samples == 0 || samples >= (1ull << 32) - 1)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample: samples must be in [1, 2^32 - 2]");
+    // the shard boundaries are fixed by set_comm; refused before any collective (settle is one)
+    if (ctx->sharded && (multi || samples != ctx->n_global))
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "resample: a sharded filter resamples to its own count only (stratified)");
+    if (const int rc_ = settle(ctx)) return rc_;
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (check_poisoned(ctx)) return ESLAM_ERR_HIP;
+    const uint64_t n = ctx->n;
+    int rc;
+    // the current count (a sharded filter's global one: its capacity is the shard's): the resample itself
+    if (!multi && samples == ctx->n_global) {
+        ctx->dbg_valid = false;                  // the records no longer follow the particles
+        rc = standalone(ctx, FIN_RESAMPLE);
+        if (rc || !info) return rc;
+        rc = read_ctl(ctx);
+        if (rc) return rc;
+        info->n_before = info->n_after = ctx->n_global;
+        info->overruns = ctx->ctl_host->overruns;
+        return ESLAM_OK;
+    }
+    if (particle_maps(ctx) && samples > ctx->cap)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
+                    "resample: per-particle maps are sized at init; samples may not exceed that capacity");
+    rc = materialize(ctx);
+    if (rc) return rc;
+    // everything the call allocates, first: a failure returns with the filter as it was
+    const uint64_t tn = eslam_resample_tiles(n), ts = eslam_resample_tiles(samples);
+    auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+    const uint64_t o_coarse = up(n * 8), o_cnt = o_coarse + up(tn * 8), o_anc = o_cnt + 256, o_out = o_anc + up(samples * 4),
+                   o_kept = o_out + (multi ? up(samples * 4) : 0), bytes = o_kept + up((ts + 1) * 4);
+    hipError_t he = hipSuccess;
+    rc = ctx->rs_mem.grow_keep(bytes, 1, ctx->stream, &he);
+    if (rc == ESLAM_ERR_HIP) return fail(ctx, rc, hipGetErrorString(he));
+    if (rc) return fail(ctx, rc, "resample: no device memory for the cumulative sum and the draws");
+    const bool growing = samples > ctx->cap;
+    ParticleSet ps;
+    if (growing) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (alloc_particle_set(ctx, samples, ps) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "resample: no device memory for the larger particle set");
+        }
+        HIPCHK(ctx, hipDeviceSynchronize());     // the new buffers' resets, before the stream uses them
+    }
+    char* m = ctx->rs_mem;
+    uint64_t* C = reinterpret_cast<uint64_t*>(m);
+    uint64_t* coarse = reinterpret_cast<uint64_t*>(m + o_coarse);
+    uint64_t* counter = reinterpret_cast<uint64_t*>(m + o_cnt);
+    uint32_t* anc = reinterpret_cast<uint32_t*>(m + o_anc);
+    uint32_t* anc_kept = multi ? reinterpret_cast<uint32_t*>(m + o_out) : anc;
+    uint32_t* kept = reinterpret_cast<uint32_t*>(m + o_kept);
+    ctx->dbg_valid = false;                      // the records no longer follow the particles
+    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
+    HIPCHK(ctx, eslam_launch_weight_stats(ctx->st[0], ctx->st[1], n, J, ctx->ctl, ctx->shards, ctx->stream));
+    const FinParams fp = fin_params(ctx, FIN_SUM);
+    HIPCHK(ctx, eslam_launch_finalize(ctx->shards, kNShard, ctx->ctl, &fp, ctx->stream));
+    HIPCHK(ctx, eslam_launch_rs_cumsum(ctx->st[0], ctx->st[1], n, ctx->ctl, dm_minstd_pow(samples), coarse, C, counter,
+                                       ctx->stream));
+    HIPCHK(ctx, eslam_launch_rs_draw(multi ? 1 : 0, n, samples, ctx->ctl, ctx->jump, coarse, C, anc, kept, counter, ctx->stream));
+    if (multi) {
+        HIPCHK(ctx, eslam_launch_scan_excl(kept, ts + 1, ctx->stream));
+        HIPCHK(ctx, eslam_launch_rs_compact(samples, anc, kept, anc_kept, ctx->stream));
+    }
+    rc = read_ctl(ctx);                          // waits for the draws
+    if (rc) return rc;
+    uint64_t beyond = 0;
+    HIPCHK(ctx, hipMemcpy(&beyond, counter, 8, hipMemcpyDeviceToHost));
+    const uint64_t n_after = multi ? samples - beyond : samples;
+    Ctl* c = ctx->ctl_host;
+    const uint32_t base = c->base ^ c->flip;
+    const DevState out = growing ? ps.st[0] : ctx->st[base ^ 1u];
+    const bool record = keep_ancestors(ctx) && n_after;
+    uint32_t* anc_out = record ? (growing ? ps.pt.anc.get() : ctx->pt.anc.get()) : nullptr;
+    HIPCHK(ctx, eslam_launch_rs_gather(ctx->st[0], ctx->st[1], ctx->ctl, out, n_after, anc_kept, multi ? 1 : 0, 1.0 / (double)n,
+                                       anc_out, ctx->stream));
+    // K3's tile words carry the tag of the launch that wrote them; a launch over another count
+    // writes other words, so none may keep a tag from before the count changed
+    if (!growing)
+        HIPCHK(ctx, hipMemsetAsync(ctx->pt.tile_sum, 0, ((uint64_t)kPubReplicas * ctx->pub_stride + 16) * 8, ctx->stream));
+    c->base = growing ? 0u : base ^ 1u;
+    c->flip = 0;
+    c->gather = 0;
+    rc = write_ctl(ctx);                         // waits for the gather: the old set may go
+    if (rc) return rc;
+    if (growing) adopt_particle_set(ctx, ps, samples);
+    ctx->n = ctx->n_global = n_after;
+    ctx->has_anc = record;
+    if (info) {
+        info->n_before = n;
+        info->n_after = n_after;
+        if (multi) info->dropped = beyond;
+        else info->overruns = beyond;
+    }
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_resample_stratified(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)
+{
+    return resample_to(ctx, samples, false, info);
+}
+
+extern "C" int eslam_gpu_resample_multinomial(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)
+{
+    return resample_to(ctx, samples, true, info);
+}
+
 extern "C" int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index)
 {
     if (!ctx || !index) return ESLAM_ERR_INVALID_ARG;
@@ -3005,7 +3156,11 @@ extern "C" int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double
     if (rc) return rc;
     const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
     if (!ctx->sharded) {
-        HIPCHK(ctx, eslam_launch_centroid(ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, ctx->scratch, ctx->stream));
+        // the chunk records and the tree's second level, in the context's own buffer
+        const uint64_t csz = 64ull * J, chunks = (ctx->n + csz - 1) / csz;
+        rc = grow(ctx, ctx->cent, 2 * (chunks ? chunks : 1) * 5 * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(ctx, eslam_launch_centroid(ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, ctx->cent, ctx->scratch, ctx->stream));
     } else {
         // the shards are chunk-aligned: every rank's chunk records, all-gathered (padded to
         // the largest shard) and laid out in global chunk order, feed the same fixed tree

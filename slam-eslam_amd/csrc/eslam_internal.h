@@ -36,6 +36,17 @@ constexpr int kWindowLds = ESLAM_WINDOW_LDS;
 #define ESLAM_K1_ATTR
 #endif
 
+#if defined(__HIPCC__)
+// A^e for e < 2^32 from the context's three jump tables: A^(i), A^(i*2^11), A^(i*2^22)
+__device__ __forceinline__ uint32_t jump_pow(const uint32_t* __restrict__ jt, uint64_t e)
+{
+    uint32_t a = jt[e & 2047u];
+    uint32_t b = jt[2048u + ((e >> 11) & 2047u)];
+    uint32_t c = jt[4096u + ((e >> 22) & 1023u)];
+    return dm_mulmod31(dm_mulmod31(a, b), c);
+}
+#endif
+
 // one statistics shard: exact sums as 4 limbs of 32-bit columns (uint64 each)
 struct alignas(128) Shard {
     uint64_t A[DM_NBUCKETS][4];          // sum over chunks of  w_A * mprob        (per bucket)

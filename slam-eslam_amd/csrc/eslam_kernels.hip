@@ -157,15 +157,6 @@ __device__ __forceinline__ void atomic_store_agent(uint64_t* p, uint64_t v)
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ uint32_t jump_pow(const uint32_t* __restrict__ jt, uint64_t e)
-{
-    // A^e for e < 2^32 from three tables: A^(i), A^(i*2^11), A^(i*2^22)
-    uint32_t a = jt[e & 2047u];
-    uint32_t b = jt[2048u + ((e >> 11) & 2047u)];
-    uint32_t c = jt[4096u + ((e >> 22) & 1023u)];
-    return dm_mulmod31(dm_mulmod31(a, b), c);
-}
-
 // ---------------------------------------------------------------------------------------
 // Diagnostic builds only (-DESLAM_STAMPS, tools/stamps.py): per-block s_memrealtime stamps
 // (100 MHz, one clock for the whole device) at the phase boundaries of K1 and K3, written by
@@ -4956,21 +4947,21 @@ extern "C" hipError_t eslam_launch_centroid_tree(double* a, double* b, uint64_t 
     return centroid_tree(a, b, m, out, stream);
 }
 
-extern "C" hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* out,
+// tmp: the caller's scratch of 2 x max(chunks, 1) x 5 doubles (the chunk records and the tree's
+// second level).  It belongs to the context: stream-ordered pool memory here gave the second of
+// two contexts of one process, each on its own stream, another centroid than the first for the
+// same particles (the block one stream had freed was handed to the other).
+extern "C" hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* tmp, double* out,
                                             hipStream_t stream)
 {
     const uint64_t csz = 64ull * J;
     const uint64_t chunks = (n + csz - 1) / csz;
     const uint64_t cap = chunks ? chunks : 1;
-    double* tmp = nullptr;
-    hipError_t e = hipMallocAsync((void**)&tmp, 2 * cap * 5 * sizeof(double), stream);
-    if (e != hipSuccess) return e;
     double* a = tmp;
     double* b = tmp + cap * 5;
-    e = hipMemsetAsync(a, 0, 5 * sizeof(double), stream);
+    hipError_t e = hipMemsetAsync(a, 0, 5 * sizeof(double), stream);
     if (e == hipSuccess) e = eslam_launch_centroid_chunks(s0, s1, n, J, ctl, a, stream);
     if (e == hipSuccess) e = centroid_tree(a, b, chunks, out, stream);
-    (void)hipFreeAsync(tmp, stream);
     return e;
 }
 

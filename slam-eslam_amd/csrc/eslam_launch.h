@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip), declared once.  All six .hip files include it, the defining one too: the
+// (eslam_ctx.hip), declared once.  All seven .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -69,7 +69,19 @@ hipError_t eslam_launch_best_index(DevState s0, DevState s1, uint64_t n, Ctl* ct
 hipError_t eslam_launch_centroid_chunks(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* chunk_out,
                                         hipStream_t stream);
 hipError_t eslam_launch_centroid_tree(double* a, double* b, uint64_t m, double* out, hipStream_t stream);
-hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* out, hipStream_t stream);
+hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* tmp, double* out,
+                                 hipStream_t stream);
+
+// ---- eslam_resample.hip (resample to a count: the cumulative sum, the draws' searches, the gather)
+uint64_t eslam_resample_tiles(uint64_t items);
+hipError_t eslam_launch_rs_cumsum(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint32_t jump_samples, uint64_t* coarse,
+                                  uint64_t* C, uint64_t* counter, hipStream_t stream);
+hipError_t eslam_launch_rs_draw(int multinomial, uint64_t n, uint64_t samples, const Ctl* ctl, const uint32_t* jt,
+                                const uint64_t* coarse, const uint64_t* C, uint32_t* anc, uint32_t* kept, uint64_t* counter,
+                                hipStream_t stream);
+hipError_t eslam_launch_rs_compact(uint64_t samples, const uint32_t* anc, const uint32_t* offs, uint32_t* out, hipStream_t stream);
+hipError_t eslam_launch_rs_gather(DevState s0, DevState s1, const Ctl* ctl, DevState out, uint64_t m, const uint32_t* anc,
+                                  int set_weight, double weight, uint32_t* anc_out, hipStream_t stream);
 
 // ---- eslam_hash.hip
 hipError_t eslam_launch_hash_sweep(const dm_hash_grid* g, const double* pts, const double* orient, uint32_t steps, int32_t* out,

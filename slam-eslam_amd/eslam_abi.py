@@ -273,6 +273,19 @@ class UpdateInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class ResampleInfo(C.Structure):
+    """eslam_resample_info (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("n_before", C.c_uint64),
+        ("n_after", C.c_uint64),
+        ("overruns", C.c_uint64),
+        ("dropped", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class RngState(C.Structure):
     _fields_ = [
         ("minstd_x", C.c_uint32),

@@ -94,6 +94,8 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_get_weights_sum.argtypes = [vp, dp]
     L.eslam_gpu_normalize_weights.argtypes = [vp, dp]
     L.eslam_gpu_resample.argtypes = [vp]
+    L.eslam_gpu_resample_stratified.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
+    L.eslam_gpu_resample_multinomial.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
     L.eslam_gpu_get_best_particle_index.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.eslam_gpu_get_centroid.argtypes = [vp, dp, dp]
     L.eslam_gpu_get_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
@@ -365,6 +367,20 @@ class GpuFilter:
 
     def resample(self):
         self._check(self.L.eslam_gpu_resample(self.h))
+
+    def resample_stratified(self, samples):
+        """eslam_gpu_resample_stratified: resample_stratified(samples), to any count (weights
+        carried); returns the ResampleInfo"""
+        info = A.ResampleInfo()
+        self._check(self.L.eslam_gpu_resample_stratified(self.h, samples, C.byref(info)))
+        return info
+
+    def resample_multinomial(self, samples):
+        """eslam_gpu_resample_multinomial: resample_multinomial(samples); draws beyond the weight
+        sum are dropped, every weight becomes 1 / n_before; returns the ResampleInfo"""
+        info = A.ResampleInfo()
+        self._check(self.L.eslam_gpu_resample_multinomial(self.h, samples, C.byref(info)))
+        return info
 
     def best_index(self):
         i = C.c_uint64()
