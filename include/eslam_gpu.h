@@ -589,8 +589,30 @@ int eslam_gpu_set_rng_state(eslam_ctx* ctx, const eslam_rng_state* st);
  * the context's own, as with eslam_gpu_upload_particles.
  * Not carried: the last update's eslam_update_info, the RECORD_CONTACTS records, the
  * ancestors and the kernel times; after a load they read as after upload_particles.
- * Sharded filters (nranks > 1): ESLAM_ERR_UNSUPPORTED from all five calls, deliberately, as
- * for eslam_gpu_shared_map_update (per-rank blobs and re-sharding are not built).            */
+ *
+ * Positional forms (eslam_gpu_save_at / eslam_gpu_load_at): the same version-1 blob as one
+ * logical file of info->bytes bytes, written and read by offset.  On a one-GPU filter save_at
+ * writes every byte of [0, bytes) exactly once, the bytes eslam_gpu_save_stream writes, and
+ * load_at is load_stream reading by offset (known_bytes: the file's size when known, else 0).
+ *
+ * Sharded filters (eslam_gpu_set_comm, any nranks): save_at, load_at, eslam_gpu_snapshot_size
+ * and eslam_gpu_load (every rank holds the whole blob) are collectives in SPMD order.  The
+ * ranks write one blob between them: rank 0 the header, grid, hash and scalars; every rank its
+ * shard of the particle arrays, and its tables and pages behind those of the ranks below it
+ * (shards are contiguous and tables and pages are rank-local, so rank-major order is the
+ * canonical order).  Without per-particle maps the blob is the one-GPU filter's, byte for byte.
+ * With them it differs only in how tables are shared across shard boundaries (a sharded filter
+ * keeps one copy per rank), never in what a particle's own map shows.  Any layout loads any
+ * blob whose n is its n_global (else ESLAM_ERR_INVALID_ARG, before any collective): each rank
+ * reads the shared parts, its shard of the particles, and the tables and pages its particles
+ * name; a table named from both sides of a shard boundary is loaded by both ranks.  The page
+ * pool check is per rank.  Both calls end with an all_gather of the ranks' return codes:
+ * ESLAM_OK on one rank means every rank wrote or loaded its part; a failing rank returns its
+ * own code, the others ESLAM_ERR_COMM, and after a failed load every rank holds no particles.
+ * info: bytes, particles, tables, pages and sections are the filter's on every rank, chunks
+ * counts this rank's callbacks.  eslam_gpu_save, eslam_gpu_save_stream and
+ * eslam_gpu_load_stream return ESLAM_ERR_UNSUPPORTED on a sharded filter, before any
+ * collective: a sequential stream cannot carry a part of a file.                            */
 #define ESLAM_SNAPSHOT_VERSION 1
 #define ESLAM_SNAPSHOT_GRID 0x1u
 #define ESLAM_SNAPSHOT_HASH 0x2u
@@ -605,6 +627,8 @@ typedef struct eslam_snapshot_info {
 } eslam_snapshot_info;
 typedef int (*eslam_write_fn)(void* user, const void* data, uint64_t bytes);  /* 0 = ok */
 typedef int (*eslam_read_fn)(void* user, void* data, uint64_t bytes);         /* 0 = ok */
+typedef int (*eslam_pwrite_fn)(void* user, uint64_t offset, const void* data, uint64_t bytes); /* 0 = ok */
+typedef int (*eslam_pread_fn)(void* user, uint64_t offset, void* data, uint64_t bytes);        /* 0 = ok */
 
 int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info);
 int eslam_gpu_save_stream(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info);
@@ -613,6 +637,10 @@ int eslam_gpu_load_stream(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t 
  * than the blob's own size, are ESLAM_ERR_INVALID_ARG                                      */
 int eslam_gpu_save(eslam_ctx* ctx, void* buf, uint64_t capacity, uint64_t chunk_bytes, eslam_snapshot_info* info);
 int eslam_gpu_load(eslam_ctx* ctx, const void* buf, uint64_t bytes, uint64_t chunk_bytes, eslam_snapshot_info* info);
+/* the blob by offset; the only forms a sharded filter saves through                          */
+extern int eslam_gpu_save_at(eslam_ctx* ctx, eslam_pwrite_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info);
+extern int eslam_gpu_load_at(eslam_ctx* ctx, eslam_pread_fn r, void* user, uint64_t known_bytes /* 0: unknown */,
+                             uint64_t chunk_bytes, eslam_snapshot_info* info);
 
 /* ---- SurfaceHash (useHash = true): pose hash of the map by terrain slope ----------------
  * SurfaceHash::create  src/SurfaceHash.hpp:155-231 on the map of eslam_gpu_set_map, with

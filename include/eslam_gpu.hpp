@@ -25,9 +25,13 @@
 #include <cstring>
 #include <istream>
 #include <ostream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include <fcntl.h>
+#include <unistd.h>
 
 #include "eslam_gpu.h"
 
@@ -1042,14 +1046,36 @@ public:
             throw std::runtime_error("setCommRccl: bad id or shard table");
         check(ctx_, eslam_gpu_set_comm_rccl(ctx_, nranks, rank, id.data(), nGlobal, shardGbase.data()));
         sharded_ = nranks > 0;
+        rank_ = rank;
     }
     // the same with caller-supplied collectives (eslam_gpu_set_comm); comm == nullptr: one GPU
     void setComm(const eslam_comm* comm, uint64_t nGlobal, const std::vector<uint64_t>& shardGbase)
     {
         check(ctx_, eslam_gpu_set_comm(ctx_, comm, nGlobal, comm ? shardGbase.data() : nullptr));
         sharded_ = comm != nullptr;
+        rank_ = comm ? comm->rank : 0;
     }
     bool sharded() const { return sharded_; }
+    int rank() const { return rank_; }
+
+    // the device's snapshot as one file written and read by offset (eslam_gpu_save_at /
+    // eslam_gpu_load_at): on a sharded estimator collectives, every rank writing and reading its
+    // part of the one blob; returns what the call reports (bytes: the blob's size)
+    eslam_snapshot_info saveAt(eslam_pwrite_fn pwrite, void* user, uint64_t chunkBytes = 0)
+    {
+        flush();
+        eslam_snapshot_info info;
+        check(ctx_, eslam_gpu_save_at(ctx_, pwrite, user, chunkBytes, &info));
+        return info;
+    }
+    eslam_snapshot_info loadAt(eslam_pread_fn pread, void* user, uint64_t knownBytes = 0, uint64_t chunkBytes = 0)
+    {
+        eslam_snapshot_info info;
+        const int rc = eslam_gpu_load_at(ctx_, pread, user, knownBytes, chunkBytes, &info);
+        invalidate();
+        check(ctx_, rc);
+        return info;
+    }
 
     // write the edits made to the getParticles() vector back to the device (a no-op without
     // any); every call above that uses the particles on the device runs it first.  On a
@@ -1153,6 +1179,7 @@ private:
     mutable bool view_valid_ = false;
     mutable uint32_t last_m_ = 0;
     bool sharded_ = false;
+    int rank_ = 0;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -1300,6 +1327,71 @@ public:
         resetMappingPoses();              // not in the state: the next scan and image map, as after init
     }
 
+    // The same state as one file: this object's own part in a fixed prefix of kStatePrefix bytes
+    // (zeros behind it), the device's snapshot behind the prefix, written and read by offset.
+    // Works on a sharded filter too (collectives: every rank calls them with the same path):
+    // rank 0 writes the prefix -- the odometry state is the same on every rank -- and every rank
+    // its part of the blob; loadState then loads into the estimator as it is sharded, each rank
+    // its slice, whatever layout wrote the file.  An unsharded filter may be only constructed.
+    void saveState(const std::string& path, uint64_t chunkBytes = 0)
+    {
+        PoseEstimator& f = estimator();
+        std::ostringstream head(std::ios::out | std::ios::binary);
+        detail::put(head, kStateMagic);
+        detail::put(head, (uint32_t)(sharedMap_ ? 1 : 0));
+        detail::put(head, (uint32_t)0);
+        detail::put(head, update_idx_);
+        odometry_.saveState(head);
+        detail::putState(head, last_state_);
+        detail::putQ(head, last_orientation_);
+        std::string prefix = head.str();
+        if (prefix.size() > kStatePrefix) throw std::runtime_error("saveState: the filter's own state exceeds its prefix");
+        prefix.resize(kStatePrefix, '\0');
+        StateFile file(path, O_WRONLY | O_CREAT);
+        if (!f.sharded() || f.rank() == 0)
+            if (pwriteFile(&file, 0, prefix.data(), kStatePrefix) != 0) throw std::runtime_error("saveState: cannot write " + path);
+        file.base = kStatePrefix;
+        const eslam_snapshot_info info = f.saveAt(&EmbodiedSlamFilter::pwriteFile, &file, chunkBytes);
+        // the file is the prefix and the blob (every rank may do this once all have written)
+        if (::ftruncate(file.fd, (off_t)(kStatePrefix + info.bytes)) != 0) throw std::runtime_error("saveState: cannot size " + path);
+    }
+    void loadState(const std::string& path, uint64_t chunkBytes = 0) { loadState(path, hashConfig_, chunkBytes); }
+    void loadState(const std::string& path, const SurfaceHashConfig& hashConfig, uint64_t chunkBytes = 0)
+    {
+        StateFile file(path, O_RDONLY);
+        std::string prefix(kStatePrefix, '\0');
+        if (preadFile(&file, 0, &prefix[0], kStatePrefix) != 0) throw std::runtime_error("loadState: cannot read " + path);
+        const off_t size = ::lseek(file.fd, 0, SEEK_END);
+        std::istringstream is(prefix, std::ios::in | std::ios::binary);
+        uint64_t magic = 0, idx = 0;
+        uint32_t shared = 0, pad = 0;
+        detail::get(is, magic);
+        if (magic != kStateMagic) throw std::runtime_error("loadState: not a filter state");
+        detail::get(is, shared);
+        detail::get(is, pad);
+        detail::get(is, idx);
+        FootContact odo = odometry_;
+        BodyContactState ls;
+        Quaterniond lo;
+        odo.loadState(is);
+        detail::getState(is, ls);
+        detail::getQ(is, lo);
+        if (!(filter_ && filter_->sharded())) {          // a sharded estimator keeps its communicator and layout
+            hashConfig_ = hashConfig;
+            filter_.reset(new PoseEstimator(odometry_, eslamConfig_, device_, hashConfig));
+            check(filter_->handle(), eslam_gpu_set_particle_maps(filter_->handle(), shared ? 0 : 1));
+        }
+        file.base = kStatePrefix;
+        filter_->loadAt(&EmbodiedSlamFilter::preadFile, &file, size > (off_t)kStatePrefix ? (uint64_t)size - kStatePrefix : 1, chunkBytes);
+        odometry_ = odo;
+        sharedMap_ = shared != 0;
+        update_idx_ = idx;
+        last_state_ = ls;
+        last_orientation_ = lo;
+        resetMappingPoses();
+    }
+    static constexpr uint64_t kStatePrefix = 4096;
+
     std::vector<PoseParticle>& getParticles() { return estimator().getParticles(); }
     size_t getBestParticleIndex() const { return estimator().getBestParticleIndex(); }
     Affine3d getCentroid() { return estimator().getCentroid().toTransform(); }
@@ -1353,6 +1445,44 @@ private:
         std::ostream& os = *static_cast<std::ostream*>(user);
         os.write(static_cast<const char*>(data), (std::streamsize)bytes);
         return os ? 0 : 1;
+    }
+    // a state file: its descriptor, and where the device's blob starts in it
+    struct StateFile {
+        int fd;
+        uint64_t base = 0;
+        StateFile(const std::string& path, int flags) : fd(::open(path.c_str(), flags, 0644))
+        {
+            if (fd < 0) throw std::runtime_error("cannot open " + path);
+        }
+        ~StateFile() { ::close(fd); }
+        StateFile(const StateFile&) = delete;
+        StateFile& operator=(const StateFile&) = delete;
+    };
+    static int pwriteFile(void* user, uint64_t offset, const void* data, uint64_t bytes)
+    {
+        const StateFile& f = *static_cast<const StateFile*>(user);
+        const char* p = static_cast<const char*>(data);
+        while (bytes) {
+            const ssize_t w = ::pwrite(f.fd, p, bytes, (off_t)(f.base + offset));
+            if (w <= 0) return 1;
+            p += w;
+            offset += (uint64_t)w;
+            bytes -= (uint64_t)w;
+        }
+        return 0;
+    }
+    static int preadFile(void* user, uint64_t offset, void* data, uint64_t bytes)
+    {
+        const StateFile& f = *static_cast<const StateFile*>(user);
+        char* p = static_cast<char*>(data);
+        while (bytes) {
+            const ssize_t r = ::pread(f.fd, p, bytes, (off_t)(f.base + offset));
+            if (r <= 0) return 1;
+            p += r;
+            offset += (uint64_t)r;
+            bytes -= (uint64_t)r;
+        }
+        return 0;
     }
     static int readStream(void* user, void* data, uint64_t bytes)
     {

@@ -3393,12 +3393,17 @@ void snap_layout(const SnapHeader& h, SnapSection sec[kSecCount], uint64_t* byte
 }
 
 enum PieceKind { PK_HOST = 0, PK_DEV, PK_SID, PK_TABLES, PK_OWNER, PK_PAGES };
-// one array of the blob: count units of unit bytes (then zeros up to 16 bytes)
+// one array of the blob, or the part of it this rank writes: count units of unit bytes at blob
+// offset off (then tail zeros, up to 16 bytes, where the part ends the array)
 struct Piece {
     int kind;
     const void* src;                         // PK_HOST: host memory; PK_DEV: device memory
     uint64_t count, unit;
+    uint64_t off = 0, tail = 0;
 };
+// the blob as positional writes and reads (the stream forms ignore the offset: their order is the blob's)
+typedef std::function<int(uint64_t off, const void* data, uint64_t bytes)> SnapSink;
+typedef std::function<int(uint64_t off, void* data, uint64_t bytes)> SnapSource;
 
 struct SnapPlan {
     SnapHeader h;
@@ -3407,7 +3412,53 @@ struct SnapPlan {
     SnapCensus cen;
     const uint32_t* sid;
     std::vector<uint32_t> bsizes;            // the pose hash's bucket sizes
+    uint64_t T = 0, P = 0;                   // this rank's live tables and pages (h.tables, h.pages: the filter's)
+    uint32_t tbase = 0, pbase = 0;           // those of the ranks below (a sharded filter)
 };
+
+const char* const kSnapStreamSharded =
+    "snapshot: a sharded filter is one file written and read by offset (eslam_gpu_save_at / eslam_gpu_load_at); "
+    "a sequential stream cannot carry a part of it";
+
+// all_gather of `bytes` of host memory per rank
+int snap_allgather(eslam_ctx* ctx, const void* send, void* recv, uint64_t bytes)
+{
+    const eslam_comm& c = ctx->comm;
+    if (!c.device_memory) {
+        if (c.allgather(c.user, send, recv, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
+        return ESLAM_OK;
+    }
+    Dev<char> d;
+    if (d.alloc(bytes * (c.nranks + 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the all_gather");
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = comm_allgather(ctx, d, d + bytes, bytes);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(recv, d + bytes, bytes * c.nranks, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ESLAM_OK;
+}
+
+// the last collective of a sharded save or load: ESLAM_OK on a rank means every rank succeeded.
+// A failing rank keeps its own code (and message); the others return ESLAM_ERR_COMM.
+int snap_agree(eslam_ctx* ctx, int rc)
+{
+    if (!ctx->sharded) return rc;
+    const std::string msg = ctx->err;
+    std::vector<int64_t> all(ctx->comm.nranks, 0);
+    const int64_t mine = rc;
+    const int crc = snap_allgather(ctx, &mine, all.data(), 8);
+    if (rc) {
+        ctx->err = msg;
+        return rc;
+    }
+    if (crc) return crc;
+    for (int r = 0; r < ctx->comm.nranks; ++r)
+        if (all[r]) return fail(ctx, ESLAM_ERR_COMM, ("snapshot: rank " + std::to_string(r) + " failed (" + std::to_string(all[r]) + ")").c_str());
+    return ESLAM_OK;
+}
 
 int snap_staging(eslam_ctx* ctx, uint64_t bytes)
 {
@@ -3435,7 +3486,7 @@ uint64_t snap_stage_bytes(uint64_t chunk, uint64_t largest, uint64_t unit)
 {
     uint64_t b = chunk < largest ? chunk : largest;
     b = b < unit ? unit : b;
-    return pad16(b < 4096 ? 4096 : b);
+    return pad16(b < 4096 ? 4096 : b) + 16;  // a part's last chunk carries the whole array's padding
 }
 
 uint64_t snap_tiles(uint64_t items) { return (items + kCompactTileItems - 1) / kCompactTileItems; }
@@ -3486,17 +3537,62 @@ int snap_census(eslam_ctx* ctx, SnapPlan& pl)
     HIPCHK(ctx, eslam_launch_snap_census_pages(&lm, &c, T, ctx->stream));
     rc = snap_read_count(ctx, c.counts + ptiles, &P);
     if (rc) return rc;
-    pl.h.tables = T;
-    pl.h.pages = P;
+    pl.T = pl.h.tables = T;
+    pl.P = pl.h.pages = P;
     return ESLAM_OK;
 }
 
 // settle, run a pending gather, take the census: the header, the scalars and the pieces of a save
+// this rank's part of the plan: everything but the counts of the other ranks
+int snap_plan_local(eslam_ctx* ctx, SnapPlan& pl);
+// the pieces this rank writes, in the blob's order
+int snap_plan_pieces(eslam_ctx* ctx, SnapPlan& pl);
+
+// On a sharded filter a collective: one all_gather of every rank's {code, tables, pages,
+// n_patches, update_count, minstd}.  A rank whose own part failed takes part in it, so either
+// every rank has a plan or every rank returns an error (its own, or ESLAM_ERR_COMM).
 int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
 {
-    if (ctx->sharded)
-        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: a sharded filter is not saved or loaded (per-rank blobs are not built)");
     if (const int rc_ = settle(ctx)) return rc_;
+    int rc = snap_plan_local(ctx, pl);
+    if (ctx->sharded) {
+        const std::string msg = ctx->err;
+        const int G = ctx->comm.nranks, me = ctx->comm.rank;
+        const uint64_t mine[6] = {(uint64_t)(int64_t)rc, pl.T, pl.P, pl.h.n_patches, pl.sc.update_count, pl.sc.minstd};
+        std::vector<uint64_t> all(6 * (size_t)G, 0);
+        const int crc = snap_allgather(ctx, mine, all.data(), sizeof(mine));
+        if (rc) {
+            ctx->err = msg;
+            return rc;
+        }
+        if (crc) return crc;
+        uint64_t T = 0, P = 0;
+        for (int r = 0; r < G; ++r) {
+            const uint64_t* q = &all[6 * (size_t)r];
+            if (q[0]) return fail(ctx, ESLAM_ERR_COMM, ("snapshot: rank " + std::to_string(r) + " failed").c_str());
+            if (q[3] != mine[3] || q[4] != mine[4] || q[5] != mine[5])
+                return fail(ctx, ESLAM_ERR_COMM, "snapshot: the ranks' grids, update counts or generators differ (not one filter)");
+            if (r == me) {
+                pl.tbase = (uint32_t)T;
+                pl.pbase = (uint32_t)P;
+            }
+            T += q[1];
+            P += q[2];
+        }
+        if (T > ctx->n_global) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the ranks hold more tables than the filter has particles");
+        if (P >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: 2^32 - 1 live pages or more");
+        pl.h.n = ctx->n_global;
+        pl.h.tables = T;
+        pl.h.pages = P;
+        snap_layout(pl.h, pl.h.sec, &pl.h.bytes);
+    }
+    return snap_plan_pieces(ctx, pl);
+}
+
+int snap_plan_local(eslam_ctx* ctx, SnapPlan& pl)
+{
+    memset(&pl.h, 0, sizeof(pl.h));
+    memset(&pl.sc, 0, sizeof(pl.sc));
     if (const int rc_ = check_poisoned(ctx)) return rc_;
     if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
     int rc = materialize(ctx);
@@ -3559,31 +3655,52 @@ int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
     sc.max_weight = ctl.max_weight;
     sc.update_count = ctl.update_count;
     sc.inv_n = ctl.inv_n;
-    // the pieces, in the blob's order
+    return ESLAM_OK;
+}
+
+// Every array of the blob is split by owner ("Sharded filters"): rank 0 writes
+// what every rank holds alike (header, grid, hash, scalars); the particle arrays go by shard;
+// tables and pages by the ranks' counts (rank-major order is the canonical order).  The zeros
+// behind an array go with the rank that holds its last element.  Unsharded: everything.
+int snap_plan_pieces(eslam_ctx* ctx, SnapPlan& pl)
+{
+    const SnapHeader& h = pl.h;
+    const Ctl& ctl = *ctx->ctl_host;
+    const DevState& s = ctx->st[ctl.base ^ ctl.flip];
     std::vector<Piece>& p = pl.pieces;
-    const uint64_t ncell = (uint64_t)h.width * h.height, n = h.n;
-    p.push_back(Piece{PK_HOST, &pl.h, sizeof(SnapHeader), 1});
-    p.push_back(Piece{PK_DEV, ctx->grid.cells, ncell + 1, 4});
-    p.push_back(Piece{PK_DEV, ctx->grid.patch, h.n_patches, 8});
-    if (h.has_height) p.push_back(Piece{PK_DEV, ctx->grid.height, h.n_patches, 4});
+    const bool lead = !ctx->sharded || ctx->comm.rank == 0;
+    uint64_t at = 0, mine = 0;
+    // the array of `total` units at the blob's cursor: this rank writes [first, first + count)
+    auto add = [&](int kind, const void* src, uint64_t total, uint64_t unit, uint64_t first, uint64_t count) {
+        Piece q{kind, src, count, unit};
+        q.off = at + first * unit;
+        q.tail = (count && first + count == total) ? pad16(total * unit) - total * unit : 0;
+        at += pad16(total * unit);
+        mine += count * unit + q.tail;
+        if (count) p.push_back(q);
+    };
+    auto whole = [&](int kind, const void* src, uint64_t total, uint64_t unit) { add(kind, src, total, unit, 0, lead ? total : 0); };
+    const uint64_t ncell = (uint64_t)h.width * h.height, n = h.n, gb = ctx->sharded ? ctx->gbase : 0, nl = ctx->n;
+    whole(PK_HOST, &pl.h, sizeof(SnapHeader), 1);
+    whole(PK_DEV, ctx->grid.cells, ncell + 1, 4);
+    whole(PK_DEV, ctx->grid.patch, h.n_patches, 8);
+    if (h.has_height) whole(PK_DEV, ctx->grid.height, h.n_patches, 4);
     if (ctx->has_hash) {
-        for (int f = 0; f < 4; ++f) p.push_back(Piece{PK_DEV, hash_field(ctx, f), h.hash_n, 8});
-        p.push_back(Piece{PK_HOST, ctx->hash_bucket.data(), h.hash_n * 4, 1});
-        p.push_back(Piece{PK_HOST, pl.bsizes.data(), pl.bsizes.size() * 4, 1});
+        for (int f = 0; f < 4; ++f) whole(PK_DEV, hash_field(ctx, f), h.hash_n, 8);
+        whole(PK_HOST, ctx->hash_bucket.data(), h.hash_n * 4, 1);
+        whole(PK_HOST, pl.bsizes.data(), pl.bsizes.size() * 4, 1);
     }
     const double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
-    for (int f = 0; f < 7; ++f) p.push_back(Piece{PK_DEV, f7[f], n, 8});
-    p.push_back(Piece{PK_DEV, s.flags, n, 1});
-    p.push_back(Piece{PK_HOST, &pl.sc, sizeof(SnapScalars), 1});
+    for (int f = 0; f < 7; ++f) add(PK_DEV, f7[f], n, 8, gb, nl);
+    add(PK_DEV, s.flags, n, 1, gb, nl);
+    whole(PK_HOST, &pl.sc, sizeof(SnapScalars), 1);
     if (h.sections & (1u << kSecMaps)) {
-        p.push_back(Piece{PK_SID, nullptr, n, 4});
-        p.push_back(Piece{PK_TABLES, nullptr, h.tables, (uint64_t)h.row_words * 4});
-        p.push_back(Piece{PK_OWNER, nullptr, h.pages, 4});
-        p.push_back(Piece{PK_PAGES, nullptr, h.pages, kPageBytes});
+        add(PK_SID, nullptr, n, 4, gb, nl);
+        add(PK_TABLES, nullptr, h.tables, (uint64_t)h.row_words * 4, pl.tbase, pl.T);
+        add(PK_OWNER, nullptr, h.pages, 4, pl.pbase, pl.P);
+        add(PK_PAGES, nullptr, h.pages, kPageBytes, pl.pbase, pl.P);
     }
-    uint64_t total = 0;
-    for (const Piece& q : p) total += pad16(q.count * q.unit);
-    if (total != h.bytes) return fail(ctx, ESLAM_ERR_HIP, "snapshot: the pieces do not add up to the layout");
+    if (at != h.bytes || (!ctx->sharded && mine != h.bytes)) return fail(ctx, ESLAM_ERR_HIP, "snapshot: the pieces do not add up to the layout");
     return ESLAM_OK;
 }
 
@@ -3627,19 +3744,37 @@ struct SnapChunk {
     bool last;                               // the piece's last chunk: its padding follows
 };
 
-int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t capacity)
+int snap_write_pieces(eslam_ctx* ctx, SnapPlan& pl, const SnapSink& w, uint64_t chunk, uint64_t* chunks_out);
+
+// positional: the sink takes every chunk with its offset (a sharded filter: this rank's chunks,
+// and the call is a collective); else the chunks come in the blob's order
+int snap_save(eslam_ctx* ctx, const SnapSink& w, bool positional, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t capacity)
 {
     if (info) memset(info, 0, sizeof(*info));
     if (!ctx || !w) return ESLAM_ERR_INVALID_ARG;
+    if (ctx->sharded && !positional) return fail(ctx, ESLAM_ERR_UNSUPPORTED, kSnapStreamSharded);
     if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
     const uint64_t chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
     SnapPlan pl;
-    int rc = snap_plan(ctx, pl);
+    int rc = snap_plan(ctx, pl);             // sharded: every rank has a plan, or every rank returns here
     if (rc) return rc;
-    if (capacity < pl.h.bytes) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: the buffer is smaller than the snapshot (eslam_gpu_snapshot_size)");
+    uint64_t chunks = 0;
+    if (capacity < pl.h.bytes)
+        rc = fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: the buffer is smaller than the snapshot (eslam_gpu_snapshot_size)");
+    else
+        rc = snap_write_pieces(ctx, pl, w, chunk, &chunks);
+    rc = snap_agree(ctx, rc);
+    if (rc) return rc;
+    snap_fill_info(pl.h, chunks, info);
+    return ESLAM_OK;
+}
+
+int snap_write_pieces(eslam_ctx* ctx, SnapPlan& pl, const SnapSink& w, uint64_t chunk, uint64_t* chunks_out)
+{
+    int rc = ESLAM_OK;
     uint64_t largest = 0, unit = 16;
     for (const Piece& q : pl.pieces) {
-        largest = std::max(largest, pad16(q.count * q.unit));
+        largest = std::max(largest, pad16(q.count * q.unit + q.tail));
         unit = std::max(unit, pad16(q.unit));
     }
     rc = snap_staging(ctx, snap_stage_bytes(chunk, largest, unit));
@@ -3670,8 +3805,8 @@ int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes
         } else if (q.kind == PK_DEV) {
             HIPCHK(ctx, hipMemcpyAsync(host, (const char*)q.src + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
         } else {
-            HIPCHK(ctx, eslam_launch_snap_pack(q.kind - PK_SID, &ctx->lm, &pl.cen, pl.sid, pl.h.tables, c.k0, c.cnt, pl.h.row_words,
-                                               ctx->snap_dev[slot], ctx->stream));
+            HIPCHK(ctx, eslam_launch_snap_pack(q.kind - PK_SID, &ctx->lm, &pl.cen, pl.sid, pl.T, pl.tbase, pl.pbase, c.k0, c.cnt,
+                                               pl.h.row_words, ctx->snap_dev[slot], ctx->stream));
             HIPCHK(ctx, hipMemcpyAsync(host, ctx->snap_dev[slot], bytes, hipMemcpyDeviceToHost, ctx->stream));
         }
         HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
@@ -3689,12 +3824,11 @@ int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes
         HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));
         const Piece& q = P[cur.piece];
         uint64_t bytes = cur.cnt * q.unit;
-        if (cur.last) {                      // zeros up to the next 16-byte boundary
-            const uint64_t all = q.count * q.unit, padded = pad16(all);
-            memset(ctx->snap_host[slot].as<char>() + bytes, 0, padded - all);
-            bytes += padded - all;
+        if (cur.last && q.tail) {            // zeros up to the array's next 16-byte boundary
+            memset(ctx->snap_host[slot].as<char>() + bytes, 0, q.tail);
+            bytes += q.tail;
         }
-        if (w(user, ctx->snap_host[slot], bytes) != 0) {
+        if (w(q.off + cur.k0 * q.unit, ctx->snap_host[slot], bytes) != 0) {
             rc = fail(ctx, ESLAM_ERR_COMM, "snapshot: the write callback failed");
             break;
         }
@@ -3706,18 +3840,20 @@ int snap_save(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes
         (void)hipStreamSynchronize(ctx->stream);    // a copy into the pinned buffers may be in flight
         return rc;
     }
-    snap_fill_info(pl.h, chunks, info);
+    *chunks_out = chunks;
     return ESLAM_OK;
 }
 
 // ---- load -------------------------------------------------------------------------------
 struct SnapReader {
     eslam_ctx* ctx;
-    eslam_read_fn r;
-    void* user;
+    SnapSource r;
     uint64_t chunk;
     uint32_t slot = 0;
     uint64_t chunks = 0;
+    uint64_t at = 0;                         // the blob offset of the next array
+    uint64_t dst0 = 0;                       // PK_TABLES / PK_OWNER: the pool entry of unit `first`
+    const SnapSubset* sub = nullptr;         // PK_OWNER: owners renamed through the subset
 };
 typedef std::function<int(const void* data, uint64_t k0, uint64_t cnt)> SnapCheck;
 
@@ -3726,10 +3862,32 @@ int snap_bad(eslam_ctx* ctx, const char* msg) { return fail(ctx, ESLAM_ERR_INVAL
 // one array of the blob through the staging buffers: every chunk is read into a pinned slot,
 // checked on the host (check; may be empty), and then copied to dst (PK_HOST: host memory,
 // may be null; PK_DEV: device memory) or unpacked into pool entries [k0, k0 + cnt)
+int snap_read_part(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check,
+                   uint64_t off, uint64_t tail);
+
+// the whole array at the cursor
 int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check)
 {
+    const uint64_t all = count * unit, off = rd.at;
+    rd.at += pad16(all);
+    rd.dst0 = 0;
+    return snap_read_part(rd, kind, dst, count, unit, rw, check, off, pad16(all) - all);
+}
+
+// units [first, first + count) of the array of `total` units at the cursor, which then moves past the array
+int snap_read_slice(SnapReader& rd, int kind, void* dst, uint64_t total, uint64_t first, uint64_t count, uint64_t unit,
+                    const SnapCheck& check)
+{
+    const uint64_t off = rd.at + first * unit;
+    rd.at += pad16(total * unit);
+    rd.dst0 = 0;
+    return snap_read_part(rd, kind, dst, count, unit, 0, check, off, 0);
+}
+
+int snap_read_part(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check,
+                   uint64_t off, uint64_t tail)
+{
     eslam_ctx* ctx = rd.ctx;
-    const uint64_t all = count * unit, tail = pad16(all) - all;
     uint64_t per = rd.chunk / unit;
     per = per ? per : 1;
     for (uint64_t k0 = 0; k0 < count; k0 += per) {
@@ -3739,7 +3897,7 @@ int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit
         rd.slot ^= 1u;
         HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));     // the slot's previous chunk has left it
         char* host = ctx->snap_host[slot].as<char>();
-        if (rd.r(rd.user, host, bytes + (last ? tail : 0)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
+        if (rd.r(off + k0 * unit, host, bytes + (last ? tail : 0)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
         ++rd.chunks;
         if (check) {
             const int rc = check(host, k0, cnt);
@@ -3753,7 +3911,10 @@ int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit
             HIPCHK(ctx, hipMemcpyAsync((char*)dst + k0 * unit, host, bytes, hipMemcpyHostToDevice, ctx->stream));
         } else {
             HIPCHK(ctx, hipMemcpyAsync(ctx->snap_dev[slot], host, bytes, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(ctx, eslam_launch_snap_unpack(kind - PK_SID, &ctx->lm, k0, cnt, rw, ctx->snap_dev[slot], ctx->stream));
+            if (kind == PK_OWNER && rd.sub)
+                HIPCHK(ctx, eslam_launch_snap_unpack_owner_subset(&ctx->lm, rd.dst0 + k0, cnt, rd.sub, ctx->snap_dev[slot], ctx->stream));
+            else
+                HIPCHK(ctx, eslam_launch_snap_unpack(kind - PK_SID, &ctx->lm, rd.dst0 + k0, cnt, rw, ctx->snap_dev[slot], ctx->stream));
         }
         HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
     }
@@ -3801,7 +3962,9 @@ int snap_check_header(eslam_ctx* ctx, const SnapHeader& h, uint64_t known_bytes)
         if (sec[k].off != h.sec[k].off || sec[k].size != h.sec[k].size)
             return snap_bad(ctx, "snapshot: a section's offset or size does not match the header's counts");
     if (bytes != h.bytes || (known_bytes && known_bytes != h.bytes)) return snap_bad(ctx, "snapshot: size does not match the header (truncated?)");
-    if (maps) {
+    if (ctx->sharded && h.n != ctx->n_global)
+        return snap_bad(ctx, "snapshot: its particle count is not the sharded context's n_global");
+    if (maps && !ctx->sharded) {             // a sharded load checks its own part's pages, once it has counted them
         const uint64_t per = ctx->cfg.local_map_pages ? ctx->cfg.local_map_pages : kDefaultMapPages;
         if (h.pages > (h.n ? h.n : 1) * per)
             return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: more live pages than the context's pool holds (raise eslam_config.local_map_pages)");
@@ -3809,14 +3972,45 @@ int snap_check_header(eslam_ctx* ctx, const SnapHeader& h, uint64_t known_bytes)
     return ESLAM_OK;
 }
 
-int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known_bytes)
+// the host's check of a chunk of table rows: every id before a kernel reads it
+SnapCheck snap_rows_check(eslam_ctx* ctx, uint32_t rw, uint32_t W, uint32_t V, uint64_t P)
+{
+    return [=](const void* d, uint64_t, uint64_t cnt) {
+        const uint32_t* v = (const uint32_t*)d;
+        for (uint64_t k = 0; k < cnt; ++k) {
+            const uint32_t* r = v + k * rw;
+            if (r[2] > 1u || r[3] > V) return snap_bad(ctx, "snapshot: a table's shadow flag or trail mark is out of range");
+            for (uint32_t s = 0; s < W; ++s)
+                if (r[4 + s] != DM_LM_NONE && r[4 + s] >= P)
+                    return snap_bad(ctx, "snapshot: a window slot names a page past the snapshot's pages");
+            for (uint32_t e = 0; e < V; ++e) {
+                const uint32_t pg = r[4 + W + 3 * e + 2];
+                if (pg != DM_LM_NONE && pg >= P) return snap_bad(ctx, "snapshot: a trail entry names a page past the snapshot's pages");
+            }
+        }
+        return (int)ESLAM_OK;
+    };
+}
+
+// the header, read and checked: no collective yet, and every rank of a sharded filter decides alike
+int snap_load_header(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known_bytes)
 {
     if (known_bytes && known_bytes < sizeof(SnapHeader)) return snap_bad(ctx, "snapshot: shorter than its header");
-    if (rd.r(rd.user, &h, sizeof(h)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
+    if (rd.r(0, &h, sizeof(h)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
     ++rd.chunks;
-    int rc = snap_check_header(ctx, h, known_bytes);
-    if (rc) return rc;
+    rd.at = sizeof(h);
+    return snap_check_header(ctx, h, known_bytes);
+}
+
+int snap_load_maps_subset(eslam_ctx* ctx, SnapReader& rd, const SnapHeader& h, uint64_t* pages_loaded);
+
+// everything behind the header.  A sharded filter reads the shared parts in full, its shard
+// [gbase, gbase + nl) of the particle arrays, and of the maps what its particles name.
+int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h)
+{
+    int rc = ESLAM_OK;
     const uint64_t ncell = (uint64_t)h.width * h.height, np = h.n_patches, n = h.n;
+    const uint64_t gb = ctx->sharded ? ctx->gbase : 0, nl = ctx->sharded ? ctx->gall[ctx->comm.rank + 1] - ctx->gbase : n;
     const bool hash = (h.sections >> kSecHash) & 1u, maps = (h.sections >> kSecMaps) & 1u;
     uint64_t largest = std::max(std::max((ncell + 1) * 4, np * 8), std::max(n * 8, h.hash_n * 8));
     largest = std::max(largest, std::max(h.tables * h.row_words * 4, h.pages * kPageBytes));
@@ -3904,14 +4098,19 @@ int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known
         ctx->has_hash = true;
     }
     // ---- the particles (the eight arrays of the current buffer, into buffer 0)
-    rc = alloc_particles(ctx, n);
+    rc = alloc_particles(ctx, nl);
     if (rc) return rc;
     if (maps && !ctx->lm_ready) return fail(ctx, ESLAM_ERR_HIP, "snapshot: per-particle maps not allocated");
     {
         const DevState& s = ctx->st[0];
         double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
-        for (int f = 0; f < 7 && !rc; ++f) rc = snap_read(rd, PK_DEV, f7[f], n, 8, 0, none);
-        if (!rc) rc = snap_read(rd, PK_DEV, s.flags, n, 1, 0, none);
+        if (ctx->sharded) {
+            for (int f = 0; f < 7 && !rc; ++f) rc = snap_read_slice(rd, PK_DEV, f7[f], n, gb, nl, 8, none);
+            if (!rc) rc = snap_read_slice(rd, PK_DEV, s.flags, n, gb, nl, 1, none);
+        } else {
+            for (int f = 0; f < 7 && !rc; ++f) rc = snap_read(rd, PK_DEV, f7[f], n, 8, 0, none);
+            if (!rc) rc = snap_read(rd, PK_DEV, s.flags, n, 1, 0, none);
+        }
         if (rc) return rc;
     }
     // ---- the scalars
@@ -3941,8 +4140,18 @@ int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known
         if (rc) return rc;
         ctx->dbg_valid = false;
     }
+    // ---- the per-particle maps of a sharded filter: this rank's subset, then the page counters
+    if (maps && ctx->sharded) {
+        uint64_t ploc = 0;
+        rc = snap_load_maps_subset(ctx, rd, h, &ploc);
+        if (!rc) rc = read_ctl(ctx);
+        if (rc) return rc;
+        ctx->ctl_host->pg_nfree = ctx->lm.npages - ploc;
+        rc = write_ctl(ctx);
+        if (rc) return rc;
+    }
     // ---- the per-particle maps: table k into pool entry k, page k into pool entry k
-    if (maps) {
+    if (maps && !ctx->sharded) {
         const uint64_t T = h.tables, P = h.pages;
         const uint32_t rw = h.row_words, W = h.wx * h.wy, V = h.local_map_trail;
         rc = snap_read(rd, PK_DEV, ctx->st[0].sid, n, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
@@ -3951,20 +4160,7 @@ int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known
                 if (v[k] >= T) return snap_bad(ctx, "snapshot: a particle names a table past the snapshot's tables");
             return (int)ESLAM_OK;
         });
-        if (!rc) rc = snap_read(rd, PK_TABLES, nullptr, T, (uint64_t)rw * 4, rw, [&](const void* d, uint64_t, uint64_t cnt) {
-            const uint32_t* v = (const uint32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k) {
-                const uint32_t* r = v + k * rw;
-                if (r[2] > 1u || r[3] > V) return snap_bad(ctx, "snapshot: a table's shadow flag or trail mark is out of range");
-                for (uint32_t s = 0; s < W; ++s)
-                    if (r[4 + s] != DM_LM_NONE && r[4 + s] >= P) return snap_bad(ctx, "snapshot: a window slot names a page past the snapshot's pages");
-                for (uint32_t e = 0; e < V; ++e) {
-                    const uint32_t pg = r[4 + W + 3 * e + 2];
-                    if (pg != DM_LM_NONE && pg >= P) return snap_bad(ctx, "snapshot: a trail entry names a page past the snapshot's pages");
-                }
-            }
-            return (int)ESLAM_OK;
-        });
+        if (!rc) rc = snap_read(rd, PK_TABLES, nullptr, T, (uint64_t)rw * 4, rw, snap_rows_check(ctx, rw, W, V, P));
         if (!rc) rc = snap_read(rd, PK_OWNER, nullptr, P, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
             const uint32_t* v = (const uint32_t*)d;
             for (uint64_t k = 0; k < cnt; ++k)
@@ -3979,22 +4175,159 @@ int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known
     return ESLAM_OK;
 }
 
-int snap_load(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t known_bytes)
+// f(a, b, local) for every run [a, b) of set bits below `limit`, ascending; local: the set bits below a
+template <typename F>
+int snap_for_runs(const std::vector<uint32_t>& bits, uint64_t limit, F f)
+{
+    uint64_t i = 0, local = 0;
+    auto bit = [&](uint64_t k) { return (bits[k >> 5] >> (k & 31)) & 1u; };
+    while (i < limit) {
+        if (!(i & 31) && bits[i >> 5] == 0u) {
+            i += 32;
+            continue;
+        }
+        if (!bit(i)) {
+            ++i;
+            continue;
+        }
+        uint64_t b = i + 1;
+        while (b < limit) {
+            if (!(b & 31) && bits[b >> 5] == 0xffffffffu) b += 32;
+            else if (bit(b)) ++b;
+            else break;
+        }
+        if (b > limit) b = limit;
+        if (const int rc = f(i, b, local)) return rc;
+        local += b - i;
+        i = b;
+    }
+    return ESLAM_OK;
+}
+
+// The per-particle maps of a sharded load ("Sharded filters"): the tables this
+// rank's particles name, in the snapshot's order, into pool tables 0, 1, ...; the pages those
+// tables name into pool pages 0, 1, ...  Two bitmaps over the snapshot's ids, ranked by
+// popcount on the device; the host walks their runs of set bits and reads each run's rows,
+// owner words and pages.  With every bit set this is the one-GPU load: entry k into pool entry k.
+int snap_load_maps_subset(eslam_ctx* ctx, SnapReader& rd, const SnapHeader& h, uint64_t* pages_loaded)
+{
+    const uint64_t T = h.tables, P = h.pages, n = h.n, gb = ctx->gbase, nl = ctx->n;
+    const uint32_t rw = h.row_words, W = h.wx * h.wy, V = h.local_map_trail;
+    const uint64_t tw = (T + 31) / 32, pw = (P + 31) / 32;
+    const uint64_t off_sid = rd.at, off_tab = off_sid + pad16(n * 4), off_own = off_tab + pad16(T * rw * 4), off_pg = off_own + pad16(P * 4);
+    const SnapCheck none;
+    Dev<uint32_t> scratch;                   // dropped with the call
+    const uint64_t words = tw + (tw + 1) + pw + (pw + 1);
+    if (scratch.alloc(words * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the subset's bitmaps");
+    }
+    HIPCHK(ctx, hipMemsetAsync(scratch, 0, words * 4, ctx->stream));
+    SnapSubset sub;
+    sub.tbits = scratch;
+    sub.tpre = sub.tbits + tw;
+    sub.pbits = sub.tpre + tw + 1;
+    sub.ppre = sub.pbits + pw;
+    sub.tables = T;
+    sub.pages = P;
+    // the scratch goes only once the stream is idle, whichever way the call ends
+    struct Idle {
+        hipStream_t s;
+        ~Idle() { (void)hipStreamSynchronize(s); }
+    } idle{ctx->stream};
+    // ---- tables: the bits of this shard's names, their ranks, the names rewritten
+    uint32_t* sid = ctx->st[0].sid;
+    int rc = snap_read_slice(rd, PK_DEV, sid, n, gb, nl, 4, [&](const void* d, uint64_t, uint64_t cnt) {
+        const uint32_t* v = (const uint32_t*)d;
+        for (uint64_t k = 0; k < cnt; ++k)
+            if (v[k] >= T) return snap_bad(ctx, "snapshot: a particle names a table past the snapshot's tables");
+        return (int)ESLAM_OK;
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, eslam_launch_snap_mark_ids(sid, nl, sub.tbits, T, ctx->stream));
+    HIPCHK(ctx, eslam_launch_snap_rank_bits(sub.tbits, tw, sub.tpre, ctx->stream));
+    HIPCHK(ctx, eslam_launch_snap_rank_sid(sid, nl, &sub, ctx->stream));
+    std::vector<uint32_t> tbits(tw + 1), pbits(pw + 1);
+    uint32_t tloc = 0, ploc = 0;
+    HIPCHK(ctx, hipMemcpyAsync(tbits.data(), sub.tbits, tw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&tloc, sub.tpre + tw, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (tloc > ctx->lm.ntables || tloc > nl) return fail(ctx, ESLAM_ERR_HIP, "snapshot: more tables named than particles");
+    // ---- rows: each run of named tables into pool tables local(run start)..., page ids still the snapshot's
+    const SnapCheck rows = snap_rows_check(ctx, rw, W, V, P);
+    rc = snap_for_runs(tbits, T, [&](uint64_t a, uint64_t b, uint64_t local) {
+        rd.dst0 = local;
+        return snap_read_part(rd, PK_TABLES, nullptr, b - a, (uint64_t)rw * 4, rw, rows, off_tab + a * rw * 4, 0);
+    });
+    if (rc) return rc;
+    // ---- pages: the bits of what those rows name, their ranks; this rank's pool must hold them
+    HIPCHK(ctx, eslam_launch_snap_mark_rows(&ctx->lm, tloc, sub.pbits, P, ctx->stream));
+    HIPCHK(ctx, eslam_launch_snap_rank_bits(sub.pbits, pw, sub.ppre, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(pbits.data(), sub.pbits, pw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&ploc, sub.ppre + pw, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ploc > ctx->lm.npages)
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY,
+                    "snapshot: more live pages than this rank's pool holds (raise eslam_config.local_map_pages)");
+    HIPCHK(ctx, eslam_launch_snap_renumber_tables(&ctx->lm, tloc, &sub, ctx->stream));
+    rd.sub = &sub;
+    rc = snap_for_runs(pbits, P, [&](uint64_t a, uint64_t b, uint64_t local) {
+        rd.dst0 = local;
+        return snap_read_part(rd, PK_OWNER, nullptr, b - a, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
+            const uint32_t* v = (const uint32_t*)d;
+            for (uint64_t k = 0; k < cnt; ++k)
+                if (v[k] != DM_LM_NONE && v[k] >= T) return snap_bad(ctx, "snapshot: a page's owner is past the snapshot's tables");
+            return (int)ESLAM_OK;
+        }, off_own + a * 4, 0);
+    });
+    rd.sub = nullptr;
+    rd.dst0 = 0;
+    if (rc) return rc;
+    // consecutive set bits are consecutive local ids: a run of pages is one plain copy
+    rc = snap_for_runs(pbits, P, [&](uint64_t a, uint64_t b, uint64_t local) {
+        return snap_read_part(rd, PK_DEV, (char*)ctx->lm.page + local * kPageBytes, b - a, kPageBytes, 0, none, off_pg + a * kPageBytes, 0);
+    });
+    if (rc) return rc;
+    HIPCHK(ctx, eslam_launch_snap_finish(&ctx->lm, tloc, ploc, ctx->stream));
+    rd.at = off_pg + P * kPageBytes;
+    *pages_loaded = ploc;
+    return ESLAM_OK;
+}
+
+// positional: the source is read by offset (a sharded filter: a collective, and each rank reads
+// its part only); else in the blob's order, every byte once
+int snap_load(eslam_ctx* ctx, const SnapSource& r, bool positional, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t known_bytes)
 {
     if (info) memset(info, 0, sizeof(*info));
     if (!ctx || !r) return ESLAM_ERR_INVALID_ARG;
-    if (ctx->sharded)
-        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: a sharded filter is not saved or loaded (per-rank blobs are not built)");
+    if (ctx->sharded && !positional) return fail(ctx, ESLAM_ERR_UNSUPPORTED, kSnapStreamSharded);
     if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
-    if (const int rc_ = settle(ctx)) return rc_;
     SnapReader rd;
     rd.ctx = ctx;
     rd.r = r;
-    rd.user = user;
     rd.chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
     SnapHeader h;
     memset(&h, 0, sizeof(h));
-    const int rc = snap_load_body(ctx, rd, h, known_bytes);
+    int rc = ESLAM_OK;
+    if (ctx->sharded) {
+        // the header decides alike on every rank, before the first collective
+        rc = snap_load_header(ctx, rd, h, known_bytes);
+        if (rc) {
+            const std::string msg = ctx->err;
+            (void)hipStreamSynchronize(ctx->stream);
+            free_particles(ctx);
+            ctx->err = msg;
+            return rc;
+        }
+        rc = settle(ctx);
+    } else {
+        rc = settle(ctx);
+        if (rc) return rc;
+        rc = snap_load_header(ctx, rd, h, known_bytes);
+    }
+    if (!rc) rc = snap_load_body(ctx, rd, h);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    rc = snap_agree(ctx, rc);                // sharded: no rank goes on with a filter another rank could not load
     if (rc) {
         // the context reads as "no particles"; set_map + init_* or another load starts it over
         const std::string msg = ctx->err;
@@ -4030,8 +4363,20 @@ int snap_mem_read(void* user, void* data, uint64_t bytes)
     return 0;
 }
 
+SnapSink snap_stream_sink(eslam_write_fn w, void* user)
+{
+    if (!w) return SnapSink();
+    return [w, user](uint64_t, const void* data, uint64_t bytes) { return w(user, data, bytes); };
+}
+SnapSource snap_stream_source(eslam_read_fn r, void* user)
+{
+    if (!r) return SnapSource();
+    return [r, user](uint64_t, void* data, uint64_t bytes) { return r(user, data, bytes); };
+}
+
 }  // namespace
 
+// a collective on a sharded filter
 extern "C" int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info)
 {
     if (info) memset(info, 0, sizeof(*info));
@@ -4045,24 +4390,50 @@ extern "C" int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info
 
 extern "C" int eslam_gpu_save_stream(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
 {
-    return snap_save(ctx, w, user, chunk_bytes, info, ~0ull);
+    return snap_save(ctx, snap_stream_sink(w, user), false, chunk_bytes, info, ~0ull);
 }
 
 extern "C" int eslam_gpu_load_stream(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
 {
-    return snap_load(ctx, r, user, chunk_bytes, info, 0);
+    return snap_load(ctx, snap_stream_source(r, user), false, chunk_bytes, info, 0);
+}
+
+extern "C" int eslam_gpu_save_at(eslam_ctx* ctx, eslam_pwrite_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
+{
+    SnapSink sink;
+    if (w) sink = [w, user](uint64_t off, const void* data, uint64_t bytes) { return w(user, off, data, bytes); };
+    return snap_save(ctx, sink, true, chunk_bytes, info, ~0ull);
+}
+
+extern "C" int eslam_gpu_load_at(eslam_ctx* ctx, eslam_pread_fn r, void* user, uint64_t known_bytes, uint64_t chunk_bytes,
+                                 eslam_snapshot_info* info)
+{
+    SnapSource src;
+    if (r) src = [r, user](uint64_t off, void* data, uint64_t bytes) { return r(user, off, data, bytes); };
+    return snap_load(ctx, src, true, chunk_bytes, info, known_bytes);
 }
 
 extern "C" int eslam_gpu_save(eslam_ctx* ctx, void* buf, uint64_t capacity, uint64_t chunk_bytes, eslam_snapshot_info* info)
 {
     if (!buf) return ESLAM_ERR_INVALID_ARG;
     SnapMem m{(char*)buf, capacity};
-    return snap_save(ctx, snap_mem_write, &m, chunk_bytes, info, capacity);
+    return snap_save(ctx, snap_stream_sink(snap_mem_write, &m), false, chunk_bytes, info, capacity);
 }
 
+// on a sharded filter every rank holds the whole blob and reads its part of it
 extern "C" int eslam_gpu_load(eslam_ctx* ctx, const void* buf, uint64_t bytes, uint64_t chunk_bytes, eslam_snapshot_info* info)
 {
     if (!buf) return ESLAM_ERR_INVALID_ARG;
+    if (ctx && ctx->sharded) {
+        const char* p = (const char*)buf;
+        const SnapSource src = [p, bytes](uint64_t off, void* data, uint64_t b) {
+            if (off > bytes || b > bytes - off) return 1;
+            memcpy(data, p + off, b);
+            return 0;
+        };
+        return snap_load(ctx, src, true, chunk_bytes, info, bytes ? bytes : 1);
+    }
     SnapMem m{(char*)const_cast<void*>(buf), bytes};
-    return snap_load(ctx, snap_mem_read, &m, chunk_bytes, info, bytes ? bytes : 1);
+    return snap_load(ctx, snap_stream_source(snap_mem_read, &m), false, chunk_bytes, info, bytes ? bytes : 1);
 }
+

@@ -474,6 +474,16 @@ struct SnapCensus {
     uint32_t* plist;                     // per compact id: the pool page
     uint32_t* counts;                    // the compactions' tile counts
 };
+// a sharded load's subset of a snapshot: the tables this rank's particles name and the pages
+// those tables name, as bitmaps over the snapshot's compact ids; the local id of a set bit b
+// is pre[b >> 5] + popc(bits[b >> 5] & below(b & 31)) (set bits keep their order)
+struct SnapSubset {
+    uint32_t* tbits;                     // (tables + 31) / 32 words
+    uint32_t* tpre;                      // their exclusive popcount prefix, the total behind it
+    uint32_t* pbits;                     // (pages + 31) / 32 words
+    uint32_t* ppre;
+    uint64_t tables, pages;              // the snapshot's counts (ids at or past them are never looked up)
+};
 constexpr uint64_t kSnapDefaultChunk = 64ull << 20;
 
 // logDebug records of the last update (k_contact_records), indexed by the particle's

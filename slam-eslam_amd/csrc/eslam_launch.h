@@ -128,9 +128,17 @@ hipError_t eslam_launch_snap_census_tables(const LocalMaps* lm, const SnapCensus
                                            hipStream_t stream);
 hipError_t eslam_launch_snap_census_pages(const LocalMaps* lm, const SnapCensus* c, uint64_t T, hipStream_t stream);
 hipError_t eslam_launch_snap_pack(int what, const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t T,
-                                  uint64_t k0, uint64_t cnt, uint32_t rw, void* out, hipStream_t stream);
+                                  uint32_t tbase, uint32_t pbase, uint64_t k0, uint64_t cnt, uint32_t rw, void* out,
+                                  hipStream_t stream);
 hipError_t eslam_launch_snap_unpack(int what, const LocalMaps* lm, uint64_t k0, uint64_t cnt, uint32_t rw, const void* in,
                                     hipStream_t stream);
 hipError_t eslam_launch_snap_finish(const LocalMaps* lm, uint64_t T, uint64_t P, hipStream_t stream);
+hipError_t eslam_launch_snap_mark_ids(const uint32_t* ids, uint64_t n, uint32_t* bits, uint64_t limit, hipStream_t stream);
+hipError_t eslam_launch_snap_mark_rows(const LocalMaps* lm, uint64_t T, uint32_t* bits, uint64_t limit, hipStream_t stream);
+hipError_t eslam_launch_snap_rank_bits(const uint32_t* bits, uint64_t words, uint32_t* pre, hipStream_t stream);
+hipError_t eslam_launch_snap_rank_sid(uint32_t* sid, uint64_t n, const SnapSubset* s, hipStream_t stream);
+hipError_t eslam_launch_snap_renumber_tables(const LocalMaps* lm, uint64_t T, const SnapSubset* s, hipStream_t stream);
+hipError_t eslam_launch_snap_unpack_owner_subset(const LocalMaps* lm, uint64_t k0, uint64_t cnt, const SnapSubset* s, const void* in,
+                                                 hipStream_t stream);
 
 }  // extern "C"

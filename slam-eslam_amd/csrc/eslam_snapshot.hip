@@ -9,6 +9,10 @@
 // ranks; the pack kernels write contiguous ranges of ranks into a staging buffer, the unpack
 // kernels read them back into pool entries [k0, k1).  A save reads the pool and the particles
 // and writes only its own scratch.
+// A sharded filter's ranks write one blob between them: the packs add the ids of the ranks
+// below (tbase, pbase).  A sharded load takes the subset its particles name: two bitmaps over
+// the snapshot's ids, ranked by popcount (k_snap_mark_*, k_snap_popc, k_snap_rank_sid,
+// k_snap_renumber_tables, k_snap_unpack_owner_subset).
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "eslam_internal.h"
@@ -27,6 +31,7 @@ struct SnapArgs {
     uint64_t n;                          // particles
     uint64_t T;                          // live tables (the page census and the packs)
     uint32_t W, K, toff, pad;            // window slots; keys per table (W + V); trail offset
+    uint32_t tbase, pbase;               // a sharded save: the compact ids of this rank's first table and page
 };
 
 // the page of key s of a table row (DM_LM_NONE: none, or an entry past the high-water mark)
@@ -141,7 +146,7 @@ __global__ void __launch_bounds__(kBlock) k_snap_pack_sid(SnapArgs a, uint64_t i
     const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= cnt) return;
     const uint32_t t = a.sid[i0 + j];
-    out[j] = t < a.lm.ntables ? a.c.trank[t] : DM_LM_NONE;
+    out[j] = t < a.lm.ntables ? a.c.trank[t] + a.tbase : DM_LM_NONE;
 }
 
 // a wave per table: the row {centre x, y, shadow, hw, W slots, V x {a, b, page}} padded to
@@ -165,12 +170,12 @@ __global__ void __launch_bounds__(kBlock) k_snap_pack_tables(SnapArgs a, uint64_
         else if (q == 3u) v = hw;
         else if (q < 4u + a.W) {
             const uint32_t p = row[q - 4u];
-            v = (p != DM_LM_NONE && p < a.lm.npages) ? a.c.prank[p] : DM_LM_NONE;
+            v = (p != DM_LM_NONE && p < a.lm.npages) ? a.c.prank[p] + a.pbase : DM_LM_NONE;
         } else if (q < 4u + a.W + 3u * a.lm.V) {
             const uint32_t e = (q - 4u - a.W) / 3u, f = (q - 4u - a.W) - 3u * e;
             const uint32_t p = e < hw ? row[a.toff + 4u * e + 2u] : DM_LM_NONE;
             const bool live = p != DM_LM_NONE && p < a.lm.npages;
-            if (f == 2u) v = live ? a.c.prank[p] : DM_LM_NONE;
+            if (f == 2u) v = live ? a.c.prank[p] + a.pbase : DM_LM_NONE;
             else v = live ? row[a.toff + 4u * e + f] : 0u;
         }
         o[q] = v;
@@ -186,7 +191,7 @@ __global__ void __launch_bounds__(kBlock) k_snap_pack_owner(SnapArgs a, uint64_t
     const uint64_t o = a.lm.owner[a.c.plist[k0 + j]];
     const uint32_t t = (uint32_t)o;
     uint32_t v = DM_LM_NONE;
-    if (t < a.lm.ntables && a.c.first[t] != 0xffffffffu && (uint32_t)(o >> 32) == a.lm.tgen[t]) v = a.c.trank[t];
+    if (t < a.lm.ntables && a.c.first[t] != 0xffffffffu && (uint32_t)(o >> 32) == a.lm.tgen[t]) v = a.c.trank[t] + a.tbase;
     out[j] = v;
 }
 
@@ -255,6 +260,95 @@ __global__ void __launch_bounds__(kBlock) k_snap_finish(LocalMaps lm, uint64_t T
     }
 }
 
+// ---- a sharded load's subset ("Sharded filters"): bitmaps over the snapshot's
+// compact ids, ranked by popcount ------------------------------------------------------------
+// Copies of one table (or tables sharing a page) hammer one word: look before the atomic, as
+// k_snap_pgfirst does (the word only gains bits; a stale read costs one atomic that changes nothing).
+__device__ __forceinline__ void mark_bit(uint32_t* bits, uint32_t id)
+{
+    uint32_t* w = bits + (id >> 5);
+    const uint32_t m = 1u << (id & 31u);
+    if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(w, m);
+}
+
+__device__ __forceinline__ bool bit_set(const uint32_t* bits, uint32_t id) { return (bits[id >> 5] >> (id & 31u)) & 1u; }
+
+__device__ __forceinline__ uint32_t bit_rank(const uint32_t* bits, const uint32_t* pre, uint32_t id)
+{
+    return pre[id >> 5] + (uint32_t)__popc(bits[id >> 5] & ((1u << (id & 31u)) - 1u));
+}
+
+// one lane per id (a particle's table): bit id of the bitmap of `limit` bits
+__global__ void __launch_bounds__(kBlock) k_snap_mark_bits(const uint32_t* __restrict__ ids, uint64_t n, uint32_t* bits, uint64_t limit)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = ids[i];
+    if (t < limit) mark_bit(bits, t);
+}
+
+// a wave per pool table [0, T): the pages of its window slots and its used trail entries
+__global__ void __launch_bounds__(kBlock) k_snap_mark_rows(SnapArgs a, uint32_t* bits, uint64_t limit)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); r < a.T; r += nw) {
+        const uint32_t* row = a.lm.slot + r * a.lm.S;
+        const uint32_t cnt = a.W + hw_of(row[a.toff - 1u]);
+        for (uint32_t s = lane; s < cnt && s < a.K; s += 64u) {
+            const uint32_t p = row_page(a, row, s);
+            if (p != DM_LM_NONE && p < limit) mark_bit(bits, p);
+        }
+    }
+}
+
+// pre[w] = popc(bits[w]), pre[words] = 0: the exclusive scan then leaves the total there
+__global__ void __launch_bounds__(kBlock) k_snap_popc(const uint32_t* __restrict__ bits, uint64_t words, uint32_t* __restrict__ pre)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (w > words) return;
+    pre[w] = w < words ? (uint32_t)__popc(bits[w]) : 0u;
+}
+
+__global__ void __launch_bounds__(kBlock) k_snap_rank_sid(uint32_t* sid, uint64_t n, SnapSubset s)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = sid[i];
+    if (t < s.tables) sid[i] = bit_rank(s.tbits, s.tpre, t);
+}
+
+// a wave per pool table [0, T): the snapshot's page ids of its row become this rank's
+__global__ void __launch_bounds__(kBlock) k_snap_renumber_tables(SnapArgs a, SnapSubset s)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); r < a.T; r += nw) {
+        uint32_t* row = a.lm.slot + r * a.lm.S;
+        const uint32_t hw = hw_of(row[a.toff - 1u]);
+        for (uint32_t q = lane; q < a.lm.S; q += 64u) {
+            const bool slot = q < a.W;
+            const bool trail = q >= a.toff && ((q - a.toff) & 3u) == 2u && ((q - a.toff) >> 2) < hw;
+            if (!slot && !trail) continue;
+            const uint32_t p = row[q];
+            if (p != DM_LM_NONE && p < s.pages) row[q] = bit_rank(s.pbits, s.ppre, p);
+        }
+    }
+}
+
+// owner words of pages [k0, k0 + cnt) of this rank: a table this rank holds by its local id,
+// any other table as none (nobody here writes the page in place)
+__global__ void __launch_bounds__(kBlock) k_snap_unpack_owner_subset(SnapArgs a, uint64_t k0, uint64_t cnt, SnapSubset s,
+                                                                    const uint32_t* __restrict__ in)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= cnt) return;
+    const uint32_t t = in[j];
+    uint64_t v = ~0ull;
+    if (t != DM_LM_NONE && t < s.tables && bit_set(s.tbits, t)) v = (uint64_t)bit_rank(s.tbits, s.tpre, t);   // generation 0
+    a.lm.owner[k0 + j] = v;
+}
+
 SnapArgs snap_args(const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t n, uint64_t T)
 {
     SnapArgs a;
@@ -312,11 +406,15 @@ extern "C" hipError_t eslam_launch_snap_census_pages(const LocalMaps* lm, const 
 }
 
 // what: 0 the particles' compact table ids, 1 table rows (rw words each), 2 owner words, 3 pages
+// tbase, pbase: added to every table and page id written (a sharded save: the ids of the ranks below; else 0)
 extern "C" hipError_t eslam_launch_snap_pack(int what, const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid, uint64_t T,
-                                             uint64_t k0, uint64_t cnt, uint32_t rw, void* out, hipStream_t stream)
+                                             uint32_t tbase, uint32_t pbase, uint64_t k0, uint64_t cnt, uint32_t rw, void* out,
+                                             hipStream_t stream)
 {
     if (!cnt) return hipSuccess;
-    const SnapArgs a = snap_args(lm, c, sid, 0, T);
+    SnapArgs a = snap_args(lm, c, sid, 0, T);
+    a.tbase = tbase;
+    a.pbase = pbase;
     if (what == 0) hipLaunchKernelGGL(k_snap_pack_sid, blocks_for(cnt), dim3(kBlock), 0, stream, a, k0, cnt, (uint32_t*)out);
     else if (what == 1) hipLaunchKernelGGL(k_snap_pack_tables, blocks_for(cnt * 64), dim3(kBlock), 0, stream, a, k0, cnt, rw, (uint32_t*)out);
     else if (what == 2) hipLaunchKernelGGL(k_snap_pack_owner, blocks_for(cnt), dim3(kBlock), 0, stream, a, k0, cnt, (uint32_t*)out);
@@ -341,5 +439,59 @@ extern "C" hipError_t eslam_launch_snap_finish(const LocalMaps* lm, uint64_t T, 
     if (lm->npages > items) items = lm->npages;
     const uint64_t want = (items + kBlock - 1) / kBlock;
     if (items) hipLaunchKernelGGL(k_snap_finish, dim3((uint32_t)(want < 65536 ? want : 65536)), dim3(kBlock), 0, stream, *lm, T, P, items);
+    return hipGetLastError();
+}
+
+// ---- a sharded load's subset ------------------------------------------------------------------
+namespace {
+inline dim3 waves_for(uint64_t rows)
+{
+    const uint64_t gm = (rows + kWaves - 1) / kWaves;
+    return dim3((uint32_t)(gm < 65536 ? gm : 65536));
+}
+}  // namespace
+
+// bit ids[i] of `bits` (bits bits, cleared by the caller), i < n
+extern "C" hipError_t eslam_launch_snap_mark_ids(const uint32_t* ids, uint64_t n, uint32_t* bits, uint64_t limit, hipStream_t stream)
+{
+    if (n) hipLaunchKernelGGL(k_snap_mark_bits, blocks_for(n), dim3(kBlock), 0, stream, ids, n, bits, limit);
+    return hipGetLastError();
+}
+
+// the bits of the pages that pool tables [0, T) name (rows as unpacked: the snapshot's page ids)
+extern "C" hipError_t eslam_launch_snap_mark_rows(const LocalMaps* lm, uint64_t T, uint32_t* bits, uint64_t limit, hipStream_t stream)
+{
+    const SnapArgs a = snap_args(lm, nullptr, nullptr, 0, T);
+    if (T) hipLaunchKernelGGL(k_snap_mark_rows, waves_for(T), dim3(kBlock), 0, stream, a, bits, limit);
+    return hipGetLastError();
+}
+
+// pre[0 .. words]: the exclusive prefix of the words' popcounts, pre[words] the number of set bits
+extern "C" hipError_t eslam_launch_snap_rank_bits(const uint32_t* bits, uint64_t words, uint32_t* pre, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_snap_popc, blocks_for(words + 1), dim3(kBlock), 0, stream, bits, words, pre);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : eslam_launch_scan_excl(pre, words + 1, stream);
+}
+
+extern "C" hipError_t eslam_launch_snap_rank_sid(uint32_t* sid, uint64_t n, const SnapSubset* s, hipStream_t stream)
+{
+    if (n) hipLaunchKernelGGL(k_snap_rank_sid, blocks_for(n), dim3(kBlock), 0, stream, sid, n, *s);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t eslam_launch_snap_renumber_tables(const LocalMaps* lm, uint64_t T, const SnapSubset* s, hipStream_t stream)
+{
+    const SnapArgs a = snap_args(lm, nullptr, nullptr, 0, T);
+    if (T) hipLaunchKernelGGL(k_snap_renumber_tables, waves_for(T), dim3(kBlock), 0, stream, a, *s);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t eslam_launch_snap_unpack_owner_subset(const LocalMaps* lm, uint64_t k0, uint64_t cnt, const SnapSubset* s,
+                                                            const void* in, hipStream_t stream)
+{
+    if (!cnt) return hipSuccess;
+    const SnapArgs a = snap_args(lm, nullptr, nullptr, 0, 0);
+    hipLaunchKernelGGL(k_snap_unpack_owner_subset, blocks_for(cnt), dim3(kBlock), 0, stream, a, k0, cnt, *s, (const uint32_t*)in);
     return hipGetLastError();
 }

@@ -351,6 +351,15 @@ SNAPSHOT_PROTOTYPES = {
     "eslam_gpu_load": [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SnapshotInfo)],
 }
 
+# eslam_pwrite_fn / eslam_pread_fn: (user, offset, data, bytes)
+PWRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
+PREAD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
+
+# the positional forms (one file written and read by offset; what a sharded filter saves through)
+SNAPSHOT_AT_PROTOTYPES = {
+    "eslam_gpu_save_at": [PWRITE_FN, C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfo)],
+    "eslam_gpu_load_at": [PREAD_FN, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(SnapshotInfo)],
+}
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)
 ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p,

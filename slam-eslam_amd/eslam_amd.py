@@ -116,7 +116,8 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_init_hash.argtypes = [vp, C.c_uint64]
     L.eslam_gpu_hash_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.eslam_gpu_hash_poses.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
-    for name, args in A.SNAPSHOT_PROTOTYPES.items():     # a library without them is an error at the call
+    # a library without them is an error at the call
+    for name, args in {**A.SNAPSHOT_PROTOTYPES, **A.SNAPSHOT_AT_PROTOTYPES}.items():
         if hasattr(L, name):
             getattr(L, name).argtypes = [vp] + args
     _lib = L
@@ -475,6 +476,73 @@ class GpuFilter:
             self._grid = None
             raise EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
         self._grid = _SnapshotGrid(head)     # the geometry get_map() reports
+        self.last_snapshot = info
+        return info
+
+    def save_state_at(self, path, chunk_bytes=0):
+        """eslam_gpu_save_at into the file at `path`, opened without truncation and written with
+        os.pwrite: on a sharded filter a collective, every rank writing its part of the one file.
+        After a successful save every rank sets the file's size to the blob's (info.bytes), so an
+        older, longer file at `path` is cut to it.  Returns the SnapshotInfo."""
+        info = A.SnapshotInfo()
+        failed = []
+        fd = os.open(path, os.O_WRONLY | os.O_CREAT, 0o644)
+
+        def pwrite(_user, offset, data, nbytes):
+            try:
+                b = C.string_at(data, nbytes)
+                done = 0
+                while done < nbytes:
+                    done += os.pwrite(fd, b[done:], offset + done)
+                return 0
+            except Exception as e:           # the C side reports ESLAM_ERR_COMM
+                failed.append(e)
+                return 1
+
+        try:
+            rc = self.L.eslam_gpu_save_at(self.h, A.PWRITE_FN(pwrite), None, chunk_bytes, C.byref(info))
+            if rc == 0:
+                os.ftruncate(fd, info.bytes)     # the file is the blob (any rank may do this, at any time)
+        finally:
+            os.close(fd)
+        if rc != 0:
+            e = EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+            e.__cause__ = failed[0] if failed else None
+            raise e
+        self.last_snapshot = info
+        return info
+
+    def load_state_at(self, path, chunk_bytes=0):
+        """eslam_gpu_load_at from the file at `path`, read with os.pread: on a sharded filter a
+        collective, every rank reading the shared parts and its own slice of the rest.  Returns
+        the SnapshotInfo."""
+        info = A.SnapshotInfo()
+        fd = os.open(path, os.O_RDONLY)
+        heads = []
+
+        def pread(_user, offset, data, nbytes):
+            try:
+                b = bytearray()
+                while len(b) < nbytes:
+                    part = os.pread(fd, nbytes - len(b), offset + len(b))
+                    if not part:
+                        return 1
+                    b += part
+                if offset == 0 and not heads:
+                    heads.append(bytes(b[:_SNAP_HEADER]))
+                C.memmove(data, bytes(b), nbytes)
+                return 0
+            except Exception:
+                return 1
+
+        try:
+            rc = self.L.eslam_gpu_load_at(self.h, A.PREAD_FN(pread), None, os.fstat(fd).st_size, chunk_bytes, C.byref(info))
+        finally:
+            os.close(fd)
+        if rc != 0:
+            self._grid = None
+            raise EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+        self._grid = _SnapshotGrid(heads[0])
         self.last_snapshot = info
         return info
 

@@ -15,6 +15,13 @@ first, then --reps repeats, median and range):
                 per particle (the only way out the library had before), extrapolated
 The pack kernels' and the copies' own times come from a run of this tool under
 `rocprofv3 --kernel-trace --memory-copy-trace --stats` (k_snap_* kernels), not from this clock.
+With --at it measures the positional forms instead, on the same state and in one process:
+  save_stream_ms / save_at_ms   both into discarding callbacks, alternating
+  load_stream_ms / load_at_ms   the whole blob from memory into a second context (the full range)
+  subset_load_ms                eslam_gpu_load_at of the first half of the particles: a context that is
+                                rank 0 of a 2-rank layout whose peer only answers the all_gathers, with
+                                the time spent inside the read callbacks and their count; to be set
+                                against load_at_ms, the same blob loaded whole
 Prints one JSON line; needs a GPU (no fallback)."""
 import argparse
 import ctypes as C
@@ -115,6 +122,84 @@ def measure(n, args):
     return res
 
 
+class HalfComm:
+    """rank 0 of 2; the absent peer answers every all_gather with zeros (no error, nothing to add)"""
+    rank, nranks, device_memory, error = 0, 2, False, None
+
+    def __init__(self):
+        def allgather(user, send, recv, n, stream):
+            C.memmove(recv, send, n)
+            C.memset(recv + n, 0, n)
+            return 0
+
+        self._ag = A.ALLGATHER_FN(allgather)
+        self._a2a = A.ALLTOALLV_FN(lambda user, send, sb, recv, rb, stream: 1)
+        self.struct = A.Comm(None, 0, 2, 0, 0, self._ag, self._a2a)
+
+
+def measure_at(n, args):
+    import eslam_dist
+    cfg, f = run_filter(n, args.steps, args.map_cells, args.map_pages)
+    chunk = args.chunk_mib << 20
+    info = f.snapshot_info()
+    res = {"particles": n, "steps": args.steps, "chunk_bytes": chunk, "bytes": info.bytes, "tables": info.tables, "pages": info.pages}
+    sinfo = A.SnapshotInfo()
+    sink = A.WRITE_FN(lambda user, data, nbytes: 0)
+    psink = A.PWRITE_FN(lambda user, off, data, nbytes: 0)
+
+    def save_stream():
+        assert f.L.eslam_gpu_save_stream(f.h, sink, None, chunk, C.byref(sinfo)) == 0
+
+    def save_at():
+        assert f.L.eslam_gpu_save_at(f.h, psink, None, chunk, C.byref(sinfo)) == 0
+
+    # alternating, so that neither form has the warmer machine
+    a, b = [], []
+    save_stream()
+    save_at()
+    for _ in range(args.reps):
+        for fn, out in ((save_stream, a), (save_at, b)):
+            t = time.perf_counter()
+            fn()
+            out.append(1e3 * (time.perf_counter() - t))
+    res["save_stream_ms"], res["save_at_ms"] = stats(a), stats(b)
+    blob = f.save_state(chunk_bytes=chunk)
+    f.close()
+    base = blob.ctypes.data
+    spent = [0.0, 0]
+
+    def pread(user, off, data, nbytes):
+        t = time.perf_counter()
+        C.memmove(data, base + off, nbytes)
+        spent[0] += time.perf_counter() - t
+        spent[1] += 1
+        return 0
+
+    src = A.PREAD_FN(pread)
+    reps = args.reps
+    g = eslam_amd.GpuFilter(cfg, device=0)
+
+    def load_at(h=None):
+        assert g.L.eslam_gpu_load_at(h or g.h, src, None, blob.shape[0], chunk, C.byref(sinfo)) == 0
+
+    res["load_stream_ms"] = timed(lambda: g.load_state(blob, chunk_bytes=chunk), reps)
+    res["load_at_ms"] = timed(load_at, reps)
+    g.close()
+    # the subset path: the first half of the particles
+    hcfg = S.bench_config(A.default_config(), n)
+    hcfg.flags, hcfg.local_map_pages = cfg.flags, cfg.local_map_pages
+    h = eslam_dist.ShardedGpuFilter(hcfg, n, HalfComm(), device=0)
+    load_at(h.f.h)                           # warm-up
+    spent[0], spent[1] = 0.0, 0
+    res["subset_load_ms"] = timed(lambda: load_at(h.f.h), reps)
+    res["subset"] = {"particles": h.n_local, "read_callbacks_per_load": spent[1] // (reps + 1),
+                     "ms_in_read_callbacks_per_load": round(1e3 * spent[0] / (reps + 1), 3),
+                     "kernel_split": "not measured by this clock (rocprofv3 --kernel-trace: k_snap_mark_*, k_snap_popc, k_snap_rank_sid, "
+                                     "k_snap_renumber_tables)"}
+    h.f.close()
+    return res
+
+
 def baseline(args):
     n = 65536
     cfg, f = run_filter(n, args.steps, args.map_cells, args.map_pages)
@@ -139,8 +224,12 @@ def main():
     ap.add_argument("--no-load", dest="load", action="store_false")
     ap.add_argument("--baseline-particles", type=int, default=256, help="0: skip the get_particle_map baseline")
     ap.add_argument("--out", default=None, help="also write the JSON here")
+    ap.add_argument("--at", action="store_true", help="the positional forms (eslam_gpu_save_at / eslam_gpu_load_at) and the subset load")
     args = ap.parse_args()
-    out = {"tool": "bench_snapshot", "build_id": eslam_amd.build_id()[:16], "sizes": [measure(n, args) for n in args.particles]}
+    if args.at:
+        args.baseline_particles = 0
+    out = {"tool": "bench_snapshot", "build_id": eslam_amd.build_id()[:16],
+           "sizes": [(measure_at if args.at else measure)(n, args) for n in args.particles]}
     if args.baseline_particles:
         out["get_particle_map_baseline"] = b = baseline(args)
         for r in out["sizes"]:
