@@ -940,15 +940,23 @@ DM_CONST double dm_bm_sc_tab[256][2] = {
  * lo, log1p(r) = r + r^2 P(r) (Taylor to r^7).  The interval holding 1 has c = 1 (L = 0,
  * r = z - 1 exact), so log u keeps its relative accuracy as u -> 1.  About 1 ulp; 21 VALU
  * instructions on gfx950 against 35 for dm_log_pos (no division).                          */
-DM_FN double dm_log_bm(double u)
+/* the row of dm_bm_log_tab that dm_log_bm(u) reads */
+DM_FN uint32_t dm_log_bm_row(double u)
+{
+    const int32_t t = (int32_t)((uint32_t)(dm_bits(u) >> 32) - 0x3fe80000u);   /* 0x3fe8: 0.75 */
+    return ((uint32_t)t >> 13) & 127u;
+}
+
+/* dm_log_bm with its table row e = dm_bm_log_tab[dm_log_bm_row(u)] handed in (e0..e2 = e[0..2]):
+ * a caller may load the row early and evaluate later; the same operations on the same values */
+DM_FN double dm_log_bm_e(double u, double e0, double e1, double e2)
 {
     const uint64_t b = dm_bits(u);
     const uint32_t hi = (uint32_t)(b >> 32);
     const int32_t t = (int32_t)(hi - 0x3fe80000u);              /* 0x3fe8: 0.75 */
     const int32_t k = t >> 20;                                   /* arithmetic */
-    const uint32_t i = ((uint32_t)t >> 13) & 127u;
     const double z = dm_from_bits(((uint64_t)(hi - ((uint32_t)t & 0xfff00000u)) << 32) | (b & 0xffffffffull));
-    const double* e = dm_bm_log_tab[i];
+    const double e[3] = {e0, e1, e2};
     const double r = dm_fma(z, e[0], -1.0);
     double p = dm_fmak(r, 1.0 / 7.0, -1.0 / 6.0);
     p = dm_fmak(p, r, 0.2);
@@ -960,6 +968,12 @@ DM_FN double dm_log_bm(double u)
     const double h = kd * DM_LN2_HI + e[1];
     const double l = kd * DM_LN2_LO + e[2];
     return h + (l1p + l);
+}
+
+DM_FN double dm_log_bm(double u)
+{
+    const double* e = dm_bm_log_tab[dm_log_bm_row(u)];
+    return dm_log_bm_e(u, e[0], e[1], e[2]);
 }
 
 /* sin and cos of 2 pi (b + 1/2) 2^-32 (= dm_sincos2pi(dm_u32(b)) to about 1 ulp): the
@@ -1249,15 +1263,21 @@ DM_FN float dm_fmaf(float a, float b, float c) { return __builtin_fmaf(a, b, c);
  * Taylor series (sin to delta^3, cos to delta^4: remainders below 2^-33 relative), combined
  * by the angle-sum formulas.  About 1 ulp of fp32; every operation is an IEEE fp32 add, mul or
  * fma, so the host and the device agree bit for bit.                                       */
-DM_FN void dm_sincos2pi32f(uint32_t b, float* s, float* c)
+/* with the table row {e0, e1} = dm_bm_sc_tab32[b >> 24] handed in (a caller may load it early) */
+DM_FN void dm_sincos2pi32f_e(uint32_t b, float e0, float e1, float* s, float* c)
 {
-    const float* e = dm_bm_sc_tab32[b >> 24];
     const float d = dm_fmaf((float)(b & 0xffffffu), DM_BM_DELTA_F, 0.5f * DM_BM_DELTA_F);
     const float z = d * d;
     const float sd = dm_fmaf(d * z, -1.0f / 6.0f, d);
     const float cd = dm_fmaf(z, dm_fmaf(z, 1.0f / 24.0f, -0.5f), 1.0f);
-    *s = dm_fmaf(e[0], cd, e[1] * sd);
-    *c = dm_fmaf(e[1], cd, -(e[0] * sd));
+    *s = dm_fmaf(e0, cd, e1 * sd);
+    *c = dm_fmaf(e1, cd, -(e0 * sd));
+}
+
+DM_FN void dm_sincos2pi32f(uint32_t b, float* s, float* c)
+{
+    const float* e = dm_bm_sc_tab32[b >> 24];
+    dm_sincos2pi32f_e(b, e[0], e[1], s, c);
 }
 
 /* sqrt(x) correctly rounded in fp32 for a positive normal x: on the device the compiler's own
@@ -1284,14 +1304,37 @@ DM_FN float dm_sqrtf_pos(float x)
  * angle's sin / cos in fp32; each normal is the exact fp64 product of the two fp32 factors
  * (24 + 24 bits).  Noise draws need no more than fp32's 2^-24 relative resolution (the
  * reference's own uniforms carry 31 bits), and fp32 arithmetic issues at twice the fp64 rate. */
-DM_FN void dm_box_muller32(uint32_t a, uint32_t b, double* z0, double* z1)
+/* The two table rows of one dm_box_muller32(a, b).  dm_box_muller32 = dm_bm_rows, then
+ * dm_box_muller32_e: a kernel may put other memory traffic between the two, so that the
+ * arithmetic waits for these small loads only.                                          */
+typedef struct {
+    double l0, l1, l2;                   /* dm_bm_log_tab[dm_log_bm_row(dm_u32(a))][0..2] */
+    float s, c;                          /* dm_bm_sc_tab32[b >> 24] */
+} dm_bm_rows_t;
+
+DM_FN dm_bm_rows_t dm_bm_rows(uint32_t a, uint32_t b)
+{
+    const double* l = dm_bm_log_tab[dm_log_bm_row(dm_u32(a))];
+    const float* e = dm_bm_sc_tab32[b >> 24];
+    dm_bm_rows_t t;
+    t.l0 = l[0]; t.l1 = l[1]; t.l2 = l[2];
+    t.s = e[0]; t.c = e[1];
+    return t;
+}
+
+DM_FN void dm_box_muller32_e(uint32_t a, uint32_t b, dm_bm_rows_t t, double* z0, double* z1)
 {
     /* -2 log u in [4.6e-10, 45.8] for u in [2^-33, 1): positive normal in fp32 */
-    const float r = dm_sqrtf_pos((float)(-2.0 * dm_log_bm(dm_u32(a))));
+    const float r = dm_sqrtf_pos((float)(-2.0 * dm_log_bm_e(dm_u32(a), t.l0, t.l1, t.l2)));
     float s, c;
-    dm_sincos2pi32f(b, &s, &c);
+    dm_sincos2pi32f_e(b, t.s, t.c, &s, &c);
     *z0 = (double)r * (double)c;
     *z1 = (double)r * (double)s;
+}
+
+DM_FN void dm_box_muller32(uint32_t a, uint32_t b, double* z0, double* z1)
+{
+    dm_box_muller32_e(a, b, dm_bm_rows(a, b), z0, z1);
 }
 
 /* RNG stream identifiers (Philox counter word 3, bits 24..31) */

@@ -32,6 +32,15 @@ constexpr int kStatsLds = 2048;          // bytes of the statistics scratch at t
 // granules (inferred, r04i): K1 blocks of 32 736 B ran four per CU (each took 33 280 of the
 // 160 KB), blocks of 31 776 B (32 000 allocated) run five: K1 180 -> 167 us at 4M
 constexpr int kWindowLds = ESLAM_WINDOW_LDS;
+#ifndef ESLAM_K1_BM_LDS                  // experiment builds may leave the tables in global memory
+#define ESLAM_K1_BM_LDS 1
+#endif
+// K1 stages the two Box-Muller tables (dm_bm_log_tab 4 KB, dm_bm_sc_tab32 2 KB) in the last
+// kBmLds bytes of the window's LDS when the staged window leaves them free (the bench's cloud
+// needs about a third of the window), and reads them from global memory otherwise: no byte of
+// LDS more, and the same table values either way
+constexpr int kBmLds = 6144;
+static_assert(kBmLds <= kWindowLds, "the tables lie inside the window's LDS");
 #ifndef ESLAM_K1_ATTR                    // experiment builds may set an occupancy attribute on K1
 #define ESLAM_K1_ATTR
 #endif

@@ -190,6 +190,8 @@ __device__ uint32_t g_stamps_grid[3];    // gridDim.x of the last stamped K1 / K
 // v_readlane (a VALU instruction) on every row.  A volatile asm load + wait cannot be
 // hoisted, so each value occupies SGPRs only where it is used; the scalar cache serves the
 // repeats.  Outputs are early-clobber: the loads are in flight while the address is live.
+// Blocks that are used together are loaded as one group with one wait (below), and a field is
+// fetched once per particle row: 9 waits per row of the bench instantiation instead of 22.
 // ---------------------------------------------------------------------------------------
 typedef uint32_t su2 __attribute__((ext_vector_type(2)));
 typedef uint32_t su4 __attribute__((ext_vector_type(4)));
@@ -224,12 +226,31 @@ __device__ __forceinline__ su16 kl16(uint32_t off)
     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(kseg()), "s"(off));
     return r;
 }
-// two blocks, one wait
-__device__ __forceinline__ void kl8_2(uint32_t off_a, uint32_t off_b, su8& a, su2& b)
-{
-    asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx2 %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(a), "=&s"(b) : "s"(kseg()), "s"(off_a), "s"(off_b));
-}
+// Groups: the blocks of a group are requested together and waited for once, so a wave parks
+// once per group and not once per block (scalar loads return out of order: the only wait there
+// is is lgkmcnt(0)).  Requests and wait stand in one asm statement.  Split in two statements
+// (request now, wait in front of the first use, the blocks passed through the wait as "+s"
+// operands) the compiler is free to copy a block's registers between the two, before the
+// data has arrived: it did (DESIGN.md 4, K1's waits).
+#define ESLAM_KL_GROUP2(name, WA, WB) \
+    __device__ __forceinline__ void name(su##WA& a, uint32_t off_a, su##WB& b, uint32_t off_b) \
+    { \
+        asm volatile("s_load_dwordx" #WA " %0, %2, %3\n\ts_load_dwordx" #WB " %1, %2, %4\n\ts_waitcnt lgkmcnt(0)" \
+                     : "=&s"(a), "=&s"(b) : "s"(kseg()), "s"(off_a), "s"(off_b)); \
+    }
+#define ESLAM_KL_GROUP3(name, WA, WB, WC) \
+    __device__ __forceinline__ void name(su##WA& a, uint32_t off_a, su##WB& b, uint32_t off_b, su##WC& c, uint32_t off_c) \
+    { \
+        asm volatile("s_load_dwordx" #WA " %0, %3, %4\n\ts_load_dwordx" #WB " %1, %3, %5\n\ts_load_dwordx" #WC \
+                     " %2, %3, %6\n\ts_waitcnt lgkmcnt(0)" \
+                     : "=&s"(a), "=&s"(b), "=&s"(c) : "s"(kseg()), "s"(off_a), "s"(off_b), "s"(off_c)); \
+    }
+ESLAM_KL_GROUP2(kl8_2, 8, 2)
+ESLAM_KL_GROUP2(kl8_4, 8, 4)
+ESLAM_KL_GROUP2(kl16_2, 16, 2)
+ESLAM_KL_GROUP3(kl8_2_8, 8, 2, 8)
+ESLAM_KL_GROUP3(kl8_2_16, 8, 2, 16)
+ESLAM_KL_GROUP3(kl16_8_4, 16, 8, 4)
 template <class V> __device__ __forceinline__ uint64_t kq(const V& r, int k)
 {
     return (uint64_t)r[2 * k] | ((uint64_t)r[2 * k + 1] << 32);
@@ -245,12 +266,12 @@ struct StatePtrs {
     gmem<double> *x, *y, *th, *z, *zs, *w, *mprob;
     gmem<uint8_t>* flags;
 };
-__device__ __forceinline__ StatePtrs kstate(uint32_t off)
+__device__ __forceinline__ StatePtrs state_ptrs(const su16& r)
 {
-    const su16 r = kl16(off);
     return StatePtrs{kp<double>(r, 0), kp<double>(r, 1), kp<double>(r, 2), kp<double>(r, 3),
                      kp<double>(r, 4), kp<double>(r, 5), kp<double>(r, 6), kp<uint8_t>(r, 7)};
 }
+__device__ __forceinline__ StatePtrs kstate(uint32_t off) { return state_ptrs(kl16(off)); }
 
 static_assert(offsetof(StepParams, mu) == 24 && offsetof(StepParams, L22) == 88 && offsetof(StepParams, z_delta) == 120 &&
                   offsetof(StepParams, me2) == 136 && offsetof(StepParams, use_shape) == 168,
@@ -427,10 +448,11 @@ __device__ __forceinline__ uint32_t store_sid(uint32_t sid)
 template <bool DELTA = false, bool DEFER = false>
 __device__ __forceinline__ bool get_patch(const Window& win, double px, double py, double pz, double qv, double& mean,
                                           double& stdev, uint32_t sid = 0, uint32_t* dm = nullptr, uint32_t* dn = nullptr,
-                                          double* dlz = nullptr)
+                                          double* dlz = nullptr, const su16* hin = nullptr)
 {
     if constexpr (DEFER) *dm = 0xffffffffu;
-    const su16 h = kl16(KOFF(map));
+    // hin: the lookup header (the first 64 bytes of MapView) where the caller has it already
+    const su16 h = hin ? *hin : kl16(KOFF(map));
     const uint32_t width = h[12], hcells = h[13], ident = h[14], has_height = h[15];
     double lx = px, ly = py, lz = pz;    // an identity global2local is applied as the identity
     if (!ident) {
@@ -654,8 +676,10 @@ constexpr int kK1LookupBatch = ESLAM_K1_LB;
 
 template <int MAXP, bool BATCH, bool DELTA = false, bool UNG = false>
 __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, double s, double r22, double x, double y,
-                                                  double z, double meas_var, uint32_t sid)
+                                                  double z, double meas_var, uint32_t sid, const su8& wp, const su4& wq)
 {
+    // wp: me2, radius, corr, min_contacts; wq: use_shape, m, eval_mask, end_mask (StepParams,
+    // loaded by the caller once per particle row)
     CMResult r;
     // pushed contact points.  BATCH: slot = index of the contact that closed the group, so
     // every write has a static index; the slots are summed in index order = push order.
@@ -668,8 +692,6 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
     double contact_ratio = 0, pose_var_avg = 0, posevar = 0;
     double pzd = 0, pzv = 0;
     const double qv = meas_var;
-    const su8 wp = kl8(KOFF(p.me2));          // me2, radius, corr, min_contacts
-    const su4 wq = kl4(KOFF(p.use_shape));    // use_shape, m, eval_mask, end_mask
     const double radius = kd(wp, 1), corr = kd(wp, 2);
     const uint32_t m = wq[1], eval_mask = wq[2], end_mask = wq[3];
 
@@ -735,18 +757,19 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
     };
     // pose * p with pose = Translation(x, y, z) * AngleAxis(theta, UnitZ); the zero products
     // of the affine multiply are per-step constants, and "- 0.0" is exact
-    auto world = [&](uint32_t i, double& wx, double& wy, double& wz) {
+    // the contact and the map's lookup header (for the lookup that follows) in one group
+    auto world = [&](uint32_t i, double& wx, double& wy, double& wz, su16& h) {
         su8 c;
         su2 cpz;
         const uint32_t off = KOFF(p.c) + i * (uint32_t)sizeof(ContactC);
-        kl8_2(off, off + (uint32_t)offsetof(ContactC, pz), c, cpz);   // px, py, zp, zz | pz
+        kl8_2_16(c, off, cpz, off + (uint32_t)offsetof(ContactC, pz), h, KOFF(map));   // px, py, zp, zz | pz | header
         const double px = kd(c, 0), py = kd(c, 1), zp = kd(c, 2), zz = kd(c, 3), pz = kd(cpz, 0);
         wx = ((co * px + (-s) * py) + zp) + x;
         wy = ((s * px + co * py) + zp) + y;
         wz = ((zz + r22 * pz) + z) - radius;
     };
-    auto lookup = [&](double wx, double wy, double wz, double& mean, double& stdev) -> bool {
-        return get_patch<DELTA>(win, wx, wy, wz, qv, mean, stdev, sid);
+    auto lookup = [&](const su16& h, double wx, double wy, double wz, double& mean, double& stdev) -> bool {
+        return get_patch<DELTA>(win, wx, wy, wz, qv, mean, stdev, sid, nullptr, nullptr, nullptr, &h);
     };
 
     if constexpr (BATCH && UNG && kK1LookupBatch < MAXP) {
@@ -762,8 +785,9 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
                 fnd[q] = false; mn[q] = 0.0; sd[q] = 0.0; wzs[q] = 0.0;
                 if ((uint32_t)i < m) {
                     double wx, wy;
-                    world((uint32_t)i, wx, wy, wzs[q]);
-                    if ((eval_mask >> i) & 1u) fnd[q] = lookup(wx, wy, wzs[q], mn[q], sd[q]);
+                    su16 h;
+                    world((uint32_t)i, wx, wy, wzs[q], h);
+                    if ((eval_mask >> i) & 1u) fnd[q] = lookup(h, wx, wy, wzs[q], mn[q], sd[q]);
                 }
             }
 #pragma unroll
@@ -808,9 +832,10 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
                     fnd[i] = false; mn[i] = 0.0; sd[i] = 0.0; wzs[i] = 0.0; dm[i] = 0xffffffffu; dn[i] = 0u; dlz[i] = 0.0;
                     if ((uint32_t)i < m) {
                         double wx, wy;
-                        world((uint32_t)i, wx, wy, wzs[i]);
+                        su16 h;
+                        world((uint32_t)i, wx, wy, wzs[i], h);
                         if ((eval_mask >> i) & 1u)
-                            fnd[i] = get_patch<true, true>(win, wx, wy, wzs[i], qv, mn[i], sd[i], sid, &dm[i], &dn[i], &dlz[i]);
+                            fnd[i] = get_patch<true, true>(win, wx, wy, wzs[i], qv, mn[i], sd[i], sid, &dm[i], &dn[i], &dlz[i], &h);
                     }
                 }
                 store_patches<MAXP>(sid, dm, dn, dlz, qv, fnd, mn, sd);
@@ -820,8 +845,9 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
                     fnd[i] = false; mn[i] = 0.0; sd[i] = 0.0; wzs[i] = 0.0;
                     if ((uint32_t)i < m) {
                         double wx, wy;
-                        world((uint32_t)i, wx, wy, wzs[i]);
-                        if ((eval_mask >> i) & 1u) fnd[i] = lookup(wx, wy, wzs[i], mn[i], sd[i]);
+                        su16 h;
+                        world((uint32_t)i, wx, wy, wzs[i], h);
+                        if ((eval_mask >> i) & 1u) fnd[i] = lookup(h, wx, wy, wzs[i], mn[i], sd[i]);
                     }
                 }
             }
@@ -831,8 +857,9 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
                 fnd[i] = false; mn[i] = 0.0; sd[i] = 0.0; wzs[i] = 0.0;
                 if ((uint32_t)i < m) {
                     double wx, wy;
-                    world((uint32_t)i, wx, wy, wzs[i]);
-                    if ((eval_mask >> i) & 1u) fnd[i] = lookup(wx, wy, wzs[i], mn[i], sd[i]);
+                    su16 h;
+                    world((uint32_t)i, wx, wy, wzs[i], h);
+                    if ((eval_mask >> i) & 1u) fnd[i] = lookup(h, wx, wy, wzs[i], mn[i], sd[i]);
                 }
             }
         }
@@ -877,9 +904,10 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
     } else {
         for (uint32_t i = 0; i < m; ++i) {
             double wx, wy, wz, mean = 0.0, stdev = 0.0;
-            world(i, wx, wy, wz);
+            su16 h;
+            world(i, wx, wy, wz, h);
             bool found = false;
-            if (group_valid && ((eval_mask >> i) & 1u)) found = lookup(wx, wy, wz, mean, stdev);
+            if (group_valid && ((eval_mask >> i) & 1u)) found = lookup(h, wx, wy, wz, mean, stdev);
             contact(i, found, mean, stdev, wz);
         }
     }
@@ -915,7 +943,7 @@ __device__ __forceinline__ CMResult evaluate_pose(const Window& win, double co, 
             }
         }
         r.s2 = s2;
-        const uint32_t use_shape = kl2(KOFF(p.use_shape))[0];
+        const uint32_t use_shape = wq[0];
         const double pz = use_shape ? dm_exp(-0.5 * s2) : 1.0;
         r.weight = pz;
         r.zdelta = -delta;
@@ -988,6 +1016,26 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
     Window win;
     win.on = 0;
     if (WEIGHT) win = stage_window(a.map, a.p, ctl, 6.0 * tf, smem + kStatsLds);
+    // the Box-Muller tables in LDS, behind the staged window's cells where those leave the
+    // room (kBmLds at the end of the launch's LDS; a launch without the weighting has no
+    // window).  Their reads then count in lgkmcnt and never queue behind the state gather's
+    // loads; a block whose window is larger reads the tables from global memory.
+    unsigned char* bm_tab = smem + kStatsLds + (WEIGHT ? kWindowLds - kBmLds : 0);
+    uint32_t bm_lds = 0;                     // block-uniform (a scalar)
+    if (ESLAM_K1_BM_LDS && PROJECT) {
+        static_assert(sizeof(dm_bm_log_tab) == 4096 && sizeof(dm_bm_sc_tab32) == 2048 && kBlock == 256, "one piece per thread");
+        int room = 1;
+        if (win.on) {
+            const WinBounds wb = win_bounds();   // written by stage_window before its barrier
+            room = (wb.n1 - wb.n0) * wb.cols * (int)sizeof(WinCell) <= kWindowLds - kBmLds;
+        }
+        bm_lds = (uint32_t)__builtin_amdgcn_readfirstlane(room);
+        if (bm_lds) {
+            reinterpret_cast<uint4*>(bm_tab)[threadIdx.x] = reinterpret_cast<const uint4*>(&dm_bm_log_tab[0][0])[threadIdx.x];
+            reinterpret_cast<uint2*>(bm_tab + 4096)[threadIdx.x] = reinterpret_cast<const uint2*>(&dm_bm_sc_tab32[0][0])[threadIdx.x];
+        }
+        __syncthreads();
+    }
     ESLAM_STAMP(g_stamps_k1, 1);
 
     // order-free per-lane state, kept across chunks
@@ -1041,21 +1089,69 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
         const gmem<const Rec>* rc = nullptr;
         uint32_t rec_anc = 0;
         bool clr = false;                        // this output's segment mark is set
+        // The row's memory operations are ordered so that each wait covers only what its
+        // consumer needs (vmcnt retires loads in issue order): the marks and the carry are
+        // requested first and the draws, which need only the particle's index, are computed
+        // while they fly; the Box-Muller table rows come from LDS (bm_lds) or are requested
+        // before the gathered state, so the Box-Muller arithmetic waits for the tables alone
+        // and runs under the state's latency; the state is waited for where theta is first
+        // used.  The same operations on the same operands as in source order: the same bits.
+        dm_philox_ctr d0 = {}, d1 = {};
+        dm_bm_rows_t t0 = {}, t1 = {};
+        su8 key = {};                            // seed, proj_event, gbase
+        auto draws = [&]() {
+            if (!PROJECT) return;
+            const uint64_t gi = kq(key, 2) + i;
+            // draw layout (DESIGN.md 2): call 0 -> two Box-Muller pairs (z0, z1), (z2, sn0);
+            // call 1 -> slip test + slip factor, spread pair (sn1, sn2).  A lane past n draws
+            // too (a pure function of its index) and uses nothing of it.
+            d0 = dm_draw(kq(key, 0), DM_STREAM_PROJECT, kq(key, 1), gi, 0);
+            d1 = dm_draw(kq(key, 0), DM_STREAM_PROJECT, kq(key, 1), gi, 1);
+            // the words are used under i < n only, where the compiler would sink the whole
+            // computation, behind the wait for the marks: this keeps it here
+            asm volatile("" ::"v"(d0.v[0]), "v"(d0.v[1]), "v"(d0.v[2]), "v"(d0.v[3]), "v"(d1.v[0]), "v"(d1.v[1]),
+                         "v"(d1.v[2]), "v"(d1.v[3]));
+        };
         if (gath) {
-            const su8 g = kl8(KOFF(gv));              // marks, row_first, anc, recs
-            const su2 gf = kl2(KOFF(gv.record));      // record, multi
-            gmem<uint32_t>* marks = kp<uint32_t>(g, 0);
-            // expand the segment marks of this row: inclusive max-scan + the row carry.  Both
-            // loads are issued together; the mark is cleared with the row's other stores at its
-            // end (vmcnt counts stores too: a store here would add its round trip to the wait
-            // before the state loads)
+            su8 g;                                    // marks, row_first, anc, recs
+            su2 gf;                                   // record, multi
+            if constexpr (PROJECT) kl8_2_8(g, KOFF(gv), gf, KOFF(gv.record), key, KOFF(p.seed));
+            else kl8_2(g, KOFF(gv), gf, KOFF(gv.record));
+            // a lane past n (the last row only) reads the last particle's mark and drops it: the
+            // load stands in no branch, so nothing waits for it before the draws
             const uint32_t carry = kp<const uint32_t>(g, 1)[row0 / kRow] + 1u;
-            uint32_t m = 0;
-            if (i < n) { m = marks[i]; clr = m != 0; }
+            uint32_t m = kp<uint32_t>(g, 0)[i < n ? i : n - 1];
+            draws();
+            // expand the segment marks of this row: inclusive max-scan + the row carry.  The
+            // mark is cleared with the row's other stores at its end (vmcnt counts stores too: a
+            // store here would add its round trip to the wait before the state loads)
+            m = i < n ? m : 0u;
+            clr = m != 0;
             m = wave_incl_max_u32(m);
             m = m > carry ? m : carry;
             src = decode_source(m - 1u, gf[1], kp<const Rec>(g, 3), &rc);
             rec_anc = gf[0];
+        } else {
+            if constexpr (PROJECT) key = kl8(KOFF(p.seed));
+            draws();
+        }
+        if (PROJECT) {
+            if (bm_lds) {
+                auto rows = [&](uint32_t wa, uint32_t wb) {
+                    const double* l = reinterpret_cast<const double*>(bm_tab) + 4 * dm_log_bm_row(dm_u32(wa));
+                    const float* e = reinterpret_cast<const float*>(bm_tab + 4096) + 2 * (wb >> 24);
+                    dm_bm_rows_t t;
+                    t.l0 = l[0]; t.l1 = l[1]; t.l2 = l[2];
+                    t.s = e[0]; t.c = e[1];
+                    return t;
+                };
+                t0 = rows(d0.v[0], d0.v[1]);
+                t1 = rows(d0.v[2], d0.v[3]);
+            } else {
+                t0 = dm_bm_rows(d0.v[0], d0.v[1]);
+                t1 = dm_bm_rows(d0.v[2], d0.v[3]);
+            }
+            __builtin_amdgcn_sched_barrier(0);       // the table loads stay in front of the state's
         }
         // lanes past n (only in the last row of the last chunk) compute nothing but take part
         // in the row's bucket walk, so the walk's state stays wave-uniform (scalar)
@@ -1083,22 +1179,26 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
         double mprob = 0.0;
         uint32_t flags = 0;
         if (PROJECT) {
-            const su8 key = kl8(KOFF(p.seed));       // seed, proj_event, gbase
-            const uint64_t gi = kq(key, 2) + i;
-            // draw layout (DESIGN.md 2): call 0 -> two Box-Muller pairs (z0, z1), (z2, sn0);
-            // call 1 -> slip test + slip factor, spread pair (sn1, sn2)
-            const dm_philox_ctr d0 = dm_draw(kq(key, 0), DM_STREAM_PROJECT, kq(key, 1), gi, 0);
-            const dm_philox_ctr d1 = dm_draw(kq(key, 0), DM_STREAM_PROJECT, kq(key, 1), gi, 1);
+            // the sampler's and the z motion's arguments in one group, waited for while the
+            // table rows and the state are in flight
+            su16 P;                                  // mu0 mu1 mu2 L00 L10 L11 L20 L21
+            su8 Q;                                   // L22 slip_factor yaw max_yaw_dev
+            su4 Z;                                   // z_delta z_var
+            kl16_8_4(P, KOFF(p.mu), Q, KOFF(p.L22), Z, KOFF(p.z_delta));
             double z0, z1, z2, sn0;
-            dm_box_muller32(d0.v[0], d0.v[1], &z0, &z1);
-            dm_box_muller32(d0.v[2], d0.v[3], &z2, &sn0);
+            dm_box_muller32_e(d0.v[0], d0.v[1], t0, &z0, &z1);
+            dm_box_muller32_e(d0.v[2], d0.v[3], t1, &z2, &sn0);
             // odometry.getPoseDeltaSample2D() = mu + L z
-            const su16 P = kl16(KOFF(p.mu));         // mu0 mu1 mu2 L00 L10 L11 L20 L21
-            const su8 Q = kl8(KOFF(p.L22));          // L22 slip_factor yaw max_yaw_dev
             const double dx = kd(P, 0) + kd(P, 3) * z0;
             double dy = kd(P, 1) + (kd(P, 4) * z0 + kd(P, 5) * z1);
             const double dth = kd(P, 2) + ((kd(P, 6) * z0 + kd(P, 7) * z1) + kd(Q, 0) * z2);
             if (dm_u32(d1.v[0]) < kd(Q, 1)) dy *= dm_u32(d1.v[1]);
+            // the first use of the gathered state.  The pose delta is complete in front of it (the
+            // compiler would sink the Box-Muller arithmetic behind the wait for the state, next
+            // to its uses), and nothing of the state moves up into that arithmetic, which would
+            // bring the wait with it
+            asm volatile("" ::"v"(dx), "v"(dy), "v"(dth));
+            __builtin_amdgcn_sched_barrier(0);
             double s, co;
             dm_sincos(th, &s, &co);
             x += co * dx - s * dy;
@@ -1107,7 +1207,6 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
             if (kd(Q, 3) > 0.0) {
                 if (dm_fabs(th - kd(Q, 2)) > kd(Q, 3)) w *= 0.7;
             }
-            const su4 Z = kl4(KOFF(p.z_delta));      // z_delta z_var
             z += kd(Z, 0);
             zs = dm_sqrt_fast(zs * zs + kd(Z, 1));
             if (do_spread) {
@@ -1122,14 +1221,18 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
             double s, co;
             dm_sincos(th, &s, &co);
             const double r22 = (1.0 - co) + co;
-            const double meas_var = zs * zs + kd(kl2(KOFF(p.me2)), 0);
+            // the weighting's arguments, one group per row
+            su8 wp;                                  // me2, radius, corr, min_contacts
+            su4 wq;                                  // use_shape, m, eval_mask, end_mask
+            kl8_4(wp, KOFF(p.me2), wq, KOFF(p.use_shape));
+            const double meas_var = zs * zs + kd(wp, 0);
             uint32_t sid = 0;
             if constexpr (DELTA) {
                 // per-particle maps: the host materialises every gather first, so particle i
                 // is at i; its store name sits next to the state (DevState::sid)
                 sid = store_sid(kp<const uint32_t>(kl2(st_off + (uint32_t)offsetof(DevState, sid)), 0)[i]);
             }
-            CMResult r = evaluate_pose<MAXP, BATCH, DELTA, UNG>(win, co, s, r22, x, y, z, meas_var, sid);
+            CMResult r = evaluate_pose<MAXP, BATCH, DELTA, UNG>(win, co, s, r22, x, y, z, meas_var, sid, wp, wq);
             if (meas_var == 0) {            // evaluatePose throws (src/ContactModel.cpp:122): no contact points
                 rowerr = true;
                 r.accepted = false;
@@ -1169,7 +1272,7 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
                 maxm = (maxm < r.weight) ? r.weight : maxm;
                 nDTP += 1u + (r.ncp << 16);
                 // pow(weight, 1.0/found) with weight = exp(-s2/2): exp(-s2/2 * (1/found))
-                const uint32_t use_shape = kl2(KOFF(p.use_shape))[0];
+                const uint32_t use_shape = wq[0];
                 if (!use_shape || r.ncp == 0) sw = dm_pow(r.weight, inv_n);
                 else sw = r.weight == 0.0 ? 0.0 : dm_exp((-0.5 * r.s2) * inv_n);
             } else {
@@ -1185,8 +1288,13 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
             mprob = mp_in;
             flags = fl_in;
         }
-        // all stores of the row at the end: one scalar load of the output pointers
-        const StatePtrs st = kstate(st_off);
+        // all stores of the row at the end: the output pointers and, for the clear, the marks
+        // pointer in one group
+        su16 so;
+        su2 mp = {};
+        if (gath) kl16_2(so, st_off, mp, KOFF(gv.marks));
+        else so = kl16(st_off);
+        const StatePtrs st = state_ptrs(so);
         if (PROJECT || gath) {
             K1_ST(st.x + i, x);
             K1_ST(st.y + i, y);
@@ -1201,7 +1309,7 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
             K1_ST(st.zs + i, zs);
             if (gath || w != w_in || w != w) K1_ST(st.w + i, w);
         }
-        if (clr) kp<uint32_t>(kl2(KOFF(gv.marks)), 0)[i] = 0;
+        if (clr) kp<uint32_t>(mp, 0)[i] = 0;
         {
             // v_max_f32 returns the other operand for a NaN: NaN coordinates are skipped
             const float xf = (float)x, yf = (float)y;
@@ -4308,7 +4416,7 @@ extern "C" hipError_t eslam_launch_project_weight(int project, int weight, int m
     uint64_t chunks = (p->n + csz - 1) / csz;
     if (sel && sel->mode == 2u) chunks = sel->c_lo + (chunks > sel->c_hi ? chunks - sel->c_hi : 0);   // the edge chunks
     if (chunks == 0) return hipSuccess;
-    const size_t lds = kStatsLds + (weight ? kWindowLds : 0);
+    const size_t lds = kStatsLds + (weight ? kWindowLds : (project && ESLAM_K1_BM_LDS ? kBmLds : 0));
     K1Args args;
     args.p = *p;
     args.map = *map;
