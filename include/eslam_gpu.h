@@ -345,13 +345,37 @@ typedef struct eslam_shared_merge_info {
  * Errors: ESLAM_ERR_INVALID_ARG (null arguments, a filter with ESLAM_FLAG_PARTICLE_MAPS,
  * non-finite patches), ESLAM_ERR_NO_ENVIRONMENT (no map), ESLAM_ERR_NOT_INITIALISED (no
  * particles), ESLAM_ERR_UNSUPPORTED (a sharded filter: every rank holds its own copy of the
- * grid, and a merge in global particle order across ranks is not built),
+ * grid, and the merge in global particle order is the collective
+ * eslam_gpu_shared_map_update_sharded below; this call runs no collective),
  * ESLAM_ERR_OUT_OF_MEMORY (an allocation failed, or a run's placed patches could take the
  * grid past 2^32 - 1 patches).  After a failure the grid holds the runs merged before it
  * (info->particles_done particles).  count == 0 succeeds and changes nothing.  info may be
  * NULL.                                                                                    */
 int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
                                 eslam_shared_merge_info* info);
+/* The same merge on a sharded filter (eslam_gpu_set_comm), a collective in SPMD order: every
+ * rank passes the same scan and the same max_records.  The particles run in global index
+ * order 0 .. n_global-1, and every rank merges every run into its own copy of the grid, so
+ * afterwards every rank's grid (and the cell table and occupancy bits the step and the match
+ * read) equals, byte for byte, the grid of one context holding all n_global particles.  Per
+ * run the ranks exchange the run's poses (x, y, theta, zPos, zSigma: 40 bytes per particle,
+ * one all_to_all_v), not the records.  The runs are those of the plain call with n = n_global,
+ * and info (the same on every rank) counts global particles and records.
+ * Memory: the plain call's scratch, bounded by max_records, plus the exchange memory of at
+ * most (nranks + 1) x run particles x 40 bytes (a run has at most max_records / count
+ * particles, at least one), kept with the context like the scratch.
+ * Every check the plain call makes on its arguments and the filter's state runs before the
+ * first collective, with the plain call's codes.  The ranks then compare {count, max_records,
+ * a 64-bit hash of the patches' bytes}: when they differ every rank returns
+ * ESLAM_ERR_INVALID_ARG and no grid has changed.  Before a run changes any grid the ranks
+ * agree that each of them has the memory for it: when one has not, it returns its own code
+ * (ESLAM_ERR_OUT_OF_MEMORY), the others ESLAM_ERR_COMM, and every rank holds the grid of the
+ * same completed runs with the same info->particles_done; ESLAM_OK on one rank means every
+ * rank succeeded.  A failed callback is ESLAM_ERR_COMM.  count == 0 succeeds and changes
+ * nothing (the ranks still compare it).  On a filter that is not sharded this is the plain
+ * call: the same bytes, the same counters.                                                 */
+int eslam_gpu_shared_map_update_sharded(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count,
+                                        uint64_t max_records, eslam_shared_merge_info* info);
 /* the shared grid as the device holds it (after eslam_gpu_set_map and every merge since): its
  * size (any pointer may be NULL) ...                                                        */
 int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64_t* n_patches, int* has_height);
@@ -690,7 +714,8 @@ typedef struct eslam_comm {
  * The context's config particle_count is the global count.  Sharded contexts support
  * the hot path (step/project/update/sync), init, upload/download of the local shard,
  * weights sum / normalise / resample, the best particle (global index), the centroid, the
- * hash respawn and per-particle maps, each equal to one GPU bit for bit.  comm == NULL
+ * hash respawn, per-particle maps and the merge into the shared map
+ * (eslam_gpu_shared_map_update_sharded), each equal to one GPU bit for bit.  comm == NULL
  * returns the context to one GPU.
  * Calls on a sharded filter follow SPMD order: every rank makes the same sequence of
  * calls that update, write, normalise, resample or reduce (they run collectives).  The

@@ -764,7 +764,9 @@ public:
     // the same merge with the shared map (useShared = true: every particle's pgrid is the one
     // grid, src/EmbodiedSlamFilter.cpp:184-227): the scan goes into the shared grid once per
     // particle, at that particle's pose, in particle order (eslam_gpu_shared_map_update; the
-    // particles do not change).  Returns the merge's counters.
+    // particles do not change).  Returns the merge's counters.  On a sharded estimator this is
+    // the collective eslam_gpu_shared_map_update_sharded: every rank must pass the same scan, and
+    // every rank's copy of the grid ends as one GPU's would (global particle order).
     eslam_shared_merge_info updateSharedMap(const std::vector<ScanPatch>& scan, uint64_t maxRecords = 0)
     {
         flush();
@@ -774,7 +776,10 @@ public:
             p[k].stdev = scan[k].stdev;
         }
         eslam_shared_merge_info info;
-        check(ctx_, eslam_gpu_shared_map_update(ctx_, p.data(), (uint32_t)p.size(), maxRecords, &info));
+        if (sharded())
+            check(ctx_, eslam_gpu_shared_map_update_sharded(ctx_, p.data(), (uint32_t)p.size(), maxRecords, &info));
+        else
+            check(ctx_, eslam_gpu_shared_map_update(ctx_, p.data(), (uint32_t)p.size(), maxRecords, &info));
         return info;
     }
 
@@ -1248,7 +1253,8 @@ public:
     // update(body2odometry, dimage, camera2body)  src/EmbodiedSlamFilter.cpp:239-309: gated by
     // mappingCameraThreshold on stereoPose; the image's MLS always merges
     // (processMap(scan, false, true)), into the shared grid or into every particle's map.  The
-    // texture image of the reference's signature is not taken.
+    // texture image of the reference's signature is not taken.  On a sharded
+    // estimator with the shared map the merge is a collective: every rank passes the same image.
     bool update(const Affine3d& body2odometry, const DistanceImage& dimage, const Affine3d& camera2body)
     {
         if (!eslamConfig_.mappingCameraThreshold.test(stereoPose_.inverse() * body2odometry * camera2body)) return false;
@@ -1267,7 +1273,8 @@ public:
     // build's match rule, eslam_gpu_map_match); update then merges the patches into every
     // particle's own map (useSharedMap = false; the reference's update-only call, :340-342) or,
     // with the shared map, into the one grid once per particle in particle order (the camera
-    // path's processMap(scanMap, false, true), :301)
+    // path's processMap(scanMap, false, true), :301).  On a sharded estimator the shared map's
+    // merge is a collective (PoseEstimator::updateSharedMap): every rank passes the same scan.
     void processMap(const std::vector<ScanPatch>& scanMap, bool match, bool update)
     {
         if (match) estimator().matchMaps(scanMap);

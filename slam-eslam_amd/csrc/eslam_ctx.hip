@@ -277,6 +277,10 @@ struct eslam_ctx {
     uint64_t map_np_cap = 0;                 // patches grid.patch / grid.height have room for
     // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
     Dev<void> sm_mem;
+    // eslam_gpu_shared_map_update_sharded's exchange memory, kept between calls: kSmXHead bytes for
+    // the small all_gathers, then a run's staged pose records (one copy per rank) and the gathered
+    // run, at most (nranks + 1) x run particles x 40 bytes
+    Dev<void> sm_x;
     // eslam_gpu_scan_from_laser / _depth: the build's scratch (ScanWork) and the last
     // built scan's patches (capacity in patches), both kept between calls
     Dev<void> scan_mem;
@@ -1879,8 +1883,85 @@ static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t sca
     return ESLAM_OK;
 }
 
-extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
-                                           eslam_shared_merge_info* info)
+// ---- the merge on a sharded filter (eslam_gpu_shared_map_update_sharded): every rank merges
+// every run into its own copy of the grid, from the run's poses gathered in global order
+constexpr uint64_t kSmPoseBytes = kSmPoseWords * 8;
+constexpr uint64_t kSmXHead = 4096;          // ctx->sm_x starts with the small all_gathers' words
+
+// all_gather of `words` 64-bit words per rank between host arrays (device-memory callbacks:
+// through the head of ctx->sm_x)
+static int sm_allgather_words(eslam_ctx* ctx, const uint64_t* send, uint64_t* recv, uint32_t words)
+{
+    const eslam_comm& c = ctx->comm;
+    const uint64_t bytes = 8ull * words;
+    static_assert(8ull * 4 * (kMaxRanks + 1) <= kSmXHead, "the head holds four words per rank");
+    if (!c.device_memory) {
+        if (c.allgather(c.user, send, recv, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
+        return ESLAM_OK;
+    }
+    char* d = ctx->sm_x.as<char>();
+    HIPCHK(ctx, hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = comm_allgather(ctx, d, d + bytes, bytes);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(recv, d + bytes, bytes * c.nranks, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ESLAM_OK;
+}
+
+// ESLAM_OK on a rank means every rank passed `rc` = ESLAM_OK.  A failing rank keeps its own code
+// (and message); the others return ESLAM_ERR_COMM.
+static int sm_agree(eslam_ctx* ctx, int rc)
+{
+    const std::string msg = ctx->err;
+    const uint64_t mine = (uint64_t)(int64_t)rc;
+    uint64_t all[kMaxRanks] = {};
+    const int crc = sm_allgather_words(ctx, &mine, all, 1);
+    if (rc) {
+        ctx->err = msg;
+        return rc;
+    }
+    if (crc) return crc;
+    for (int r = 0; r < ctx->comm.nranks; ++r)
+        if (all[r])
+            return fail(ctx, ESLAM_ERR_COMM,
+                        ("shared_map_update_sharded: rank " + std::to_string(r) + " failed (" + std::to_string((int64_t)all[r]) + ")").c_str());
+    return ESLAM_OK;
+}
+
+// the pose records of the run's particles [i0, i0 + np) (global), in global order, into `recv`:
+// every rank stages its part of the run once per rank and the all_to_all_v hands every rank
+// every part, in rank order -- the shards are consecutive, so that is the run's order
+static int sm_exchange(eslam_ctx* ctx, uint64_t i0, uint64_t np, double* send, double* recv)
+{
+    const int G = ctx->comm.nranks, me = ctx->comm.rank;
+    uint64_t sb[kMaxRanks], rb[kMaxRanks], first = 0, mine = 0;
+    for (int r = 0; r < G; ++r) {
+        const uint64_t a = i0 > ctx->gall[r] ? i0 : ctx->gall[r];
+        const uint64_t b = i0 + np < ctx->gall[r + 1] ? i0 + np : ctx->gall[r + 1];
+        const uint64_t c = b > a ? b - a : 0;
+        rb[r] = c * kSmPoseBytes;
+        if (r == me) {
+            first = c ? a - ctx->gbase : 0;
+            mine = c;
+        }
+    }
+    for (int r = 0; r < G; ++r) sb[r] = mine * kSmPoseBytes;
+    if (mine) HIPCHK(ctx, eslam_launch_sm_stage(ctx->st[0], ctx->st[1], ctx->ctl, first, mine, (uint32_t)G, send, ctx->stream));
+    return comm_alltoallv(ctx, send, sb, recv, rb);
+}
+
+static uint64_t sm_patch_hash(const eslam_scan_patch* patches, uint32_t count)
+{
+    uint64_t h = 0xcbf29ce484222325ull;                        // FNV-1a over the patches' bytes
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(patches);
+    for (uint64_t k = 0; k < (uint64_t)count * sizeof(eslam_scan_patch); ++k) h = (h ^ p[k]) * 0x100000001b3ull;
+    return h;
+}
+
+// both entry points.  collective: eslam_gpu_shared_map_update_sharded; on a sharded filter
+// (sh) the runs cover the global index range and read gathered poses.
+static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
+                     eslam_shared_merge_info* info, bool collective)
 {
     if (info) memset(info, 0, sizeof(*info));
     if (!ctx || (!patches && count)) return ESLAM_ERR_INVALID_ARG;
@@ -1892,51 +1973,97 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
             return fail(ctx, ESLAM_ERR_INVALID_ARG, "shared_map_update: scan patches must be finite");
     if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (ctx->sharded)
+    if (ctx->sharded && !collective)
         return fail(ctx, ESLAM_ERR_UNSUPPORTED,
                     "shared_map_update: a sharded filter keeps a copy of the grid per rank; the merge in global particle "
-                    "order across ranks is not built");
+                    "order is the collective eslam_gpu_shared_map_update_sharded");
+    const bool sh = ctx->sharded;
     if (const int rc_ = check_poisoned(ctx)) return rc_;
+    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    if (sh) {
+        // every check above ran before the first collective; then the ranks must have been given
+        // the same call, or their grids would differ from here on
+        if (count && ncell >= 0xffffffffull)
+            return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
+        if (const int rc_ = settle(ctx)) return rc_;           // a deferred sharded exchange first
+        if (ctx->sm_x.cap() < kSmXHead && ctx->sm_x.alloc(kSmXHead) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update_sharded: no device memory for the exchange");
+        }
+        const uint64_t mine[3] = {count, max_records, sm_patch_hash(patches, count)};
+        uint64_t all[3 * kMaxRanks] = {};
+        if (const int rc_ = sm_allgather_words(ctx, mine, all, 3)) return rc_;
+        for (int r = 0; r < ctx->comm.nranks; ++r)
+            if (memcmp(all + 3 * r, mine, sizeof(mine)) != 0)
+                return fail(ctx, ESLAM_ERR_INVALID_ARG,
+                            "shared_map_update_sharded: the ranks passed different scans or max_records; every rank must make "
+                            "the same call");
+    }
     if (info) info->n_patches = ctx->map_np;
     if (!count) return ESLAM_OK;
-    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
     if (ncell >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
     // a run: whole particles, at most max_records records, at least one particle
-    const uint64_t P = count, n = ctx->n;
+    const uint64_t P = count, n = sh ? ctx->n_global : ctx->n;
     uint64_t lim = max_records ? max_records : kSmDefaultRecords;
     if (lim > (1ull << 31)) lim = 1ull << 31;                  // record indices are 32-bit
     uint64_t per = lim / P;
     per = per < 1 ? 1 : (per > n ? n : per);
     SmScratch sc;
     ScanPatch* d_sp = nullptr;
-    int rc = sm_scratch(ctx, per * P, ncell, P, &sc, &d_sp);
-    if (!rc) rc = materialize(ctx);                           // the particles as they stand
+    double *x_send = nullptr, *x_recv = nullptr;               // a sharded run's pose records, out and in
+    auto setup = [&]() -> int {
+        int rc = sm_scratch(ctx, per * P, ncell, P, &sc, &d_sp);
+        if (!rc && sh) {
+            // the staged copies (one per rank) and the gathered run
+            const uint64_t G = ctx->comm.nranks, out = (G * per * kSmPoseBytes + 255) & ~255ull;
+            hipError_t he_ = hipSuccess;
+            rc = ctx->sm_x.grow_keep(kSmXHead + out + per * kSmPoseBytes, 1, ctx->stream, &he_);
+            if (rc == ESLAM_ERR_OUT_OF_MEMORY)
+                return fail(ctx, rc, "shared_map_update_sharded: no device memory for the exchange (lower max_records)");
+            if (rc) HIPCHK(ctx, he_);
+            x_send = reinterpret_cast<double*>(ctx->sm_x.as<char>() + kSmXHead);
+            x_recv = reinterpret_cast<double*>(ctx->sm_x.as<char>() + kSmXHead + out);
+        }
+        if (!rc) rc = materialize(ctx);                       // the particles as they stand
+        if (rc) return rc;
+        static_assert(sizeof(ScanPatch) == sizeof(eslam_scan_patch), "scan patch layout");
+        HIPCHK(ctx, hipMemcpyAsync(d_sp, patches, P * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(sc.cnt, 0, kSmCounters * 8, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(sc.touched, 0, ncell * 4, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // `patches` is the caller's
+        return ESLAM_OK;
+    };
+    int rc = setup();
+    if (sh) rc = sm_agree(ctx, rc);                           // an allocation can fail on one rank only
     if (rc) return rc;
-    static_assert(sizeof(ScanPatch) == sizeof(eslam_scan_patch), "scan patch layout");
-    HIPCHK(ctx, hipMemcpyAsync(d_sp, patches, P * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(sc.cnt, 0, kSmCounters * 8, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(sc.touched, 0, ncell * 4, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));           // `patches` is the caller's
     GridBufs spare;
     uint64_t spare_cap = 0;
     uint64_t cnt[kSmCounters] = {};
     uint64_t done = 0, runs = 0, placed_all = 0;
     hipError_t he = hipSuccess;
+    // what k_sm_place / k_sm_apply read the poses from: the particles, or (SmRun::gath) the gathered run
+    DevState gathered = {};
+    gathered.x = x_recv;
+    const DevState a0 = sh ? gathered : ctx->st[0], a1 = sh ? gathered : ctx->st[1];
     for (uint64_t i0 = 0; i0 < n && !rc; i0 += per) {
+        const uint64_t np = n - i0 < per ? n - i0 : per;
         SmRun run = {};
-        run.i0 = i0;
+        run.i0 = sh ? 0 : i0;
         run.P = count;
-        run.R = (n - i0 < per ? n - i0 : per) * P;
+        run.R = np * P;
         run.ncell = (uint32_t)ncell;
         run.is_id = ctx->map.g2l_identity;
         run.sp = d_sp;
-        if ((he = eslam_launch_sm_place(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &run, &sc, ctx->stream)) != hipSuccess) break;
+        run.gath = sh ? 1u : 0u;
+        if (sh && (rc = sm_exchange(ctx, i0, np, x_send, x_recv)) != ESLAM_OK) break;
         uint64_t placed = 0;
-        if ((he = hipMemcpyAsync(&placed, sc.cnt + kSmRunPlaced, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-        if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
-        if (placed) {
-            // the new arrays exist before anything of the grid changes: a run that finds no room
-            // leaves the grid as the runs before it made it
+        // the new arrays exist before anything of the grid changes: a run that finds no room
+        // leaves the grid as the runs before it made it
+        do {
+            if ((he = eslam_launch_sm_place(a0, a1, ctx->ctl, &ctx->map, &run, &sc, ctx->stream)) != hipSuccess) break;
+            if ((he = hipMemcpyAsync(&placed, sc.cnt + kSmRunPlaced, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
+            if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
+            if (!placed) break;
             const uint64_t need = ctx->map_np + placed;
             if (need > 0xffffffffull) {
                 rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: the grid would pass 2^32 - 1 patches");
@@ -1947,13 +2074,23 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
                 want = want > 0xffffffffull ? 0xffffffffull : want;
                 const bool h = ctx->grid.height != nullptr;
                 spare_cap = sm_alloc_grid(&spare, ncell, want, h) ? want : sm_alloc_grid(&spare, ncell, need, h) ? need : 0;
-                if (!spare_cap) {
-                    rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
-                    break;
-                }
+                if (!spare_cap) rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
             }
+        } while (0);
+        if (sh) {
+            // the ranks agree before any of them changes its grid (the apply fuses in place): after
+            // a failure every rank holds the grid of the same completed runs
+            if (he != hipSuccess) {
+                ctx->err = std::string("shared_map_update: ") + hipGetErrorString(he);
+                he = hipSuccess;
+                rc = ESLAM_ERR_HIP;
+            }
+            rc = sm_agree(ctx, rc);
+        }
+        if (he != hipSuccess || rc) break;
+        if (placed) {
             const SmGrid cur = ctx->grid.view(), next = spare.view();
-            if ((he = eslam_launch_sm_merge(ctx->st[0], ctx->st[1], ctx->ctl, &run, &cur, &next, &sc, ctx->stream)) != hipSuccess) break;
+            if ((he = eslam_launch_sm_merge(a0, a1, ctx->ctl, &run, &cur, &next, &sc, ctx->stream)) != hipSuccess) break;
             uint32_t total = 0;
             if ((he = hipMemcpyAsync(&total, next.cell_start + ncell, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
             if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
@@ -1966,7 +2103,7 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
             ctx->map.occ = ctx->grid.occ; ctx->map.cell_tab = ctx->grid.cell_tab;
         }
         placed_all += placed;
-        done = i0 + run.R / P;
+        done = i0 + np;
         ++runs;
     }
     if (he == hipSuccess) he = hipMemcpy(cnt, sc.cnt, sizeof(cnt), hipMemcpyDeviceToHost);
@@ -1987,6 +2124,18 @@ extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patc
         return ESLAM_ERR_HIP;
     }
     return rc;
+}
+
+extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
+                                           eslam_shared_merge_info* info)
+{
+    return sm_update(ctx, patches, count, max_records, info, false);
+}
+
+extern "C" int eslam_gpu_shared_map_update_sharded(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count,
+                                                   uint64_t max_records, eslam_shared_merge_info* info)
+{
+    return sm_update(ctx, patches, count, max_records, info, true);
 }
 
 extern "C" int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64_t* n_patches, int* has_height)

@@ -412,9 +412,11 @@ struct SmRun {
     uint32_t P;
     uint32_t ncell;                      // width * height: also the key of a record that is not placed
     uint32_t is_id;                      // the grid's global2local is the identity
-    uint32_t pad;
+    uint32_t gath;                       // 0: the particles' own columns at i0 + ip.  1, a sharded run (i0 = 0): the
+                                         //   DevState's x names the run's gathered records, kSmPoseWords doubles each
     const ScanPatch* sp;                 // the scan (device)
 };
+constexpr uint32_t kSmPoseWords = 5;     // a sharded run's pose record: x, y, theta, zPos, zSigma (40 bytes)
 // the grid's arrays a merge reads and writes (fuses in place) or rebuilds into
 struct SmGrid {
     uint32_t* cell_start;

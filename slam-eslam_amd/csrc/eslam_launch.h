@@ -109,6 +109,8 @@ hipError_t eslam_launch_hash_replace_global(DevState s0, DevState s1, const Ctl*
 
 // ---- eslam_shared_map.hip
 size_t eslam_sm_sort_bytes(uint64_t records);
+hipError_t eslam_launch_sm_stage(DevState s0, DevState s1, const Ctl* ctl, uint64_t first, uint64_t cnt, uint32_t copies,
+                                 double* out, hipStream_t stream);
 hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const SmRun* run,
                                  const SmScratch* s, hipStream_t stream);
 hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl* ctl, const SmRun* run, const SmGrid* cur,

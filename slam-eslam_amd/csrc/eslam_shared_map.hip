@@ -14,6 +14,12 @@
 // chain of one cell is serial by contract (the fp32-rounded fuse is not associative), so a
 // concentrated cloud leaves few lanes with long segments; speed was not the goal here.
 // Not on the per-step hot path.
+// A sharded filter (eslam_gpu_shared_map_update_sharded) runs the same pipeline on every rank's
+// copy of the grid: k_sm_stage packs the rank's part of a run as 40-byte pose records, the
+// ranks exchange them, and the kGath instantiations of k_sm_place / k_sm_apply read particle ip
+// of the run from the gathered records (SmRun::gath: s0.x names them) instead of the rank's own
+// columns.  The parameter lists are the same, so the one-context instantiations are the code
+// they were before the gathered form existed.
 #include <hip/hip_runtime.h>
 
 #include "eslam_internal.h"
@@ -25,6 +31,8 @@ constexpr int kSmApplyBlock = 64;        // one wave per block: long segments sp
 
 // record r of the run: its cell in keys[r] (run.ncell when the particle is skipped or the patch
 // falls off the grid), r itself in vals[r].  The placement is eslam_gpu_map_update's.
+// kGath: particle ip's pose is the run's gathered record ip (s0.x: SmRun::gath), not column i0 + ip.
+template <bool kGath>
 __global__ void __launch_bounds__(kBlock) k_sm_place(DevState s0, DevState s1, const Ctl* __restrict__ ctl, MapView map,
                                                      SmRun run, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                      uint64_t* __restrict__ cnt)
@@ -36,7 +44,8 @@ __global__ void __launch_bounds__(kBlock) k_sm_place(DevState s0, DevState s1, c
         const uint64_t ip = r / run.P;
         const uint32_t k = (uint32_t)(r - ip * run.P);
         const uint64_t i = run.i0 + ip;
-        const double x = st.x[i], y = st.y[i], th = st.th[i];
+        const double* pose = kGath ? s0.x + ip * kSmPoseWords : nullptr;
+        const double x = kGath ? pose[0] : st.x[i], y = kGath ? pose[1] : st.y[i], th = kGath ? pose[2] : st.th[i];
         const double bx = x - map.offset_x, by = y - map.offset_y;
         uint32_t cell = 0xffffffffu;
         if (dm_isfinite(bx) && dm_isfinite(by) && dm_isfinite(th)) {
@@ -49,7 +58,7 @@ __global__ void __launch_bounds__(kBlock) k_sm_place(DevState s0, DevState s1, c
                                         map.height_cells, &cm, &cn);
             } else {
                 const double* A = map.g2l;
-                const double wz = sp.z + st.z[i];
+                const double wz = sp.z + (kGath ? pose[3] : st.z[i]);
                 const double wx = (co * sp.x + (-sn) * sp.y) + x;
                 const double wy = (sn * sp.x + co * sp.y) + y;
                 const double lx = ((A[0] * wx + A[1] * wy) + A[2] * wz) + A[3];
@@ -95,6 +104,7 @@ __global__ void __launch_bounds__(kBlock) k_sm_heads(const uint32_t* __restrict_
 // One lane per touched cell: its records in sorted (= record) order against the cell's list,
 // the grid's patches (fused in place) and then the patches this segment appended (app[j0 ..]).
 // No other lane reads or writes this cell's patches or this slice of app.
+template <bool kGath>
 __global__ void __launch_bounds__(kSmApplyBlock) k_sm_apply(DevState s0, DevState s1, const Ctl* __restrict__ ctl, SmRun run,
                                                             SmGrid g, const uint32_t* __restrict__ keys,
                                                             const uint32_t* __restrict__ order,
@@ -116,8 +126,9 @@ __global__ void __launch_bounds__(kSmApplyBlock) k_sm_apply(DevState s0, DevStat
             const uint32_t ip = r / run.P, k = r - ip * run.P;
             const uint64_t i = run.i0 + ip;
             const ScanPatch sp = run.sp[k];
-            const double zs = st.zs[i];
-            const double wz = sp.z + st.z[i];
+            const double* pose = kGath ? s0.x + (uint64_t)ip * kSmPoseWords : nullptr;
+            const double zs = kGath ? pose[4] : st.zs[i];
+            const double wz = sp.z + (kGath ? pose[3] : st.z[i]);
             const double var = sp.stdev * sp.stdev + zs * zs;
             bool taken = false;
             for (uint32_t q = b; q < e && !taken; ++q) {
@@ -160,6 +171,23 @@ __global__ void __launch_bounds__(kSmApplyBlock) k_sm_apply(DevState s0, DevStat
     if (absorbed) atomicAdd((unsigned long long*)&cnt[kSmAbsorbed], (unsigned long long)absorbed);
     if (inserted) atomicAdd((unsigned long long*)&cnt[kSmInserted], (unsigned long long)inserted);
     if (cells) atomicAdd((unsigned long long*)&cnt[kSmTouched], (unsigned long long)cells);
+}
+
+// A sharded run's send buffer: particles [first, first + cnt) of this rank's current buffer as
+// 40-byte records {x, y, theta, zPos, zSigma}, one copy per rank (the all_to_all_v sends every
+// rank the same block).  One lane per particle: a wave's loads of a column are consecutive.
+__global__ void __launch_bounds__(kBlock) k_sm_stage(DevState s0, DevState s1, const Ctl* __restrict__ ctl, uint64_t first,
+                                                     uint64_t cnt, uint32_t copies, double* __restrict__ out)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= cnt) return;
+    const DevState st = (ctl->base ^ ctl->flip) ? s1 : s0;
+    const uint64_t i = first + t;
+    const double x = st.x[i], y = st.y[i], th = st.th[i], z = st.z[i], zs = st.zs[i];
+    for (uint32_t c = 0; c < copies; ++c) {
+        double* o = out + ((uint64_t)c * cnt + t) * kSmPoseWords;
+        o[0] = x; o[1] = y; o[2] = th; o[3] = z; o[4] = zs;
+    }
 }
 
 // the new cell sizes, ready for the exclusive scan (out[ncell] = 0 receives the total)
@@ -225,14 +253,26 @@ extern "C" size_t eslam_sm_sort_bytes(uint64_t records)
     return b;
 }
 
+// a sharded run's pose records: this rank's particles [first, first + cnt) (cnt > 0), `copies` times
+extern "C" hipError_t eslam_launch_sm_stage(DevState s0, DevState s1, const Ctl* ctl, uint64_t first, uint64_t cnt,
+                                            uint32_t copies, double* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_sm_stage, dim3(blocks_for(cnt)), dim3(kBlock), 0, stream, s0, s1, ctl, first, cnt, copies, out);
+    return hipGetLastError();
+}
+
 // (a) the records' cells; cnt[kSmRunPlaced] (zeroed here) receives the run's placed count
 extern "C" hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const SmRun* run,
                                             const SmScratch* s, hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(s->cnt + kSmRunPlaced, 0, sizeof(uint64_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sm_place, dim3(blocks_for(run->R)), dim3(kBlock), 0, stream, s0, s1, ctl, *map, *run, s->keys, s->vals,
-                       s->cnt);
+    if (run->gath)
+        hipLaunchKernelGGL(k_sm_place<true>, dim3(blocks_for(run->R)), dim3(kBlock), 0, stream, s0, s1, ctl, *map, *run, s->keys,
+                           s->vals, s->cnt);
+    else
+        hipLaunchKernelGGL(k_sm_place<false>, dim3(blocks_for(run->R)), dim3(kBlock), 0, stream, s0, s1, ctl, *map, *run, s->keys,
+                           s->vals, s->cnt);
     return hipGetLastError();
 }
 
@@ -258,8 +298,12 @@ extern "C" hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl*
     const uint64_t segs = R < ncell ? R : ncell;
     uint64_t ab = (segs + kSmApplyBlock - 1) / kSmApplyBlock;
     ab = ab < 1 ? 1 : (ab > 4096 ? 4096 : ab);
-    hipLaunchKernelGGL(k_sm_apply, dim3((uint32_t)ab), dim3(kSmApplyBlock), 0, stream, s0, s1, ctl, *run, *cur, s->keys_out,
-                       s->order, heads, flag + R, s->app, s->add, s->segpos, s->touched, s->cnt);
+    if (run->gath)
+        hipLaunchKernelGGL(k_sm_apply<true>, dim3((uint32_t)ab), dim3(kSmApplyBlock), 0, stream, s0, s1, ctl, *run, *cur,
+                           s->keys_out, s->order, heads, flag + R, s->app, s->add, s->segpos, s->touched, s->cnt);
+    else
+        hipLaunchKernelGGL(k_sm_apply<false>, dim3((uint32_t)ab), dim3(kSmApplyBlock), 0, stream, s0, s1, ctl, *run, *cur,
+                           s->keys_out, s->order, heads, flag + R, s->app, s->add, s->segpos, s->touched, s->cnt);
     hipLaunchKernelGGL(k_sm_counts, dim3(blocks_for((uint64_t)ncell + 1)), dim3(kBlock), 0, stream, cur->cell_start, s->add,
                        ncell, next->cell_start);
     e = eslam_launch_scan_excl(next->cell_start, (uint64_t)ncell + 1, stream);

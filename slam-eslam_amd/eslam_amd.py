@@ -74,6 +74,9 @@ def load_library(path=LIB_PATH):
                                          C.POINTER(C.c_int)]
         L.eslam_gpu_get_map.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.c_uint64]
+    if hasattr(L, "eslam_gpu_shared_map_update_sharded"):   # absent from older builds (A/B runs)
+        L.eslam_gpu_shared_map_update_sharded.argtypes = [vp, C.POINTER(A.ScanPatch), C.c_uint32, C.c_uint64,
+                                                          C.POINTER(A.SharedMergeInfo)]
     if hasattr(L, "eslam_gpu_scan_from_laser"):          # absent from older builds (A/B runs)
         L.eslam_scan_params_default.argtypes = [C.POINTER(A.Config), C.POINTER(A.ScanParams)]
         L.eslam_gpu_scan_from_laser.argtypes = [vp, C.POINTER(A.LaserScan), C.POINTER(A.ScanParams), C.POINTER(A.ScanInfo)]
@@ -235,6 +238,18 @@ class GpuFilter:
         error the EslamError carries the counters of the runs merged before it (`.info`)."""
         info = A.SharedMergeInfo()
         rc = self.L.eslam_gpu_shared_map_update(self.h, patches, len(patches), max_records, C.byref(info))
+        if rc != 0:
+            e = EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
+            e.info = info
+            raise e
+        return info
+
+    def shared_map_update_sharded(self, patches, max_records=0):
+        """eslam_gpu_shared_map_update_sharded: the same merge on a sharded filter, in global
+        particle order into every rank's copy of the grid.  A collective: every rank passes the
+        same scan and max_records.  On a filter that is not sharded it is shared_map_update."""
+        info = A.SharedMergeInfo()
+        rc = self.L.eslam_gpu_shared_map_update_sharded(self.h, patches, len(patches), max_records, C.byref(info))
         if rc != 0:
             e = EslamError(rc, self.L.eslam_gpu_last_error(self.h).decode())
             e.info = info
