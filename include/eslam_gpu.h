@@ -302,9 +302,42 @@ int eslam_gpu_map_match(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_
  * particle that a resample moves to another rank carries its own patches.                 */
 int eslam_gpu_set_particle_maps(eslam_ctx* ctx, int on);
 /* particle index's own patches (cell = n * width + m, mean, stdev), its window's tiles in slot
- * order and each tile's cells row by row; *count = how many it has (up to capacity written) */
+ * order and each tile's cells row by row; *count = how many it has (up to capacity written).
+ * A debugging aid: one small host copy per page, and only the particle's own cells.  The map
+ * a particle's lookups see is eslam_gpu_get_particle_grid below.                            */
 int eslam_gpu_get_particle_map(eslam_ctx* ctx, uint64_t index, uint32_t* cells, float* mean, float* stdev,
                                uint32_t capacity, uint32_t* count);
+/* particles[index].grid.getMap()  src/PoseEstimator.hpp:79-87 (GridAccess::getMap; the viewer
+ * reads it, viz/EslamWidget.cpp:108-116): particle index's whole map as one MLS grid, composed
+ * on the device.  Per cell the particle's own patch, if it has one there (a cell of a page of
+ * its window or of its trail; height 0), then the shared grid's patches of the cell in their
+ * order with their heights; cell_start is the exclusive prefix of those counts; scale, offset
+ * and global2local are the shared grid's, and the composed grid has heights if and only if the
+ * shared grid has.  A particle whose map was never centred gives the shared grid itself.
+ * getPatch on this grid (the first patch of the cell's list that passes the 3-sigma gate)
+ * answers as the particle's own lookups do, so a filter given the grid by eslam_gpu_set_map
+ * weighs a particle at that pose exactly as this filter weighs particle index.
+ * _size gives the composed patch count; the arrays are those of eslam_gpu_get_map
+ * (cell_start: width * height + 1 entries, eslam_gpu_map_size; patch_height may be NULL).
+ * Each call composes anew (the size call stops after the count); the device arrays composed
+ * into, a second set of the grid's arrays, stay with the context for the next export until
+ * the map is replaced.  Rank-local on a sharded filter: index is the local one.
+ * Errors: ESLAM_ERR_INVALID_ARG (null pointers, no ESLAM_FLAG_PARTICLE_MAPS, index out of
+ * range, patch_capacity below the composed count, a composed count past 2^32 - 1),
+ * ESLAM_ERR_NO_ENVIRONMENT, ESLAM_ERR_NOT_INITIALISED, ESLAM_ERR_UNSUPPORTED (a grid of
+ * 2^32 - 1 cells or more), ESLAM_ERR_OUT_OF_MEMORY (no device memory for the composed arrays);
+ * a poisoned filter returns its fault.  The filter does not change.                        */
+int eslam_gpu_particle_grid_size(eslam_ctx* ctx, uint64_t index, uint64_t* n_patches);
+int eslam_gpu_get_particle_grid(eslam_ctx* ctx, uint64_t index, uint32_t* cell_start, float* mean, float* stdev,
+                                float* patch_height /* may be NULL */, uint64_t patch_capacity);
+/* Continue in particle index's map: leaves the context exactly as eslam_gpu_set_map of the grid
+ * eslam_gpu_get_particle_grid(index) returns would, without the host round trip.  The composed
+ * arrays become the shared grid, the pose hash is invalidated and every particle's own map
+ * starts over, empty.  The new arrays exist before anything changes: ESLAM_ERR_OUT_OF_MEMORY
+ * leaves the filter as it was.  On a sharded filter ESLAM_ERR_UNSUPPORTED, with no collective
+ * run: export on the owning rank and give every rank the grid by eslam_gpu_set_map.  The other
+ * errors are eslam_gpu_get_particle_grid's.                                                  */
+int eslam_gpu_adopt_particle_map(eslam_ctx* ctx, uint64_t index);
 
 /* ---- the shared map (useSharedMap = true): processMap's merge into the one grid ----------
  * EmbodiedSlamFilter::processMap(scanMap, match, update = true) with a shared map
@@ -719,7 +752,7 @@ typedef struct eslam_comm {
  * returns the context to one GPU.
  * Calls on a sharded filter follow SPMD order: every rank makes the same sequence of
  * calls that update, write, normalise, resample or reduce (they run collectives).  The
- * rank-local getters (download, records, particle maps, RNG state, hash poses) may be
+ * rank-local getters (download, records, particle maps, particle grids, RNG state, hash poses) may be
  * called by any subset of ranks: the only collective they can run is the previous
  * update's deferred exchange, which every rank completes exactly once -- in a getter, in
  * its next collective call or in eslam_gpu_finish -- so the ranks stay matched.         */

@@ -730,6 +730,53 @@ public:
         const eslam_mls_grid g = env.toC();
         check(ctx_, eslam_gpu_set_map(ctx_, &g));
         check(ctx_, eslam_gpu_set_particle_maps(ctx_, useShared ? 0 : 1));
+        setGridGeometry(env);
+    }
+    // the geometry particleGrid() gives its grids (setEnvironment records it; an estimator that
+    // took its map from a loaded state is told here): scale, offset and global2local of env
+    void setGridGeometry(const MlsGrid& env)
+    {
+        geometry_ = MlsGrid();
+        geometry_.scaleX = env.scaleX; geometry_.scaleY = env.scaleY;
+        geometry_.offsetX = env.offsetX; geometry_.offsetY = env.offsetY;
+        geometry_.global2local = env.global2local;
+        has_geometry_ = true;
+    }
+    // particles[i].grid.getMap()  src/PoseEstimator.hpp:79-87 (GridAccess::getMap; the viewer's
+    // viewMap(particle_idx) reads it, viz/EslamWidget.cpp:108-116): particle i's whole map -- its
+    // own patch per cell, then the shared grid's -- composed on the device
+    // (eslam_gpu_get_particle_grid), as an MlsGrid setEnvironment takes.  getPatch on it answers
+    // as particle i's own lookups do.  useShared = false only; i is the local index on a sharded
+    // estimator.
+    MlsGrid particleGrid(size_t i)
+    {
+        if (!has_geometry_) throw std::runtime_error("particleGrid: no grid geometry (setEnvironment or setGridGeometry)");
+        flush();
+        uint32_t w = 0, h = 0;
+        int heights = 0;
+        uint64_t np = 0;
+        check(ctx_, eslam_gpu_map_size(ctx_, &w, &h, nullptr, &heights));
+        check(ctx_, eslam_gpu_particle_grid_size(ctx_, (uint64_t)i, &np));
+        MlsGrid g = geometry_;
+        g.width = w;
+        g.height = h;
+        g.cellStart.assign((size_t)w * h + 1, 0u);
+        g.mean.assign(np, 0.0f);
+        g.stdev.assign(np, 0.0f);
+        if (heights) g.patchHeight.assign(np, 0.0f);
+        // (non-null patch pointers for an empty grid too)
+        float none = 0.0f;
+        check(ctx_, eslam_gpu_get_particle_grid(ctx_, (uint64_t)i, g.cellStart.data(), np ? g.mean.data() : &none,
+                                                np ? g.stdev.data() : &none, heights && np ? g.patchHeight.data() : nullptr, np));
+        return g;
+    }
+    // continue in particle i's map (eslam_gpu_adopt_particle_map): as setEnvironment(particleGrid(i))
+    // with the map mode kept and no host round trip -- the composed grid becomes the shared one and
+    // every particle's own map starts over, empty.  One GPU only.
+    void adoptParticleMap(size_t i)
+    {
+        flush();
+        check(ctx_, eslam_gpu_adopt_particle_map(ctx_, (uint64_t)i));
     }
     // cloneMaps  src/PoseEstimator.cpp:31-47: the copies a resample made share their ancestor's
     // patches until the next map update gives each a private copy (copy on write), so there is
@@ -1185,6 +1232,8 @@ private:
     mutable uint32_t last_m_ = 0;
     bool sharded_ = false;
     int rank_ = 0;
+    MlsGrid geometry_;                             // particleGrid(): scale, offset, global2local
+    bool has_geometry_ = false;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -1281,6 +1330,11 @@ public:
         if (update && !sharedMap_) estimator().updateMaps(scanMap);
         if (update && sharedMap_) estimator().updateSharedMap(scanMap);
     }
+
+    // After a mapping run (useSharedMap = false), localise in the map particle i built, e.g. the
+    // best one's (getBestParticleIndex()): PoseEstimator::adoptParticleMap.  The filter keeps
+    // its map mode, so later scans merge into fresh per-particle maps on top of the adopted grid.
+    void adoptParticleMap(size_t i) { estimator().adoptParticleMap(i); }
 
     // saveState / loadState: everything the filter needs to continue bit for bit -- this object's
     // own state (the map mode, the update count, the contact odometry between two updates), then

@@ -281,6 +281,12 @@ struct eslam_ctx {
     // the small all_gathers, then a run's staged pose records (one copy per rank) and the gathered
     // run, at most (nranks + 1) x run particles x 40 bytes
     Dev<void> sm_x;
+    // eslam_gpu_get_particle_grid / eslam_gpu_adopt_particle_map's scratch (PgScratch), kept between calls
+    Dev<void> pg_mem;
+    // ... and the arrays the last export composed into, kept for the next one (room for pg_out_cap
+    // patches on a grid of pg_out_cells cells; dropped with the map, handed over by an adoption)
+    GridBufs pg_out;
+    uint64_t pg_out_cap = 0, pg_out_cells = 0;
     // eslam_gpu_scan_from_laser / _depth: the build's scratch (ScanWork) and the last
     // built scan's patches (capacity in patches), both kept between calls
     Dev<void> scan_mem;
@@ -614,6 +620,8 @@ static void free_particles(eslam_ctx* ctx)
 static void free_map(eslam_ctx* ctx)
 {
     ctx->grid = GridBufs{};
+    ctx->pg_out = GridBufs{};
+    ctx->pg_out_cap = ctx->pg_out_cells = 0;
     ctx->map_np = ctx->map_np_cap = 0;
     ctx->has_map = false;
 }
@@ -2170,6 +2178,125 @@ extern "C" int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* me
         else memset(patch_height, 0, np * 4);
     }
     return ESLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// a particle's whole map as one grid (kernels in eslam_particle_grid.hip)
+// ---------------------------------------------------------------------------------------
+// The checks of the three entry points, then the directory of particle index's table and the
+// composed counts (in *s): *total = the composed grid's patches.
+static int pgrid_count(eslam_ctx* ctx, uint64_t index, PgScratch* s, uint64_t* total)
+{
+    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
+    if (!particle_maps(ctx)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "no per-particle maps (ESLAM_FLAG_PARTICLE_MAPS)");
+    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (index >= ctx->n) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle index out of range");
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    if (ncell >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "particle_grid: the grid has 2^32 - 1 cells or more");
+    int rc = materialize(ctx);
+    if (!rc) rc = read_ctl(ctx);
+    if (rc) return rc;
+    if (!ctx->lm_ready) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "per-particle maps are not set up");
+    const size_t bytes = eslam_pgrid_work_bytes(ctx->map.width, ctx->map.height_cells, nullptr, nullptr);
+    if (bytes > ctx->pg_mem.cap() && ctx->pg_mem.alloc(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "particle_grid: no device memory for the scratch");
+    }
+    (void)eslam_pgrid_work_bytes(ctx->map.width, ctx->map.height_cells, ctx->pg_mem.get(), s);
+    const uint32_t* sid = ctx->st[ctx->ctl_host->base ^ ctx->ctl_host->flip].sid;
+    HIPCHK(ctx, eslam_launch_pgrid_count(&ctx->lm, sid + index, &ctx->map, s, ctx->stream));
+    uint64_t own = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&own, s->own, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *total = ctx->map_np + own;
+    if (*total > 0xffffffffull) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle_grid: the composed grid would pass 2^32 - 1 patches");
+    return ESLAM_OK;
+}
+
+// ... and the composed grid itself in ctx->pg_out, a second set of the grid's arrays that stays
+// with the context for the next export (allocating them cost more than composing into them);
+// a count above `capacity` (the caller's arrays) is refused first
+static int pgrid_compose(eslam_ctx* ctx, uint64_t index, uint64_t* total, uint64_t capacity)
+{
+    PgScratch s;
+    if (const int rc_ = pgrid_count(ctx, index, &s, total)) return rc_;
+    if (capacity < *total)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "get_particle_grid: patch_capacity is below the composed patch count (eslam_gpu_particle_grid_size)");
+    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    const bool h = ctx->grid.height != nullptr;
+    if (!ctx->pg_out.cells || ctx->pg_out_cells != ncell || ctx->pg_out_cap < *total || (ctx->pg_out.height != nullptr) != h) {
+        // room for the window and the trail full of patches, so other particles' exports fit too
+        uint64_t want = ctx->map_np + ((uint64_t)ctx->lm.wx * ctx->lm.wy + ctx->lm.V) * DM_LM_PAGE_CELLS;
+        want = want < *total ? *total : (want > 0xffffffffull ? 0xffffffffull : want);
+        ctx->pg_out_cells = ncell;
+        ctx->pg_out_cap = sm_alloc_grid(&ctx->pg_out, ncell, want, h) ? want : sm_alloc_grid(&ctx->pg_out, ncell, *total, h) ? *total : 0;
+        if (!ctx->pg_out.cells) {
+            ctx->pg_out_cap = ctx->pg_out_cells = 0;
+            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "particle_grid: no device memory for the composed grid");
+        }
+    }
+    const SmGrid cur = ctx->grid.view(), nw = ctx->pg_out.view();
+    HIPCHK(ctx, eslam_launch_pgrid_fill(&ctx->lm, &ctx->map, &s, &cur, &nw, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_particle_grid_size(eslam_ctx* ctx, uint64_t index, uint64_t* n_patches)
+{
+    if (!ctx || !n_patches) return ESLAM_ERR_INVALID_ARG;
+    PgScratch s;
+    return pgrid_count(ctx, index, &s, n_patches);
+}
+
+extern "C" int eslam_gpu_get_particle_grid(eslam_ctx* ctx, uint64_t index, uint32_t* cell_start, float* mean, float* stdev,
+                                           float* patch_height, uint64_t patch_capacity)
+{
+    if (!ctx || !cell_start || !mean || !stdev) return ESLAM_ERR_INVALID_ARG;
+    uint64_t np = 0;
+    if (const int rc_ = pgrid_compose(ctx, index, &np, patch_capacity)) return rc_;
+    const GridBufs& out = ctx->pg_out;
+    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
+    HIPCHK(ctx, hipMemcpy(cell_start, out.cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
+    if (!np) return ESLAM_OK;
+    std::vector<float2> patch(np);
+    HIPCHK(ctx, hipMemcpy(patch.data(), out.patch, np * sizeof(float2), hipMemcpyDeviceToHost));
+    for (uint64_t k = 0; k < np; ++k) {
+        mean[k] = patch[k].x;
+        stdev[k] = patch[k].y;
+    }
+    if (patch_height) {
+        if (out.height) HIPCHK(ctx, hipMemcpy(patch_height, out.height, np * 4, hipMemcpyDeviceToHost));
+        else memset(patch_height, 0, np * 4);
+    }
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_adopt_particle_map(eslam_ctx* ctx, uint64_t index)
+{
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    // refused before any collective (settle is one)
+    if (ctx->sharded)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
+                    "adopt_particle_map: a sharded filter keeps a copy of the grid per rank; export the map on the owning "
+                    "rank (eslam_gpu_get_particle_grid) and give it to every rank by eslam_gpu_set_map");
+    // the new arrays exist before anything changes
+    uint64_t np = 0;
+    if (const int rc_ = pgrid_compose(ctx, index, &np, ~0ull)) return rc_;
+    // as eslam_gpu_set_map: the grid's arrays, the view every later launch reads, no pose hash,
+    // and every particle's map starts over, empty (they name cells of the previous grid)
+    ctx->grid = std::move(ctx->pg_out);                          // (hipFree waits for the device)
+    ctx->pg_out = GridBufs{};
+    const uint64_t cap = ctx->pg_out_cap;
+    ctx->pg_out_cap = ctx->pg_out_cells = 0;
+    ctx->map.cell_start = ctx->grid.cells; ctx->map.patch = ctx->grid.patch; ctx->map.height = ctx->grid.height;
+    ctx->map.occ = ctx->grid.occ; ctx->map.cell_tab = ctx->grid.cell_tab;
+    ctx->map.has_height = ctx->grid.height ? 1u : 0u;
+    ctx->map_np = np;
+    ctx->map_np_cap = cap ? cap : 1;
+    ctx->has_hash = false;
+    return local_maps_reset(ctx);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -443,6 +443,16 @@ struct SmScratch {
 enum SmCounter : uint32_t { kSmFused = 0, kSmAbsorbed, kSmInserted, kSmTouched, kSmRunPlaced, kSmCounters = 8 };
 constexpr uint64_t kSmDefaultRecords = 1ull << 21;   // max_records = 0: 64 MiB of scratch
 
+// ---- a particle's whole map as one grid (eslam_gpu_get_particle_grid, eslam_particle_grid.hip) --
+// the scratch of a composition, carved from one allocation of the context (eslam_pgrid_work_bytes)
+struct PgScratch {
+    uint32_t* dir;                       // tx * ty: the page of the particle's table per grid tile (DM_LM_NONE: none)
+    uint32_t* bsum;                      // per block of kBlock cells (+ 1): the composed lists' total length, then
+                                         //   the exclusive scan of those (the last: the composed grid's patches)
+    uint64_t* own;                       // the particle's own patches on the grid
+    uint32_t tx, ty;                     // the grid in tiles of 8 x 8 cells (rounded up)
+};
+
 // ---- the scan MLS from a sensor reading (eslam_gpu_scan_from_*, eslam_scan.hip) --
 // the reading: a laser scan (ranges) or a depth image (float bits), n points
 struct ScanReading {

@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip), declared once.  All seven .hip files include it, the defining one too: the
+// (eslam_ctx.hip), declared once.  All eight .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -115,6 +115,14 @@ hipError_t eslam_launch_sm_place(DevState s0, DevState s1, const Ctl* ctl, const
                                  const SmScratch* s, hipStream_t stream);
 hipError_t eslam_launch_sm_merge(DevState s0, DevState s1, const Ctl* ctl, const SmRun* run, const SmGrid* cur,
                                  const SmGrid* next, const SmScratch* s, hipStream_t stream);
+
+// ---- eslam_particle_grid.hip
+// the scratch of a composition on a width x height grid: its size, and its arrays within `mem` (may be null: size only)
+size_t eslam_pgrid_work_bytes(uint32_t width, uint32_t height, void* mem, PgScratch* s);
+hipError_t eslam_launch_pgrid_count(const LocalMaps* lm, const uint32_t* sidp, const MapView* map, const PgScratch* s,
+                                    hipStream_t stream);
+hipError_t eslam_launch_pgrid_fill(const LocalMaps* lm, const MapView* map, const PgScratch* s, const SmGrid* cur,
+                                   const SmGrid* out, hipStream_t stream);
 
 // ---- eslam_scan.hip
 // the scratch of a build of n points: its size, and its arrays within `mem` (may be null: size only)

@@ -85,6 +85,11 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_set_particle_maps.argtypes = [vp, C.c_int]
     L.eslam_gpu_get_particle_map.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]
+    if hasattr(L, "eslam_gpu_get_particle_grid"):        # absent from older builds (A/B runs)
+        L.eslam_gpu_particle_grid_size.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.eslam_gpu_get_particle_grid.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64]
+        L.eslam_gpu_adopt_particle_map.argtypes = [vp, C.c_uint64]
     L.eslam_gpu_download_records.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(A.ParticleRecord),
                                              C.POINTER(A.CPoint), C.c_uint32]
     L.eslam_gpu_particle_count.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -321,6 +326,34 @@ class GpuFilter:
             if c.value <= cap:
                 return cells[:c.value], mean[:c.value], sd[:c.value]
             cap = c.value
+
+    def particle_grid(self, i, capacity=None):
+        """eslam_gpu_get_particle_grid: particles[i].grid.getMap(), particle i's whole map (its
+        own patch per cell, then the shared grid's) composed on the device, as GridArrays with
+        the shared grid's geometry: what set_map() takes.  capacity: the patch arrays' size
+        (default: eslam_gpu_particle_grid_size)."""
+        if self._grid is None:
+            raise EslamError(A.ERR_NO_ENVIRONMENT, "No environment attached.")
+        w, h, hh, n = C.c_uint32(), C.c_uint32(), C.c_int(), C.c_uint64()
+        self._check(self.L.eslam_gpu_map_size(self.h, C.byref(w), C.byref(h), None, C.byref(hh)))
+        self._check(self.L.eslam_gpu_particle_grid_size(self.h, i, C.byref(n)))
+        cap = n.value if capacity is None else capacity
+        cells = np.zeros(w.value * h.value + 1, np.uint32)
+        mean = np.zeros(max(cap, 1), np.float32)
+        sd = np.zeros(max(cap, 1), np.float32)
+        hgt = np.zeros(max(cap, 1), np.float32) if hh.value else None
+        fp = C.POINTER(C.c_float)
+        self._check(self.L.eslam_gpu_get_particle_grid(self.h, i, cells.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       mean.ctypes.data_as(fp), sd.ctypes.data_as(fp),
+                                                       hgt.ctypes.data_as(fp) if hh.value else None, cap))
+        g, k = self._grid, n.value
+        return A.GridArrays(w.value, h.value, g.scale, g.offset, cells, mean[:k], sd[:k], hgt[:k] if hh.value else None, g.g2l)
+
+    def adopt_particle_map(self, i):
+        """eslam_gpu_adopt_particle_map: continue in particle i's map, as set_map(particle_grid(i))
+        without the host round trip: it becomes the shared grid and every particle's own map
+        starts over, empty"""
+        self._check(self.L.eslam_gpu_adopt_particle_map(self.h, i))
 
     def count(self):
         n = C.c_uint64()
