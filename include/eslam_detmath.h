@@ -1854,6 +1854,17 @@ DM_FN uint32_t dm_lm_half(double r, double scale)
     const uint32_t h = (uint32_t)q;
     return (double)h < q ? h + 1u : h;
 }
+/* the words of a device table's row (eslam_internal.h LocalMaps; the oracle keeps its own,
+ * unpadded rows): the window's W = wx wy slots, then at least two bookkeeping words (the
+ * shadow flag and the trail's high-water mark: the last two words before the trail), padded to
+ * whole 16-byte words, then the trail's V entries of 4 words.  W is odd.  W = 1 (mod 4) (hx and
+ * hy of one parity, so every square-cell window): W + 3 words, what padding W alone to a
+ * multiple of 4 gives (81 -> 84), so reserving the two words grows no such row.  W = 3 (mod 4)
+ * (parities differ): W + 5 (99 -> 104), where padding W alone would leave a single word.     */
+DM_FN uint32_t dm_lm_row_words(uint32_t W, uint32_t V)
+{
+    return ((W + 2u + 3u) & ~3u) + 4u * V;
+}
 /* the centre tile of a particle at grid-local l (one axis): the tile of the cell
  * floor((l - offset) * inv_scale), saturated to int32 (callers skip non-finite positions)  */
 DM_FN int32_t dm_lm_centre(double l, double off, double inv)

@@ -2521,6 +2521,8 @@ double or_dm(int fn, double x, double y)
     case 19: dm_box_muller32((uint32_t)x, (uint32_t)y, &s, &c); return c;   /* z1 */
     case 26: { float fs, fc; dm_sincos2pi32f((uint32_t)x, &fs, &fc); return fs; }
     case 27: { float fs, fc; dm_sincos2pi32f((uint32_t)x, &fs, &fc); return fc; }
+    case 28: return (double)dm_lm_half(x, y);                                /* (range, cell size) */
+    case 29: return (double)dm_lm_row_words((uint32_t)x, (uint32_t)y);       /* (W, V) */
     default: return NAN;
     }
 }

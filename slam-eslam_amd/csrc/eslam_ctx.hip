@@ -771,9 +771,14 @@ static int local_maps_reset(eslam_ctx* ctx)
     lm.wy = 2 * lm.hy + 1;
     if (ctx->cfg.local_map_trail > 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "local_map_trail: at most 4096 tiles");
     lm.V = ctx->cfg.local_map_trail;
-    // a table's row: the window's slots, padded (NONE) to whole 16-byte words, then the trail's
-    // V 16-byte entries
-    lm.S = ((lm.wx * lm.wy + 3u) & ~3u) + 4u * lm.V;
+    // a table's row: the window's W = wx * wy slots, two bookkeeping words (the shadow flag and
+    // the trail's high-water mark, the last two words before the trail), padded (NONE) to whole
+    // 16-byte words, then the trail's V 16-byte entries.  W is odd: W = 1 (mod 4) when hx and hy
+    // have the same parity (every square-cell window), and then ((W + 2 + 3) & ~3) = W + 3 =
+    // ((W + 3) & ~3), e.g. 81 -> 84 either way: no such row grows by the two reserved words.
+    // W = 3 (mod 4) when the parities differ: padding W alone would leave one word for the two,
+    // so the row takes W + 5, e.g. 99 -> 104.
+    lm.S = dm_lm_row_words(lm.wx * lm.wy, lm.V);
     lm.mx = lm_magic(lm.wx);
     lm.my = lm_magic(lm.wy);
     lm.bx = lm.wx * (((1u << 29) + lm.wx - 1) / lm.wx);

@@ -130,9 +130,12 @@ struct DevState {
 // around the particle (eslam_detmath.h DM_LM_*: the window reaches maxSensorRange and moves
 // with the particle at every map update) and a trail of up to V tiles the window has left.
 //   table  what a particle names (DevState::sid): the window centre and a row of S words: the
-//          window's slots (wx * wy, padded with DM_LM_NONE to a multiple of 4; the slot of tile
-//          (a, b) being (a mod wx) + wx (b mod wy), each a page id or DM_LM_NONE), then the
-//          trail's V entries {a, b, page, -} (page DM_LM_NONE: empty; lm_trail_* below).
+//          window's slots (wx * wy; the slot of tile (a, b) being (a mod wx) + wx (b mod wy),
+//          each a page id or DM_LM_NONE), DM_LM_NONE words up to a multiple of 4 whose last two
+//          are bookkeeping, no page ids (the shadow flag, then the trail's high-water mark:
+//          dm_lm_row_words always leaves room for both), then the trail's V entries
+//          {a, b, page, -} (page DM_LM_NONE: empty; lm_trail_* below).  Whoever walks a row's
+//          pages reads the wx * wy slots and the trail's used entries, nothing in between.
 //          The resample copies the name, so copies share a table; a map update that changes
 //          a table another particle also names writes the result to a free table the particle
 //          then names (copy on write: a shared table is never written).
@@ -148,7 +151,7 @@ struct LocalMaps {
     int2* ctr;                           // per table: window centre tile (DM_LM_UNSET: an empty table)
     uint32_t* slot;                      // per table: S page ids
     float2* page;                        // per page: 64 cells {mean, stdev}, row-major (m & 7) + 8 (n & 7)
-    uint32_t S, wx, wy, hx;              // S: words per table row (window slots + 4 V)
+    uint32_t S, wx, wy, hx;              // S: words per table row (dm_lm_row_words(wx wy, V))
     uint32_t hy, V;                      // V: trail entries per table (the last 4 V words of a row)
     uint64_t mx, my;                     // lm_magic(wx), lm_magic(wy)
     // --- the map update and the collection only
@@ -190,7 +193,8 @@ struct alignas(8) MapPayPage {
 };
 static_assert(sizeof(MapPayPage) == 528, "payload page");
 constexpr uint32_t kPayTrail = 0x80000000u;
-// a table row's word lm_trail_off - 2 (window padding): kLmShadow when the map holds its own
+// a table row's word lm_trail_off - 2 (the first of the two bookkeeping words every row
+// reserves after its window's slots, dm_lm_row_words): kLmShadow when the map holds its own
 // copy of a cell the shared grid covers (lookups then ask the particle's cells first)
 constexpr uint32_t kLmShadow = 1u;
 // the tables' pool holds 2 x cap tables: at most n <= cap are named by a particle, so at least

@@ -1897,9 +1897,10 @@ __device__ __forceinline__ bool lm_in(int32_t a, int32_t c, uint32_t h)
 
 // ---- the trail (eslam_internal.h LocalMaps; the oracle's lm_trail_* and lm_recentre): a
 // table's tiles outside its window, V entries {a, b, page, -} closing its row.  The last word
-// before them (window padding: (2h + 1)^2 is odd, so there always is one) holds the trail's
-// high-water mark hw (DM_LM_NONE: 0): entries from hw on are empty and are neither read nor
-// copied (their words may be stale)
+// before them holds the trail's high-water mark hw (DM_LM_NONE: 0): entries from hw on are
+// empty and are neither read nor copied (their words may be stale).  The word before that is
+// the shadow flag.  Neither is a window slot: dm_lm_row_words reserves both after the
+// (2 hx + 1)(2 hy + 1) slots whatever the parities of hx and hy
 __device__ __forceinline__ uint32_t lm_trail_off(const LocalMaps& lm) { return lm.S - 4u * lm.V; }
 __device__ __forceinline__ uint32_t lm_hw_word(uint32_t w) { return w == DM_LM_NONE ? 0u : w; }
 __device__ __forceinline__ int32_t lm_cheb(int32_t a, int32_t b, int32_t na, int32_t nb)
@@ -2229,17 +2230,18 @@ __global__ void __launch_bounds__(kBlock) k_pg_clear(uint8_t* __restrict__ mark,
         m4[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// one wave per table (grid-stride): its lanes walk the slots, then the trail's pages
+// one wave per table (grid-stride): its lanes walk the window's wx * wy slots (not the
+// bookkeeping words after them, which are no page ids), then the trail's pages
 __global__ void __launch_bounds__(kBlock) k_pg_mark(LocalMaps lm, const uint32_t* __restrict__ ref, const uint32_t* __restrict__ gate)
 {
     if (!*gate) return;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nw = (uint64_t)gridDim.x * kWaves;
-    const uint32_t toff = lm.S - 4u * lm.V;
+    const uint32_t W = lm.wx * lm.wy, toff = lm.S - 4u * lm.V;
     for (uint64_t t = (uint64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); t < lm.ntables; t += nw) {
         if (ref[t] == 0u) continue;
         const uint32_t* sl = lm.slot + t * lm.S;
-        for (uint32_t s = lane; s < toff; s += 64u) {
+        for (uint32_t s = lane; s < W; s += 64u) {
             const uint32_t p = sl[s];
             if (p != DM_LM_NONE) lm.mark[p] = 1u;
         }
@@ -4643,10 +4645,10 @@ __global__ void __launch_bounds__(kBlock) k_pay_hdr(const DevState s0, const Dev
         const uint32_t X = st.sid[i];
         const bool share = pay_shares(send, j, seg);
         const uint32_t* row = lm.slot + (uint64_t)X * lm.S;
-        const uint32_t toff = lm.S - 4u * lm.V;
+        const uint32_t W = lm.wx * lm.wy, toff = lm.S - 4u * lm.V;
         uint32_t c = 0;
-        if (!share) {
-            for (uint32_t s = lane; s < toff; s += 64u) c += row[s] != DM_LM_NONE ? 1u : 0u;
+        if (!share) {                                    // the window's slots and the trail's used entries
+            for (uint32_t s = lane; s < W; s += 64u) c += row[s] != DM_LM_NONE ? 1u : 0u;
             const uint32_t hw = lm_hw_word(row[toff - 1u]);
             for (uint32_t e = lane; e < hw; e += 64u) c += row[toff + 4u * e + 2u] != DM_LM_NONE ? 1u : 0u;
             c = wave_sum_u32(c);
@@ -4677,17 +4679,17 @@ __global__ void __launch_bounds__(kBlock) k_pay_pack(const DevState s0, const De
         const uint64_t i = (send[j].src >> 8) - gbase;
         const uint32_t X = st.sid[i];
         const uint32_t* row = lm.slot + (uint64_t)X * lm.S;
-        const uint32_t toff = lm.S - 4u * lm.V;
+        const uint32_t W = lm.wx * lm.wy, toff = lm.S - 4u * lm.V;
         uint64_t q = off[j];
         const uint32_t hw = lm_hw_word(row[toff - 1u]);
-        for (uint32_t s = 0; s < toff + hw; ++s) {
-            const bool tr = s >= toff;
-            const uint32_t p = tr ? row[toff + 4u * (s - toff) + 2u] : row[s];
+        for (uint32_t s = 0; s < W + hw; ++s) {          // k_pay_hdr's walk: npg pages
+            const bool tr = s >= W;
+            const uint32_t p = tr ? row[toff + 4u * (s - W) + 2u] : row[s];
             if (p == DM_LM_NONE) continue;
             if (lane == 0) {
-                pay[q].slot = tr ? (kPayTrail | (s - toff)) : s;
-                pay[q].a = tr ? (int32_t)row[toff + 4u * (s - toff)] : 0;
-                pay[q].b = tr ? (int32_t)row[toff + 4u * (s - toff) + 1u] : 0;
+                pay[q].slot = tr ? (kPayTrail | (s - W)) : s;
+                pay[q].a = tr ? (int32_t)row[toff + 4u * (s - W)] : 0;
+                pay[q].b = tr ? (int32_t)row[toff + 4u * (s - W) + 1u] : 0;
                 pay[q].pad = 0;
             }
             pay[q].cell[lane] = lm.page[(uint64_t)p * DM_LM_PAGE_CELLS + lane];

@@ -30,7 +30,7 @@ struct SnapArgs {
     const uint32_t* sid;                 // the current state buffer's table names
     uint64_t n;                          // particles
     uint64_t T;                          // live tables (the page census and the packs)
-    uint32_t W, K, toff, pad;            // window slots; keys per table (W + V); trail offset
+    uint32_t W, K, toff;                 // window slots; keys per table (W + V); trail offset
     uint32_t tbase, pbase;               // a sharded save: the compact ids of this rank's first table and page
 };
 
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(kBlock) k_snap_pack_tables(SnapArgs a, uint64_
         uint32_t v = 0u;
         if (q == 0u) v = (uint32_t)ctr.x;
         else if (q == 1u) v = (uint32_t)ctr.y;
-        else if (q == 2u) v = (a.pad >= 2u && row[a.toff - 2u] == kLmShadow) ? 1u : 0u;
+        else if (q == 2u) v = row[a.toff - 2u] == kLmShadow ? 1u : 0u;
         else if (q == 3u) v = hw;
         else if (q < 4u + a.W) {
             const uint32_t p = row[q - 4u];
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(kBlock) k_snap_unpack_tables(SnapArgs a, uint6
         if (q < a.W) v = r[4u + q];
         else if (q < a.toff) {
             if (q == a.toff - 1u) v = hw ? hw : DM_LM_NONE;
-            else if (q == a.toff - 2u && a.pad >= 2u) v = r[2] ? kLmShadow : DM_LM_NONE;
+            else if (q == a.toff - 2u) v = r[2] ? kLmShadow : DM_LM_NONE;
         } else {
             const uint32_t e = (q - a.toff) >> 2, f = (q - a.toff) & 3u;
             if (e < hw && f < 3u) v = r[4u + a.W + 3u * e + f];
@@ -361,7 +361,6 @@ SnapArgs snap_args(const LocalMaps* lm, const SnapCensus* c, const uint32_t* sid
     a.W = lm->wx * lm->wy;
     a.K = a.W + lm->V;
     a.toff = lm->S - 4u * lm->V;
-    a.pad = a.toff - a.W;
     return a;
 }
 

@@ -10,7 +10,16 @@ import eslam_abi as A
 import synthetic as S
 
 FIELDS = ("x", "y", "orientation", "zpos", "zsigma", "weight", "mprob", "floating", "n_contact_points")
-SCENARIOS = ("forced", "natural", "upload", "hash", "config3", "config4", "maps", "edit", "records", "heirloom", "chunks")
+SCENARIOS = ("forced", "natural", "upload", "hash", "config3", "config4", "maps", "edit", "records", "heirloom", "chunks",
+             "maps_rect", "maps_rect_trail", "maps_sq_trail")
+# `maps` on grids that are square in neither sense (rect_grids.py): maps_rect on the 150 x 110
+# grid of 0.10 x 0.08 m cells (a 9 x 11-tile window) with a scan reaching back over the mapped
+# cells, so migrating maps carry the shadow flag; maps_rect_trail on the empty prior of the same
+# grid rotated by 0.7 rad, a trail of 16 and a walk that moves mapped tiles out of the window, so
+# migrating maps carry trail entries; maps_sq_trail the same on 0.10 x 0.10 m cells
+MAPS_SCENARIOS = ("maps", "maps_rect", "maps_rect_trail", "maps_sq_trail")
+TRAIL_SCENARIOS = ("maps_rect_trail", "maps_sq_trail")
+TRAIL_STEPS, TRAIL_DX, TRAIL_YAW = 24, 0.05, 0.7
 EDIT_GLOBAL = (0, 37)                            # edit: the particles one rank edits
 CONFIG3_STEPS = 3
 MAP_SAMPLES = 64                                 # config4: particles whose maps are compared
@@ -26,8 +35,14 @@ def scenario_config(name, n_global):
     cfg = A.default_config()
     cfg.seed = 1234
     cfg.flags |= A.FLAG_RECORD_ANCESTORS
-    if name in ("forced", "config3", "config4", "maps", "burst", "edit", "getter0", "records", "heirloom", "chunks"):
+    if name in ("forced", "config3", "config4", "burst", "edit", "getter0", "records", "heirloom", "chunks") + MAPS_SCENARIOS:
         S.bench_config(cfg, n_global)
+        if name in MAPS_SCENARIOS and name != "maps":
+            cfg.flags |= A.FLAG_PARTICLE_MAPS
+            cfg.local_map_pages = 48             # the copies of the mapped cells the scan reaches
+            if name in TRAIL_SCENARIOS:
+                cfg.local_map_trail = 16
+                cfg.local_map_pages = 160        # ~35 tiles a particle (the scan fills the window's rear) and its copies' pages
         if name == "chunks":                     # an explicit summation chunk (eslam_config.sum_chunk_rows)
             cfg.sum_chunk_rows = 3
         if name == "config3":
@@ -68,6 +83,15 @@ def scenario_grid(name):
         return S.unmapped_beyond(S.rough_map(cells=120), 0.3)
     if name == "heirloom":                        # the empty prior: every cell is a particle's own
         return S.unmapped_beyond(S.rough_map(cells=120), -1e9)
+    if name == "maps_rect":
+        import rect_grids as G
+        return G.rect_prior("beyond", (0.10, 0.08))
+    if name == "maps_rect_trail":
+        import rect_grids as G
+        return G.rect_prior("empty", (0.10, 0.08), yaw=TRAIL_YAW)
+    if name == "maps_sq_trail":
+        import rect_grids as G
+        return G.rotated(S.unmapped_beyond(S.rough_map(cells=150), -1e9), yaw=TRAIL_YAW)
     return S.rough_map(cells=120) if name not in ("forced", "burst", "edit", "getter0", "records") else S.rough_map(cells=120, multi=False)
 
 
@@ -242,7 +266,7 @@ def run_scenario(f, name, n_global, lo, hi, steps=6, info_fn=None):
         _snap(rec, "res", f, True)
     elif name == "hash":
         f.init_pose([0.0, 0.0, 0.18], [1.0, 0.0, 0.0, 0.0])       # SurfaceHash::create + init(N, hash)
-    elif name == "maps":
+    elif name in MAPS_SCENARIOS:
         f.init_gaussian(hi - lo, [0.0, 0.0, 0.0], [0.05, 0.05, 0.02], 0.18, 0.05)
     else:
         sigma = [0.1, 0.1, 0.1] if name == "forced" else [0.6, 0.6, 0.3]
@@ -272,10 +296,19 @@ def run_scenario(f, name, n_global, lo, hi, steps=6, info_fn=None):
     if name == "hash":
         from hash_util import slope_stream
         stream = slope_stream(steps)
+    elif name in TRAIL_SCENARIOS:                # straight ahead: both window axes of the rotated grid move
+        stream = S.step_stream(TRAIL_STEPS, dx=TRAIL_DX, dyaw=0.0, tilt=True)
     else:
-        stream = S.step_stream(steps, tilt=(name in ("natural", "maps")))
-    scan = S.scan_patches() if name == "maps" else None
-    probe = S.scan_patches(z=-0.15) if name == "maps" else None
+        stream = S.step_stream(steps, tilt=(name in ("natural",) + MAPS_SCENARIOS))
+    scan = probe = None
+    if name == "maps":
+        scan, probe = S.scan_patches(), S.scan_patches(z=-0.15)
+    elif name == "maps_rect":                    # reaching back over the cells the shared grid covers
+        scan = S.scan_patches(nx=10, ny=6, x0=-0.9, x1=0.95)
+        probe = S.scan_patches(nx=10, ny=6, x0=-0.9, x1=0.95, z=-0.15)
+    elif name in TRAIL_SCENARIOS:                # to the window's rear and sides: the tiles it leaves hold pages
+        scan = S.scan_patches(nx=12, ny=8, x0=-2.6, x1=0.95, y0=-1.4, y1=1.4)
+        probe = S.scan_patches(nx=12, ny=8, x0=-2.6, x1=0.95, y0=-1.4, y1=1.4, z=-0.15)
     for k, st in enumerate(stream):
         if name == "edit" and k == 2:
             edit_particles(f, lo, hi)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_ffi as O
-from dist_scenarios import run_scenario, scenario_config
+from dist_scenarios import TRAIL_SCENARIOS, run_scenario, scenario_config, scenario_grid
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -66,6 +66,22 @@ def assert_same(got, want, label):
             f"{label} {key}: differs at {np.count_nonzero(g != w)} entries"
 
 
+def trail_tiles(name, rec):
+    """the cells of the particles' final maps that lie outside the window around their pose (the
+    last map update centred it there): cells of trail tiles -- the maps that migrated carried them"""
+    import math
+    import rect_grids as G
+    grid = scenario_grid(name)
+    hx, hy = (min(max(math.ceil(3.0 / (8.0 * s)), 1), 15) for s in grid.scale)
+    lx, ly = G.to_local(grid, rec["centroid/x"], rec["centroid/y"], rec["centroid/zpos"])
+    m, n = G.cell_coords(grid, lx, ly)
+    ca, cb = np.floor(m).astype(np.int64) >> 3, np.floor(n).astype(np.int64) >> 3
+    owner = np.repeat(np.arange(len(ca)), rec["maps/count"].astype(np.int64))
+    cells = rec["maps/cells"].astype(np.int64)
+    ta, tb = (cells % grid.width) >> 3, (cells // grid.width) >> 3
+    return int(np.count_nonzero((np.abs(ta - ca[owner]) > hx) | (np.abs(tb - cb[owner]) > hy)))
+
+
 def single_oracle(name, n_global):
     cfg = scenario_config(name, n_global)
     f = O.OracleFilter(cfg, O.SUM_CONTRACT)
@@ -77,12 +93,17 @@ def single_oracle(name, n_global):
                                                  ("hash", 1500, 3), ("maps", 3000, 2), ("maps", 1500, 3),
                                                  ("burst", 3000, 2), ("edit", 3000, 2), ("edit", 1000, 3),
                                                  ("heirloom", 2000, 2), ("heirloom", 1500, 3),
-                                                 ("chunks", 3000, 2), ("chunks", 1500, 3)])
+                                                 ("chunks", 3000, 2), ("chunks", 1500, 3),
+                                                 ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
+                                                 ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
+                                                 ("maps_sq_trail", 3000, 2)])
 def test_sharded_oracle_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("oracle", name, n_global, world, str(tmp_path)))
     assert_same(got, want, f"{name} N={n_global} world={world}")
-    if name == "maps":
+    if name in TRAIL_SCENARIOS:
+        assert trail_tiles(name, want) > 0
+    if name.startswith("maps"):
         # particles (and their own maps) did migrate between ranks
         import eslam_abi as A
         g = A.shard_bounds(n_global, world)

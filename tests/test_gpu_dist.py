@@ -17,7 +17,10 @@ pytestmark = pytest.mark.gpu
                                                  ("maps", 3000, 2), ("maps", 1500, 3),
                                                  ("burst", 5000, 2), ("burst", 7001, 3), ("edit", 3000, 2),
                                                  ("edit", 1500, 3), ("heirloom", 2000, 2), ("heirloom", 1500, 3),
-                                                 ("chunks", 3000, 2), ("chunks", 1500, 3)])
+                                                 ("chunks", 3000, 2), ("chunks", 1500, 3),
+                                                 ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
+                                                 ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
+                                                 ("maps_sq_trail", 3000, 2)])
 def test_sharded_gpu_gloo_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("gpu", name, n_global, world, str(tmp_path), mem="host", timeout=400))
@@ -68,7 +71,8 @@ def test_sharded_gpu_rccl_one_rank(oracle, tmp_path, name, n_global):
     assert_same(got, want, f"gpu rccl {name} N={n_global}")
 
 
-@pytest.mark.parametrize("name,n_global", [("forced", 5000), ("upload", 2000), ("hash", 3000), ("maps", 2000)])
+@pytest.mark.parametrize("name,n_global", [("forced", 5000), ("upload", 2000), ("hash", 3000), ("maps", 2000),
+                                           ("maps_rect", 2000)])
 def test_sharded_gpu_native_rccl_one_rank(oracle, tmp_path, name, n_global):
     want = single_oracle(name, n_global)
     got = merge(launch("gpu", name, n_global, 1, str(tmp_path), mem="rccl", timeout=400))

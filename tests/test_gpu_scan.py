@@ -163,7 +163,7 @@ def scan_readings():
     return [cs["depth_61x47"], cs["laser_1081"], cs["two_levels"]]
 
 
-@pytest.mark.parametrize("prior", ["rough", "unmapped"])
+@pytest.mark.parametrize("prior", ["rough", "unmapped", "rect", "rect_rotated"])
 def test_scan_drives_particle_maps(gpu_mod, oracle, prior):
     """per-particle maps: device-built patches into eslam_gpu_map_match / eslam_gpu_map_update over
     three steps == the oracle given the reference's patches (particles, sampled maps, counters)"""
@@ -173,6 +173,9 @@ def test_scan_drives_particle_maps(gpu_mod, oracle, prior):
     grid = S.rough_map(cells=120)
     if prior == "unmapped":                    # the scans' cells are the maps' own beyond x = 0.3
         grid = S.unmapped_beyond(grid, 0.3)
+    if prior.startswith("rect"):               # 150 x 110 cells of 0.10 x 0.08 m: a 9 x 11-tile window
+        import rect_grids
+        grid = rect_grids.rect_prior("beyond", (0.10, 0.08), yaw=0.3 if prior == "rect_rotated" else None)
     gpu = gpu_mod.GpuFilter(cfg)
     orc = O.OracleFilter(cfg, O.SUM_CONTRACT)
     for f in (gpu, orc):

@@ -56,6 +56,10 @@ def case_grid(case):
         return S.flat_map(cells=120)
     if case == "spread":
         return S.rough_map(cells=60)
+    if case in ("rect", "rect_rotated"):  # 150 x 110 cells of 0.10 x 0.08 m (tests/rect_grids.py)
+        import rect_grids
+        grid = rect_grids.rect_rough_map(150, 110, (0.10, 0.08))
+        return rotated(grid) if case == "rect_rotated" else grid
     grid = S.rough_map(cells=120)
     if case == "rough_heights":           # as test_shared_map_match_bit_exact builds them
         rng = np.random.default_rng(3)
@@ -85,7 +89,8 @@ def wide_scans():
     return [S.scan_patches(nx=12, ny=9, x0=-1.0, x1=2.5, y0=-1.5, y1=1.2, z=z) for z in (-0.18, -0.1, 0.4)]
 
 
-@pytest.mark.parametrize("case", ["flat", "rough", "rough_heights", "rotated_grid", "concentrated", "spread"])
+@pytest.mark.parametrize("case", ["flat", "rough", "rough_heights", "rotated_grid", "concentrated", "spread", "rect",
+                                  "rect_rotated"])
 def test_shared_map_update_bit_exact(gpu_mod, oracle, case):
     grid = case_grid(case)
     gpu, orc = make_pair(gpu_mod, grid, case_sigma(case))

@@ -47,9 +47,17 @@ def shared_update(grid, particles, st, n=N):
     return g.download()
 
 
-@pytest.mark.parametrize("case", ["beyond", "mapped", "empty", "heights"])
+def case_grid(case):
+    if case.startswith("rect_"):             # 150 x 110 cells of 0.10 x 0.08 m (tests/rect_grids.py), also rotated
+        import rect_grids
+        kind, _, rot = case[5:].partition("_")
+        return rect_grids.rect_prior(kind, (0.10, 0.08), yaw=0.7 if rot else None)
+    return R.prior_grid(case, 80)
+
+
+@pytest.mark.parametrize("case", ["beyond", "mapped", "empty", "heights", "rect_beyond", "rect_mapped", "rect_beyond_rotated"])
 def test_composed_grid_answers_like_the_particle(oracle, case):
-    grid = R.prior_grid(case, 80)
+    grid = case_grid(case)
     f, before, st = run_maps_oracle(grid)
     maps = {i: f.particle_map(i) for i in PROBES}
     f.update(st)

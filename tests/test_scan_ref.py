@@ -186,6 +186,78 @@ def test_case_list_preconditions(refs):
         assert key == sorted(key), name
 
 
+# ---- the reference's patches on a grid that is square in neither sense -----------------------
+@pytest.mark.parametrize("yaw", [None, 0.7])
+@pytest.mark.parametrize("name", ["laser_1081", "depth_61x47", "two_levels"])
+def test_reference_patches_on_a_rectangular_grid(oracle, name, yaw):
+    """The scan MLS has a square grid of its own; the map it is merged into need not be.  The
+    reference's patches, merged by the oracle into three particles' maps on 150 x 110 cells of
+    0.10 x 0.08 m (empty prior; identity and rotated global2local), fill the cells numpy's
+    floor((l - offset) / scale) names per axis, n * width + m, inside the particle's 9 x 11-tile
+    window; the patches beyond it are the ones counted as dropped.  A patch closer than 1e-6 of a
+    cell to a border may land on either side (the oracle multiplies by 1 / scale)."""
+    import eslam_abi as A
+    import oracle_ffi as O
+    import rect_grids as G
+    import synthetic as S
+    scale, (hx, hy) = G.RECT_CASES["9x11"]
+    grid = G.rect_prior("empty", scale, yaw=yaw)
+    scan, _ = SR.reference_patches(SR.cases()[name])
+    assert len(scan) > 0
+    pa = A.ParticleArrays(3)
+    pa.x[:], pa.y[:], pa.orientation[:] = [0.013, -0.431, 0.377], [0.021, 0.263, -0.305], [0.0, 0.4, -1.1]
+    pa.zpos[:], pa.zsigma[:], pa.weight[:] = 0.18, 0.05, 1.0 / 3
+    cfg = S.bench_config(A.default_config(), 3)
+    cfg.flags |= A.FLAG_PARTICLE_MAPS
+    orc = O.OracleFilter(cfg, O.SUM_CONTRACT)
+    orc.set_map(grid)
+    orc.upload(pa)
+    orc.map_update(scan)
+    sx = np.array([s.position[0] for s in scan])
+    sy = np.array([s.position[1] for s in scan])
+    sz = np.array([s.position[2] for s in scan])
+    dropped = filled = 0
+    for i in range(3):
+        co, sn = math.cos(pa.orientation[i]), math.sin(pa.orientation[i])
+        lx, ly = G.to_local(grid, co * sx - sn * sy + pa.x[i], sn * sx + co * sy + pa.y[i], sz + pa.zpos[i])
+        m, n = G.cell_coords(grid, lx, ly)
+        pm, pn = G.cell_coords(grid, *G.to_local(grid, pa.x[i], pa.y[i], pa.zpos[i]))
+        assert min(abs(pm - round(pm)), abs(pn - round(pn))) > 1e-6
+        ca, cb = int(math.floor(pm)) >> 3, int(math.floor(pn)) >> 3
+        fm, fn = np.floor(m).astype(np.int64), np.floor(n).astype(np.int64)
+        on = (fm >= 0) & (fm < grid.width) & (fn >= 0) & (fn < grid.height)
+        inside = on & (np.abs((fm >> 3) - ca) <= hx) & (np.abs((fn >> 3) - cb) <= hy)
+        sure = (np.abs(m - np.round(m)) > 1e-6) & (np.abs(n - np.round(n)) > 1e-6)
+        assert sure.mean() > 0.99
+        got = set(orc.particle_map(i)[0].astype(np.int64).tolist())
+        must = set((fn * grid.width + fm)[inside & sure].tolist())
+        may = set((fn * grid.width + fm)[inside].tolist())
+        for dm_ in (-1, 0, 1):                             # a border patch: the neighbouring cell
+            for dn in (-1, 0, 1):
+                may |= set(((fn + dn) * grid.width + fm + dm_)[on & ~sure].tolist())
+        assert must <= got <= may, (name, yaw, i, len(must - got), len(got - may))
+        dropped += int(np.count_nonzero(on & ~inside))
+        filled += len(got)
+    assert filled > 0
+    if all_sure(grid, pa, scan):                           # no patch near a border: the count is exact
+        assert orc.info().map_patches_dropped == dropped
+
+
+def all_sure(grid, pa, scan):
+    """every patch of every particle keeps off the cell borders (then the dropped count is exact)"""
+    import rect_grids as G
+    sx = np.array([s.position[0] for s in scan])
+    sy = np.array([s.position[1] for s in scan])
+    sz = np.array([s.position[2] for s in scan])
+    for i in range(pa.n):
+        co, sn = math.cos(pa.orientation[i]), math.sin(pa.orientation[i])
+        lx, ly = G.to_local(grid, co * sx - sn * sy + pa.x[i], sn * sx + co * sy + pa.y[i], sz + pa.zpos[i])
+        m, n = G.cell_coords(grid, lx, ly)
+        if not ((np.abs(m - np.round(m)) > 1e-6) & (np.abs(n - np.round(n)) > 1e-6)).all():
+            return False
+    return True
+
+
 # ---- closed forms --------------------------------------------------------------------------
 H = 0.37
 

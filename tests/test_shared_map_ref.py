@@ -6,6 +6,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import eslam_abi as A
 import shared_map_ref as R
@@ -143,6 +144,50 @@ def test_rotated_particle_and_grid_frame():
     shifted.g2l = [1.0, 0, 0, 1.0, 0, 1.0, 0, 0, 0, 0, 1.0, 0]
     g, _ = R.merge(shifted, pa, scan([(1.0, 0.0, 0.25, 0.1)]))
     assert len(cell(g, 2 * W + 2)) == 1 and int(g.cell_start[-1]) == 1
+
+
+RECT_W, RECT_H = 5, 3                   # a grid square in neither sense: 5 x 3 cells of 0.5 m x 2 m, origin (-1, -3)
+RECT_SCALE, RECT_OFF = (0.5, 2.0), (-1.0, -3.0)
+
+
+@pytest.mark.parametrize("m,n", [(0, 0), (4, 0), (1, 2), (4, 2), (3, 1)])
+@pytest.mark.parametrize("frame", ["identity", "shifted", "quarter_turn"])
+def test_rectangular_grid_with_rectangular_cells(m, n, frame):
+    """a patch aimed at the centre of cell (m, n) lands in cell n * width + m and nowhere else:
+    per axis floor((l - offset) / scale), with the axis' own offset, scale and extent (a cell
+    index below 5 in y or a y extent of 10 m would be another axis' numbers).  Through the
+    identity, a global2local shifted by (0.25, -1) and one turned by 90 degrees."""
+    cs = np.zeros(RECT_W * RECT_H + 1, np.uint32)
+    e = np.zeros(0, np.float32)
+    grid = A.GridArrays(RECT_W, RECT_H, RECT_SCALE, RECT_OFF, cs, e, e)
+    lx = RECT_OFF[0] + (m + 0.5) * RECT_SCALE[0]             # the cell's centre in the grid's frame
+    ly = RECT_OFF[1] + (n + 0.5) * RECT_SCALE[1]
+    if frame == "identity":
+        wx, wy = lx, ly
+    elif frame == "shifted":                                 # l = p + (0.25, -1)
+        grid.g2l = [1.0, 0, 0, 0.25, 0, 1.0, 0, -1.0, 0, 0, 1.0, 0]
+        wx, wy = lx - 0.25, ly + 1.0
+    else:                                                    # l = (p_y, -p_x): exact in floating point
+        grid.g2l = [0.0, 1.0, 0, 0, -1.0, 0.0, 0, 0, 0, 0, 1.0, 0]
+        wx, wy = -ly, lx
+    pa = particles([(wx - 0.125, wy, 0.0, 0.25, 0.125)])     # the patch sits 0.125 m ahead of the particle
+    g, info = R.merge(grid, pa, scan([(0.125, 0.0, 0.5, 0.25)]))
+    counts = np.diff(g.cell_start.astype(np.int64))
+    assert counts.tolist() == [1 if c == n * RECT_W + m else 0 for c in range(RECT_W * RECT_H)]
+    assert (g.width, g.height, g.scale, g.offset) == (RECT_W, RECT_H, RECT_SCALE, RECT_OFF)
+    assert (info.patches_placed, info.patches_off_grid, info.inserted) == (1, 0, 1)
+    assert bits(g.mean[0]) == bits(0.5 + 0.25) and bits(g.stdev[0]) == bits(math.sqrt(0.25 * 0.25 + 0.125 * 0.125))
+    # one cell past the grid's edge on either axis is off the grid, though inside the other axis' extent
+    for dx, dy in ((RECT_W * RECT_SCALE[0], 0.0), (0.0, RECT_H * RECT_SCALE[1])):
+        ox, oy = (lx + dx, ly + dy) if frame != "quarter_turn" else (lx, ly)
+        if frame == "quarter_turn":
+            far = particles([(-(ly + dy) - 0.125, lx + dx, 0.0, 0.25, 0.125)])
+        elif frame == "shifted":
+            far = particles([(ox - 0.25 - 0.125, oy + 1.0, 0.0, 0.25, 0.125)])
+        else:
+            far = particles([(ox - 0.125, oy, 0.0, 0.25, 0.125)])
+        g2, info2 = R.merge(grid, far, scan([(0.125, 0.0, 0.5, 0.25)]))
+        assert (info2.patches_placed, info2.patches_off_grid, int(g2.cell_start[-1])) == (0, 1, 0), (dx, dy)
 
 
 def test_merge_info_layout_matches_ctypes(tmp_path):
