@@ -1167,10 +1167,15 @@ int or_init_hash(or_filter* f, uint64_t n)
 
 typedef struct { float w; uint32_t i; } or_widx;
 
+/* (float weight, index) ascending; -0 == +0 (canonicalised by the caller).  std::sort is
+ * undefined when a weight is NaN: the build's rule puts a NaN of either sign
+ * after +inf, ties by index like any other, which makes this a total order */
 static int widx_cmp(const void* a, const void* b)
 {
     const or_widx* x = (const or_widx*)a;
     const or_widx* y = (const or_widx*)b;
+    const int xn = x->w != x->w, yn = y->w != y->w;
+    if (xn != yn) return xn - yn;
     if (x->w < y->w) return -1;
     if (y->w < x->w) return 1;
     return x->i < y->i ? -1 : (x->i > y->i);

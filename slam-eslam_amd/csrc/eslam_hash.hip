@@ -131,7 +131,8 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(const uint32_t* __rest
     }
 }
 
-// sort keys of (float weight, index): ascending float order, -0 == +0, ties by index
+// sort keys of (float weight, index): ascending float order, -0 == +0, ties by index; a NaN
+// of either sign takes the top key, after +inf
 __global__ void __launch_bounds__(kBlock) k_hash_keys(DevState s0, DevState s1, const Ctl* __restrict__ ctl, uint64_t n,
                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals)
 {
@@ -142,7 +143,7 @@ __global__ void __launch_bounds__(kBlock) k_hash_keys(DevState s0, DevState s1, 
     if (wf == 0.0f) wf = 0.0f;
     uint32_t b;
     __builtin_memcpy(&b, &wf, 4);
-    keys[i] = (b >> 31) ? ~b : (b | 0x80000000u);
+    keys[i] = (wf != wf) ? 0xffffffffu : ((b >> 31) ? ~b : (b | 0x80000000u));
     vals[i] = (uint32_t)i;
 }
 

@@ -4268,7 +4268,8 @@ __global__ void __launch_bounds__(kBlock) k_init_gaussian(DevState s0, uint64_t 
 
 // ---------------------------------------------------------------------------------------
 // ParticleFilter::getBestParticleIndex (src/ParticleFilter.hpp:160-173): first index of the
-// maximum weight; NaN never compares greater.  out[0] = max ordered key, out[1] = index.
+// maximum weight; NaN never compares greater, and -0 == +0 (the reference's `weight > best`):
+// the zero's sign is dropped before the ordered key.  out[0] = max ordered key, out[1] = index.
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_best_max(DevState s0, DevState s1, uint64_t n, const Ctl* __restrict__ ctl,
                                                      uint64_t* out)
@@ -4276,7 +4277,8 @@ __global__ void __launch_bounds__(kBlock) k_best_max(DevState s0, DevState s1, u
     const DevState st = (ctl->base ^ ctl->flip) ? s1 : s0;
     uint64_t best = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const double w = st.w[i];
+        double w = st.w[i];
+        if (w == 0.0) w = 0.0;
         if (w == w) { const uint64_t k = order_key(w); best = best > k ? best : k; }
     }
     for (int o = 32; o >= 1; o >>= 1) { const uint64_t t = __shfl_xor(best, o, 64); best = best > t ? best : t; }
@@ -4290,7 +4292,8 @@ __global__ void __launch_bounds__(kBlock) k_best_index(DevState s0, DevState s1,
     const uint64_t key = out[0];
     uint64_t idx = ~0ull;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const double w = st.w[i];
+        double w = st.w[i];
+        if (w == 0.0) w = 0.0;
         if (w == w && order_key(w) == key) { idx = i < idx ? i : idx; break; }
     }
     for (int o = 32; o >= 1; o >>= 1) { const uint64_t t = __shfl_xor(idx, o, 64); idx = idx < t ? idx : t; }

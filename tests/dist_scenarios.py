@@ -11,7 +11,7 @@ import synthetic as S
 
 FIELDS = ("x", "y", "orientation", "zpos", "zsigma", "weight", "mprob", "floating", "n_contact_points")
 SCENARIOS = ("forced", "natural", "upload", "hash", "config3", "config4", "maps", "edit", "records", "heirloom", "chunks",
-             "maps_rect", "maps_rect_trail", "maps_sq_trail")
+             "maps_rect", "maps_rect_trail", "maps_sq_trail", "hash_edges")
 # `maps` on grids that are square in neither sense (rect_grids.py): maps_rect on the 150 x 110
 # grid of 0.10 x 0.08 m cells (a 9 x 11-tile window) with a scan reaching back over the mapped
 # cells, so migrating maps carry the shadow flag; maps_rect_trail on the empty prior of the same
@@ -30,6 +30,13 @@ def scenario_config(name, n_global):
     if name == "hash":                           # useHash: init from the hash, respawn every 2nd step
         from hash_util import hash_config
         cfg = hash_config(n_global, steps=8, bins=20, period=2, percentage=0.2)
+        cfg.seed = 1234
+        return cfg
+    if name == "hash_edges":
+        # the respawn replaces 90 %: replace_count exceeds every shard, so a rank contributes
+        # all its (key, index) pairs, cnt[r] = n_r (hash_edges_zeros, hash_edges_arrays)
+        from hash_util import hash_config
+        cfg = hash_config(n_global, steps=8, bins=20, period=1, percentage=0.9)
         cfg.seed = 1234
         return cfg
     cfg = A.default_config()
@@ -72,7 +79,7 @@ def scenario_config(name, n_global):
 
 
 def scenario_grid(name):
-    if name == "hash":
+    if name in ("hash", "hash_edges"):
         from hash_util import hash_grid
         return hash_grid(cells=60)
     if name == "config3":
@@ -151,6 +158,47 @@ def upload_arrays(n_global, lo, hi):
     pa.mprob[:] = 1.0
     pa.floating[:] = 1
     pa.n_contact_points[:] = 0
+    out = A.ParticleArrays(hi - lo)
+    for f in FIELDS:
+        getattr(out, f)[:] = getattr(pa, f)[lo:hi]
+    return out
+
+
+def hash_edges_zeros(n_global):
+    """hash_edges: the global indices of the -0.0 (on the first rank) and of the +0.0 (on the
+    last one) of the zero pair, whose other weights are negative: the best particle is the -0.0"""
+    return 5, n_global - 3
+
+
+def hash_edges_arrays(n_global, lo, hi, which):
+    """The shard [lo, hi) of hash_edges' uploads.  which = "zero_pair": negative weights but a
+    -0.0 and a +0.0 on different ranks.  which = "mixed": one set at the edges of the respawn
+    order's key (float(weight), index) -- zeros of both signs spread over the ranks, doubles
+    1 + j 2^-40 that are one float, the float rounding ties 1 + 2^-24 and 1 + 3 2^-24,
+    float-denormal-range j 2^-140 and 2^-151 (a float zero), random dyadic weights -- with the
+    maximum 1.5 twice, on different ranks."""
+    rng = np.random.default_rng(n_global)
+    pa = A.ParticleArrays(n_global)
+    pa.x[:] = rng.normal(0, 0.2, n_global)
+    pa.y[:] = rng.normal(0, 0.2, n_global)
+    pa.orientation[:] = rng.normal(0, 0.1, n_global)
+    pa.zpos[:] = 0.18
+    pa.zsigma[:] = 0.25
+    pa.mprob[:] = 1.0
+    j = np.arange(n_global)
+    if which == "zero_pair":
+        w = -(1.0 + (j * 7 % 13)) * 2.0 ** -6
+        a, b = hash_edges_zeros(n_global)
+        w[a], w[b] = -0.0, 0.0
+    else:
+        u = 2.0 ** -24
+        kinds = [np.where(j % 2 == 0, -0.0, 0.0), 1.0 + j * 2.0 ** -40, np.where(j % 3 == 0, 1 + u, 1 + 3 * u),
+                 (j % 4000) * 2.0 ** -140, np.full(n_global, 2.0 ** -151),
+                 rng.integers(0, 1 << 20, n_global) * 2.0 ** -30]
+        pick = rng.integers(0, len(kinds), n_global)
+        w = np.choose(pick, kinds)
+        w[[n_global // 5, (2 * n_global) // 3]] = 1.5
+    pa.weight[:] = w
     out = A.ParticleArrays(hi - lo)
     for f in FIELDS:
         getattr(out, f)[:] = getattr(pa, f)[lo:hi]
@@ -266,6 +314,23 @@ def run_scenario(f, name, n_global, lo, hi, steps=6, info_fn=None):
         _snap(rec, "res", f, True)
     elif name == "hash":
         f.init_pose([0.0, 0.0, 0.18], [1.0, 0.0, 0.0, 0.0])       # SurfaceHash::create + init(N, hash)
+    elif name == "hash_edges":
+        from hash_util import slope_stream
+        f.init_pose([0.0, 0.0, 0.18], [1.0, 0.0, 0.0, 0.0])
+        f.upload(hash_edges_arrays(n_global, lo, hi, "zero_pair"))
+        rec["best_zero"] = np.array([f.best_index()])
+        f.upload(hash_edges_arrays(n_global, lo, hi, "mixed"))
+        rec["best0"] = np.array([f.best_index()])
+        for k, st in enumerate(slope_stream(2)):                  # period 1: both projects respawn
+            f.project(st)
+            _snap(rec, f"p{k}", f, False)
+            f.update(st)
+            info = info_fn(f)
+            _info(rec, f"s{k}", info)
+            _snap(rec, f"s{k}", f, bool(info.resampled))
+        rec["best"] = np.array([f.best_index()])
+        rec["rng"] = np.array([f.rng_state().minstd_x, f.rng_state().libc_rand_pos])
+        return rec
     elif name in MAPS_SCENARIOS:
         f.init_gaussian(hi - lo, [0.0, 0.0, 0.0], [0.05, 0.05, 0.02], 0.18, 0.05)
     else:

@@ -82,6 +82,21 @@ def trail_tiles(name, rec):
     return int(np.count_nonzero((np.abs(ta - ca[owner]) > hx) | (np.abs(tb - cb[owner]) > hy)))
 
 
+def check_hash_edges(want, n_global, world):
+    """hash_edges is what it is there for: the zero pair sits on two ranks and the -0.0 is the best
+    particle; the mixed set's best is the first of its two maxima; both respawns replace more
+    particles than the smallest shard holds, so that rank contributes all its pairs (cnt[r] = n_r)"""
+    import eslam_abi as A
+    from dist_scenarios import hash_edges_zeros, scenario_config
+    g = A.shard_bounds(n_global, world, scenario_config("hash_edges", n_global).sum_chunk_rows)
+    a, b = hash_edges_zeros(n_global)
+    assert a < g[1] and b >= g[world - 1]
+    assert int(want["best_zero"][0]) == a and int(want["best0"][0]) == n_global // 5
+    for k in range(2):
+        replaced = int(np.count_nonzero(want[f"p{k}/zsigma"] == 0.5))
+        assert replaced > min(np.diff(g)), (replaced, g)
+
+
 def single_oracle(name, n_global):
     cfg = scenario_config(name, n_global)
     f = O.OracleFilter(cfg, O.SUM_CONTRACT)
@@ -96,11 +111,14 @@ def single_oracle(name, n_global):
                                                  ("chunks", 3000, 2), ("chunks", 1500, 3),
                                                  ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
-                                                 ("maps_sq_trail", 3000, 2)])
+                                                 ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
+                                                 ("hash_edges", 1500, 3)])
 def test_sharded_oracle_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("oracle", name, n_global, world, str(tmp_path)))
     assert_same(got, want, f"{name} N={n_global} world={world}")
+    if name == "hash_edges":
+        check_hash_edges(want, n_global, world)
     if name in TRAIL_SCENARIOS:
         assert trail_tiles(name, want) > 0
     if name.startswith("maps"):

@@ -7,7 +7,7 @@ library's own RCCL communicator (eslam_gpu_set_comm_rccl)."""
 import numpy as np
 import pytest
 
-from test_dist_cpu import assert_same, launch, merge, single_oracle
+from test_dist_cpu import assert_same, check_hash_edges, launch, merge, single_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -20,11 +20,14 @@ pytestmark = pytest.mark.gpu
                                                  ("chunks", 3000, 2), ("chunks", 1500, 3),
                                                  ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
-                                                 ("maps_sq_trail", 3000, 2)])
+                                                 ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
+                                                 ("hash_edges", 1500, 3)])
 def test_sharded_gpu_gloo_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("gpu", name, n_global, world, str(tmp_path), mem="host", timeout=400))
     assert_same(got, want, f"gpu {name} N={n_global} world={world}")
+    if name == "hash_edges":
+        check_hash_edges(want, n_global, world)
 
 
 @pytest.mark.parametrize("world", [2, 3])

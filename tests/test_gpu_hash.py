@@ -1,6 +1,10 @@
 """SurfaceHash on the GPU against the oracle, bit for bit: the pose hash of
 SurfaceHash::create (sweep kernel), PoseEstimator::init(N, hash) and the sampleFromHash
-respawn inside the step (radix sort of the (float weight, index) pairs on the device)."""
+respawn inside the step (radix sort of the (float weight, index) pairs on the device).
+The respawn and getBestParticleIndex at the edge values of their orderings (signed zeros, float
+ties and denormals, overflow, NaN; replace_count 0, 1 and N; an empty bucket), against an
+independent restatement as well as the oracle: test_gpu_hash_edges.py (cases in
+hash_edge_cases.py, the restatement in hash_ref.py, the oracle against it in test_hash_ref.py)."""
 import numpy as np
 import pytest
 

@@ -116,3 +116,28 @@ def test_init_hash_and_respawn(oracle):
             replaced = max(replaced, int(np.count_nonzero(pa.zsigma == 0.5)))
         f.update(s)
     assert replaced > 0, "the slope feet should select a rare bucket and replace particles"
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 256, 257, 524288 + 257])
+def test_best_index_against_loop(oracle, n):
+    """or_best_index == the plain loop of getBestParticleIndex (hash_ref.best_index: the first
+    strictly greater weight wins, from -inf at index 0) at the weights where an ordered-key
+    maximum could differ: the maximum at the block edges and twice, zeros of both signs above
+    negative weights, all -inf, NaN (never picked), +inf and denormal doubles."""
+    import hash_edge_cases as E
+    import hash_ref as H
+    cfg = A.default_config()
+    cfg.particle_count = n
+    f = O.OracleFilter(cfg, O.SUM_CONTRACT)
+    for name, w in E.best_cases(n):
+        want = H.best_index(w.tolist())
+        if name == "neg_zero_first":
+            assert want == 0
+        if name == "pos_zero_first" and n > 1:
+            assert want == 0
+        if name == "max_twice":
+            assert want == min(3, n - 1)
+        if name in ("all_neg_inf", "all_nan"):
+            assert want == 0
+        f.upload(E.particles(w))
+        assert f.best_index() == want, name
