@@ -1654,6 +1654,88 @@ DM_FN uint64_t dm_count_draws_le(uint64_t c, uint64_t N, uint32_t xs, int shift)
     return cnt;
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* T_k <= c decided in integers                                                          */
+/* ------------------------------------------------------------------------------------ */
+/* The draw T_k = dm_fx_shift(((double)k + U_k) / N, shift), U_k = (x - 1) / M, M = 2147483646,
+ * x the minstd state of draw k, N < 2^32, approximates the real R_k = (k + u) 2^shift / N:
+ *   fl(u)   = u (1 + d1)                    |d1| <= 2^-53, so |fl(u) - u| <= 2^-53  (u < 1)
+ *   fl(k+.) = (k + fl(u)) (1 + d2)          |d2| <= 2^-53  (k and N convert exactly)
+ *   q       = fl(k+.) / N (1 + d3)          |d3| <= 2^-53
+ *   |q - (k + u) / N| <= (k + u) / N (2 2^-53 + 2^-106) + 2^-53 (1 + 2^-52) / N
+ *                     <  2^-53 (3 + 2^-51)                        ((k + u) / N < 1 <= N)
+ * q <= 1, so q 2^shift is exact and below dm_fx_shift's saturation; the truncation takes off
+ * less than 1:  |T_k - R_k| < B = 3 2^(shift-53) + 1 + 2^(shift-104)  (385.0..1 at shift 60,
+ * 769.0..1 at 61).  The margin m = 2^(shift-51) = 4 2^(shift-53) is above B from shift 54 on.
+ *
+ * T_k is non-decreasing in k: k + fl(u_k) <= k + 1 <= k + 1 + fl(u_{k+1}) (fl(u) lies in
+ * [0, 1]), k + 1 is representable, and rounding, the division by N > 0 and the truncation are
+ * monotone.  So #{k : T_k <= c} is a prefix length.
+ *
+ * With c N = k* 2^shift + rem (0 <= rem < 2^shift), c = (k* + rem / 2^shift) 2^shift / N and
+ *   R_{k*-1} <  c - rem / N               T_{k*-1} <= c for sure when rem >= m N
+ *   R_{k*+1} >= c + (2^shift - rem) / N   T_{k*+1} >  c for sure when 2^shift - rem > m N
+ * (and by monotonicity every draw below k* - 1 resp. above k* + 1 too), so the count is
+ * k* + [T_{k*} <= c], where
+ *   R_{k*} <= c - m  <=>  (x - 1) 2^shift <= (rem - m N) M     then T_{k*} < c
+ *   R_{k*} >  c + m  <=>  (x - 1) 2^shift >  (rem + m N) M     then T_{k*} > c
+ * Where draw k* - 1 or k* + 1 does not exist (k* = 0, k* = N - 1: the windows that
+ * dm_count_draws_le clamps) its condition is still applied; that only gives up certainty.
+ * Anything else -- an edge of the stratum within m, (x - 1) 2^shift inside
+ * ((rem - m N) M, (rem + m N) M], k* >= N, a shift outside [54, 61], c >= 2^62 -- is
+ * ambiguous, and the caller evaluates the draws (dm_count_draws_le).
+ * (x - 1) 2^shift has its low 32 bits zero, so comparing it with a 96-bit product L M needs
+ * only the product's upper 64 bits: A 2^32 <= P  <=>  A <= floor(P / 2^32).
+ * tests/c/check_draw_cmp.c checks the answers and B against the definition.               */
+#define DM_DRAW_GT 0
+#define DM_DRAW_LE 1
+#define DM_DRAW_AMBIGUOUS (-1)
+#define DM_DRAW_SHIFT_MIN 54
+#define DM_DRAW_SHIFT_MAX 61
+
+DM_FN int dm_draw_shift_ok(int shift) { return shift >= DM_DRAW_SHIFT_MIN && shift <= DM_DRAW_SHIFT_MAX; }
+DM_FN uint64_t dm_draw_margin(int shift) { return 1ull << (shift - 51); }
+
+/* c N = k* 2^shift + rem for N < 2^32, c < 2^62 and a shift dm_draw_shift_ok accepts (the
+ * two 32 x 32 products of the device's k* computation) */
+DM_FN void dm_draw_split(uint64_t c, uint64_t N, int shift, uint64_t* kstar, uint64_t* rem)
+{
+    const uint64_t lo = (uint64_t)(uint32_t)c * (uint32_t)N, hi = (c >> 32) * (uint64_t)(uint32_t)N;
+    const uint64_t top = hi + (lo >> 32);                   /* c N >> 32, < 2^62 */
+    const int s = (shift - 32) & 31;
+    *kstar = top >> s;
+    *rem = ((top & ((1ull << s) - 1ull)) << 32) | (uint64_t)(uint32_t)lo;
+}
+
+/* floor(L * 2147483646 / 2^32) for L < 2^62 */
+DM_FN uint64_t dm_mul_minstd_range_hi(uint64_t L)
+{
+    const uint64_t t = (uint64_t)(uint32_t)L * 2147483646u;
+    return (L >> 32) * 2147483646ull + (t >> 32);
+}
+
+/* the decision for draw k* (state x in [1, 2147483646]) from dm_draw_split's outputs; without
+ * branches, and x is not used when the answer is ambiguous for another reason */
+DM_FN int dm_draw_decide(uint64_t kstar, uint64_t rem, uint64_t N, uint32_t x, int shift)
+{
+    const uint64_t mN = N << ((shift - 51) & 31);           /* < 2^42 */
+    const int edge = (kstar >= N) | (rem < mN) | ((1ull << (shift & 63)) - rem <= mN);
+    const uint64_t a = (uint64_t)(x - 1u) << ((shift - 32) & 31);      /* (x - 1) 2^shift / 2^32 */
+    const int le = a <= dm_mul_minstd_range_hi(rem - mN);   /* (wraps when edge: unused) */
+    const int gt = a > dm_mul_minstd_range_hi(rem + mN);
+    return (edge | !(le | gt)) ? DM_DRAW_AMBIGUOUS : le;
+}
+
+/* is T_{k*} <= c, k* = floor(c N / 2^shift), x the minstd state of draw k*?  DM_DRAW_LE or
+ * DM_DRAW_GT only when that is certain and the count of draws <= c is k* + that answer */
+DM_FN int dm_draw_compare(uint64_t c, uint64_t N, uint32_t x, int shift)
+{
+    if (!dm_draw_shift_ok(shift) || (c >> 62) != 0 || N == 0 || (N >> 32) != 0) return DM_DRAW_AMBIGUOUS;
+    uint64_t kstar, rem;
+    dm_draw_split(c, N, shift, &kstar, &rem);
+    return dm_draw_decide(kstar, rem, N, x, shift);
+}
+
 
 /* trunc(v * 2^scale) as an unsigned 128-bit integer split in four 32-bit limbs.
  * v >= 0 finite.  Returns 1 if saturated (v * 2^scale >= 2^127).                        */

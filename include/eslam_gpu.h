@@ -556,6 +556,10 @@ int eslam_gpu_sync(eslam_ctx* ctx, eslam_update_info* info);
  * upload_particles starts over.  Testing only: polls before a wait gives up (default 2^18,
  * about 60 ms; 0 gives up at once, which forces the poisoned path).                        */
 int eslam_gpu_debug_set_spin_limit(eslam_ctx* ctx, uint32_t polls);
+/* Testing only: particles per thread of the one-GPU resample scan (1, 2, 4 or 8; 0 restores
+ * the rule by particle count).  The tile totals are exact integers, so the tile size never
+ * changes a result; the hook lets small filters run the instantiation of large ones.       */
+int eslam_gpu_debug_set_scan_items(eslam_ctx* ctx, uint32_t items);
 
 /* ---- ParticleFilter<T> API (src/ParticleFilter.hpp:34-173) ------------------------------ */
 int eslam_gpu_get_weights_sum(eslam_ctx* ctx, double* sum);          /* getWeightsSum :34-39     */

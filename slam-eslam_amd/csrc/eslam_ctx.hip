@@ -264,6 +264,7 @@ struct eslam_ctx {
     bool poisoned = false;                  // the particle set is undefined until re-initialised
     bool poison_pages = false;              // ... because the map pages ran out (kFaultPages)
     uint32_t spin_limit = kSpinLimit;       // polls of K3's cross-block waits (debug: 0 gives up at once)
+    uint32_t debug_scan_items = 0;          // particles per thread of the one-GPU K3 (debug; 0: scan_items(n))
     Dev<uint32_t> jump;
     uint32_t jump_n = 1;                    // A^n_global, cached
     uint64_t jump_n_for = 0;
@@ -2595,7 +2596,7 @@ static ScanParams scan_params(eslam_ctx* ctx, uint32_t phase_b, uint32_t normali
     sp.n_global = ctx->n_global;
     sp.phase_b = phase_b;
     sp.normalize = normalize;
-    sp.items = multi ? (uint32_t)kScanItems : scan_items(ctx->n);
+    sp.items = multi ? (uint32_t)kScanItems : (ctx->debug_scan_items ? ctx->debug_scan_items : scan_items(ctx->n));
     const uint64_t tile = (uint64_t)kBlock * sp.items;
     sp.ntiles = (uint32_t)((ctx->n + tile - 1) / tile);
     sp.pub_stride = ctx->pub_stride;
@@ -3175,6 +3176,14 @@ extern "C" int eslam_gpu_debug_set_spin_limit(eslam_ctx* ctx, uint32_t polls)
 {
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
     ctx->spin_limit = polls;
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_debug_set_scan_items(eslam_ctx* ctx, uint32_t items)
+{
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (items != 0 && items != 1 && items != 2 && items != 4 && items != (uint32_t)kScanItems) return ESLAM_ERR_INVALID_ARG;
+    ctx->debug_scan_items = items;
     return ESLAM_OK;
 }
 

@@ -182,6 +182,15 @@ __device__ uint32_t g_stamps_grid[3];    // gridDim.x of the last stamped K1 / K
 #else
 #define ESLAM_STAMP(arr, k) do { } while (0)
 #endif
+// Diagnostic builds only (-DESLAM_DRAW_STATS, tools/stamps.py): how many waves counted
+// stratified draws (wave_counts) and how many of them had to evaluate the draws.  Kept apart
+// from the stamps: the two atomics per wave on one address disturb the timeline.
+#ifdef ESLAM_DRAW_STATS
+__device__ uint32_t g_draw_waves[2];
+#define ESLAM_DRAW_WAVE(k) do { if ((threadIdx.x & 63u) == 0) atomicAdd(&g_draw_waves[(k)], 1u); } while (0)
+#else
+#define ESLAM_DRAW_WAVE(k) do { } while (0)
+#endif
 
 // ---------------------------------------------------------------------------------------
 // K1 kernel arguments by scalar load at the point of use.  K1 reads ~110 uniform values
@@ -3544,6 +3553,9 @@ __device__ __forceinline__ uint32_t draw_slot(uint32_t x) { return x + (x >> 3);
 template <int ITEMS> union K3Lds {
     double v[kBlock * ITEMS + kBlock * ITEMS / kSkew];
     uint64_t T[kWaves][wave_draws<ITEMS>() + wave_draws<ITEMS>() / 8];
+    // the draws' minstd states (wave_counts' integer path): a wave's row is the first half of
+    // its row of T, so a wave that falls back to T never touches another wave's states
+    uint32_t X[kWaves][2 * (wave_draws<ITEMS>() + wave_draws<ITEMS>() / 8)];
 };
 
 // Write the marks of the tile's segment starts (relative to the slice) and the row carries
@@ -3809,9 +3821,9 @@ __device__ __forceinline__ uint64_t count_from_window(uint32_t w, uint64_t dlo, 
 // (at most three) draws of its window there.  Heavy weights (more than kWaveChunks chunks of
 // draws): each target's window evaluated directly.
 template <int ITEMS>
-__device__ __forceinline__ void wave_counts(uint64_t base, uint64_t run, const uint64_t (&c)[ITEMS], uint64_t N, int shift,
-                                            uint32_t xs, const uint32_t* __restrict__ jt, uint64_t* sT,
-                                            uint64_t (&hi_r)[ITEMS], uint64_t& lo)
+__device__ __forceinline__ void wave_counts_fp(uint64_t base, uint64_t run, const uint64_t (&c)[ITEMS], uint64_t N, int shift,
+                                               uint32_t xs, const uint32_t* __restrict__ jt, uint64_t* sT,
+                                               uint64_t (&hi_r)[ITEMS], uint64_t& lo)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const double dN = (double)N, inv_N = 1.0 / dN;
@@ -3866,6 +3878,78 @@ __device__ __forceinline__ void wave_counts(uint64_t base, uint64_t run, const u
         const uint64_t prev = __shfl_up(hi_r[ITEMS - 1], 1, 64);
         lo = lane == 0 ? K0 : prev;
     }
+}
+
+// wave_counts_fp's results without evaluating a draw, when every target of the wave is decided
+// by dm_draw_decide (eslam_detmath.h: the count of a decided target is k* + [T_k* <= c], what
+// the three-draw window gives).  The wave stages only the minstd states x_k of its draws, one
+// 32-bit word each, and a target reads the state of its k*.  Taken when the wave's draws fit
+// one chunk and the shift is one the decision supports; a wave with an ambiguous target in any
+// lane (a target within the rounding margin of a draw or of a stratum edge: equal weights
+// k / N, the filter's last target) runs wave_counts_fp from its start instead.
+template <int ITEMS>
+__device__ __forceinline__ void wave_counts(uint64_t base, uint64_t run, const uint64_t (&c)[ITEMS], uint64_t N, int shift,
+                                            uint32_t xs, const uint32_t* __restrict__ jt, uint64_t* sT, uint32_t* sX,
+                                            uint64_t (&hi_r)[ITEMS], uint64_t& lo)
+{
+    // (N < 2^32 - 1 as everywhere in the draw counting: the context refuses larger filters)
+    ESLAM_DRAW_WAVE(0);
+    if (dm_draw_shift_ok(shift)) {                           // wave-uniform: the shift is scalar
+        const uint32_t lane = threadIdx.x & 63u;
+        auto rfl64 = [](uint64_t v) {
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+            const uint32_t lo_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+            return ((uint64_t)hi << 32) | (uint64_t)lo_;
+        };
+        const uint64_t wlo = rfl64(__shfl(base, 0, 64)), whi = rfl64(__shfl(base + run, 63, 64));
+        const uint64_t ks_lo = kstar_of(wlo, N, shift), ks_hi = kstar_of(whi, N, shift);
+        const uint64_t dlo = ks_lo >= 1 ? ks_lo - 1 : 0;
+        const uint64_t dhi = ks_hi + 2 < N ? ks_hi + 2 : N;
+        if (dlo < dhi && dhi - dlo <= (uint64_t)wave_draws<ITEMS>()) {
+            if (dlo + lane < dhi) {
+                const uint32_t a64 = jt[64];
+                uint32_t x = dm_mulmod31(dm_mulmod31(jump_pow(jt, dlo + 1), xs), jt[lane]);
+#pragma unroll 4
+                for (uint64_t k = dlo + lane; k < dhi; k += 64) {
+                    sX[draw_slot((uint32_t)(k - dlo))] = x;
+                    x = dm_mulmod31(x, a64);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // every target lies in [wlo, whi], so its k* lies in [ks_lo, ks_hi], inside
+            // [dlo, dhi) unless k* >= N (ambiguous: slot 0 read, not used)
+            // (a decided target has k* < N < 2^32: 32-bit slots and counts)
+            bool amb = false;
+            uint32_t cnt[ITEMS + 1];
+            const uint32_t span = (uint32_t)(dhi - dlo);
+#pragma unroll
+            for (int r = 0; r <= ITEMS; ++r) {
+                uint64_t ks, rem;
+                dm_draw_split(r < ITEMS ? base + c[r] : wlo, N, shift, &ks, &rem);
+                const uint32_t rel = (uint32_t)ks - (uint32_t)dlo;
+                const bool staged = rel < span;
+                const uint32_t x = sX[draw_slot(staged ? rel : 0u)];
+                const int d = dm_draw_decide(ks, rem, N, x, shift);
+                amb |= !staged | (d < 0);
+                cnt[r] = (uint32_t)ks + (d > 0 ? 1u : 0u);
+            }
+            if (__builtin_amdgcn_ballot_w64(amb) == 0) {
+#pragma unroll
+                for (int r = 0; r < ITEMS; ++r) hi_r[r] = cnt[r];
+                const uint64_t prev = __shfl_up(hi_r[ITEMS - 1], 1, 64);
+                lo = lane == 0 ? cnt[ITEMS] : prev;
+                return;
+            }
+            // the states are read before wave_counts_fp stores draws over them
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+    ESLAM_DRAW_WAVE(1);
+    wave_counts_fp<ITEMS>(base, run, c, N, shift, xs, jt, sT, hi_r, lo);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3993,7 +4077,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ITE
     const uint64_t i0 = t0 + (uint64_t)tid * ITEMS;
     uint64_t hi_r[ITEMS];
     uint64_t lo;
-    wave_counts<ITEMS>(base, run, c, N, shift, xs, jt, s_u.T[wave], hi_r, lo);
+    wave_counts<ITEMS>(base, run, c, N, shift, xs, jt, s_u.T[wave], s_u.X[wave], hi_r, lo);
     ESLAM_STAMP(g_stamps_k3, 6);
     if (i0 == 0) lo = 0;
     // each item's segment [lo, hi) marked as it is found (no arrays of segments held)
@@ -4082,7 +4166,7 @@ __global__ void __launch_bounds__(kBlock) k_segments_multi(DevState s0, DevState
     const uint64_t i0 = t0 + (uint64_t)tid * kScanItems;
     uint64_t hi_r[kScanItems];
     uint64_t lo;
-    wave_counts<kScanItems>(base, run, c, N, shift, ctl->minstd_start, jt, s_u.T[tid >> 6], hi_r, lo);
+    wave_counts<kScanItems>(base, run, c, N, shift, ctl->minstd_start, jt, s_u.T[tid >> 6], s_u.X[tid >> 6], hi_r, lo);
     if (i0 == 0) lo = O0;
     uint64_t seg_lo[kScanItems], seg_hi[kScanItems];
     uint32_t val[kScanItems];
@@ -5112,5 +5196,17 @@ extern "C" int64_t eslam_gpu_debug_stamps(int which, uint64_t* out, uint64_t blo
                                       : hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_mg), blocks * kStampSlots * 8);
     if (e != hipSuccess || hipMemcpyFromSymbol(grid, HIP_SYMBOL(g_stamps_grid), sizeof(grid)) != hipSuccess) return -1;
     return (int64_t)grid[which == 1 ? 0 : which == 3 ? 1 : 2];
+}
+#endif
+
+#ifdef ESLAM_DRAW_STATS
+// out[0] the waves that counted stratified draws (K3, k_segments_multi) since the counters were
+// last cleared, out[1] those of them that evaluated the draws (an ambiguous target, or no
+// integer path); clear != 0 zeroes the counters afterwards
+extern "C" int eslam_gpu_debug_draw_waves(uint32_t* out, int clear)
+{
+    const uint32_t zero[2] = {0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_draw_waves), 8) != hipSuccess) return -1;
+    return !clear || hipMemcpyToSymbol(HIP_SYMBOL(g_draw_waves), zero, 8) == hipSuccess ? 0 : -1;
 }
 #endif

@@ -99,6 +99,8 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_sync.argtypes = [vp, C.POINTER(A.UpdateInfo)]
     if hasattr(L, "eslam_gpu_debug_set_spin_limit"):     # absent from older builds (A/B runs)
         L.eslam_gpu_debug_set_spin_limit.argtypes = [vp, C.c_uint32]
+    if hasattr(L, "eslam_gpu_debug_set_scan_items"):     # absent from older builds (A/B runs)
+        L.eslam_gpu_debug_set_scan_items.argtypes = [vp, C.c_uint32]
     L.eslam_gpu_get_weights_sum.argtypes = [vp, dp]
     L.eslam_gpu_normalize_weights.argtypes = [vp, dp]
     L.eslam_gpu_resample.argtypes = [vp]
@@ -402,6 +404,11 @@ class GpuFilter:
     def debug_set_spin_limit(self, polls):
         """Testing only: polls of K3's cross-block waits before they give up (0: at once)."""
         self._check(self.L.eslam_gpu_debug_set_spin_limit(self.h, polls))
+
+    def debug_set_scan_items(self, items):
+        """Testing only: particles per thread of the one-GPU resample scan (1, 2, 4 or 8; 0: the
+        rule by particle count).  The tile size never changes a result."""
+        self._check(self.L.eslam_gpu_debug_set_scan_items(self.h, items))
 
     # -- ParticleFilter API ----------------------------------------------------------------
     def weights_sum(self):

@@ -1,5 +1,7 @@
 """Phase timeline of K1 and K3 from a -DESLAM_STAMPS diagnostic build (s_memrealtime, 10 ns):
     ESLAM_GPU_LIB=$PWD/slam-eslam_amd/lib/ab/lib_stamps.so python tools/stamps.py [particles] [warmup]
+(a build with -DESLAM_DRAW_STATS as well also reports how many waves of the last step counted
+their stratified draws in integers and how many evaluated them; its timeline is disturbed)
 Runs the bench workload (flat map, resample forced) for `warmup` steps plus one, then prints,
 per phase of the last step's K1 and K3 (the stamps are cleared before it, and the block
 counts are the launches' own), the median / max block duration and when the last block left
@@ -57,6 +59,10 @@ def main():
         f.step(st)
     f.sync()
     assert L.eslam_gpu_debug_stamps_clear() == 0  # the measured step's stamps only
+    stats = hasattr(L, "eslam_gpu_debug_draw_waves")       # a -DESLAM_DRAW_STATS build as well
+    waves = (C.c_uint32 * 2)()
+    if stats:
+        assert L.eslam_gpu_debug_draw_waves(waves, 1) == 0
     f.step(steps[-1])
     f.sync()
     buf = np.zeros((32768, 8), dtype=np.uint64)
@@ -64,6 +70,9 @@ def main():
         blocks = L.eslam_gpu_debug_stamps(which, buf.ctypes.data, 32768)
         assert blocks >= 0
         report(f"{label} at n={n} ({blocks} blocks launched)", buf.copy(), phases, min(blocks, 32768))
+    if stats:
+        assert L.eslam_gpu_debug_draw_waves(waves, 0) == 0
+        print(f"== draw counting of the last step: {waves[0]} waves, {waves[1]} of them evaluated their draws")
     f.close()
 
 
