@@ -1857,12 +1857,33 @@ DM_FN uint32_t dm_chunk_rows_cfg(uint64_t n_global, uint32_t fixed)
     return fixed ? fixed : dm_chunk_rows(n_global);
 }
 
-/* exponent e >= 1 with max_w < 2^e (weight scale of the A_n / B_n accumulators) */
+/* exponent e >= 1 with S < 2^e: the standalone resample's shift 61 - (e + 1) (its cumulative
+ * weights are compared unscaled with draws in [0, 1), so its exponent stays clamped)        */
 DM_FN int dm_weight_exp(double max_w)
 {
     if (!(max_w > 0.0) || !dm_isfinite(max_w)) return 1;
     int e = (int)((dm_bits(max_w) >> 52) & 0x7ff) - 1023 + 1;   /* 2^(e-1) <= max_w < 2^e */
     return e < 1 ? 1 : e;
+}
+
+/* The weight scale of the statistics (the A_n / B_n accumulators): e with 2^(e-1) <= max_w < 2^e,
+ * below 1 as well as above (a denormal max_w: DM_STAT_EXP_MIN; none positive and finite: 1).
+ * Sums of weights are taken in fixed point at scale DM_FX_SCALE - e, sums of squares of the
+ * weights scaled by 2^-e (dm_stat_sq) at DM_FX_SCALE, and the effective count is formed from
+ * the scaled sums S 2^-e and Q 2^-2e (both read at DM_FX_SCALE), so multiplying every weight
+ * by a power of two moves e and nothing else ("Weight scale").                  */
+#define DM_STAT_EXP_MIN (-1021)
+DM_FN int dm_stat_exp(double max_w)
+{
+    if (!(max_w > 0.0) || !dm_isfinite(max_w)) return 1;
+    int e = (int)((dm_bits(max_w) >> 52) & 0x7ff) - 1023 + 1;
+    return e < DM_STAT_EXP_MIN ? DM_STAT_EXP_MIN : e;
+}
+/* (w 2^-e)^2: the term of the standalone sum of squares */
+DM_FN double dm_stat_sq(double w, int e)
+{
+    const double v = dm_ldexp(w, -e);
+    return v * v;
 }
 
 /* weightingFunction(x, alpha, beta, gamma)  src/PoseEstimator.cpp:114-128 */

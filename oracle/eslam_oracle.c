@@ -1006,7 +1006,7 @@ int or_upload(or_filter* f, uint64_t n, const eslam_particles* p)
         if (comm_allgather(f, &mx, all, 8)) return ESLAM_ERR_COMM;
         for (int r = 0; r < f->comm.nranks; ++r) if (all[r] > mx) mx = all[r];
     }
-    f->wexp = dm_weight_exp(mx);
+    f->wexp = dm_stat_exp(mx);
     return 0;
 }
 
@@ -1385,7 +1385,8 @@ static void chunk_reduce(const double* vals, uint64_t vstride, const uint8_t* bu
 /* ---- updateWeights  src/PoseEstimator.cpp:257-352 ----------------------------------------- */
 typedef struct {
     double fw, f[DM_NBUCKETS];
-    double S, Q;          /* contract: sum of final weights and of their squares */
+    double S, Q;          /* contract: sum of final weights and of their squares, scaled by
+                             2^-wexp and 2^-2 wexp (dm_stat_exp) */
 } or_phase;
 
 static int or_update_weights(or_filter* f, const eslam_step_input* in, or_phase* ph)
@@ -1477,6 +1478,8 @@ static int or_update_weights(or_filter* f, const eslam_step_input* in, or_phase*
      * across ranks in one exchange (the device's per-rank statistics record) */
     or_acc accs[2 * DM_NBUCKETS + 1];
     memset(accs, 0, sizeof(accs));
+    /* the device's weighting kernel squares w * mprob unscaled (its per-particle loop is as it
+     * was): the squares are exact scalings of the scaled ones while they stay normal doubles */
     const int sa = DM_FX_SCALE - f->wexp, sb = DM_FX_SCALE - 2 * f->wexp;
     if (f->sum_mode == OR_SUM_CONTRACT) {
         chunk_reduce(sw_val, 1, NULL, 0, f->n, J, &accs[2 * DM_NBUCKETS], DM_FX_SCALE);
@@ -1519,8 +1522,8 @@ static int or_update_weights(or_filter* f, const eslam_step_input* in, or_phase*
     if (f->sum_mode == OR_SUM_CONTRACT) {
         double S = 0.0, Q = 0.0;
         for (int b = 0; b < DM_NBUCKETS; ++b) {
-            S = S + ph->f[b] * acc_value(&accs[b], sa);
-            Q = Q + (ph->f[b] * ph->f[b]) * acc_value(&accs[DM_NBUCKETS + b], sb);
+            S = S + ph->f[b] * acc_value(&accs[b], DM_FX_SCALE);
+            Q = Q + (ph->f[b] * ph->f[b]) * acc_value(&accs[DM_NBUCKETS + b], DM_FX_SCALE);
         }
         ph->S = S;
         ph->Q = Q;
@@ -1536,8 +1539,10 @@ static int or_update_weights(or_filter* f, const eslam_step_input* in, or_phase*
 }
 
 /* ---- normalizeWeights  src/ParticleFilter.hpp:46-70 ----------------------------------------- */
-static double normalize_with(or_filter* f, double S, double Q, int have_sums)
+/* Ss, Qs: the sums scaled by 2^-wexp and 2^-2 wexp (the fixed-point sums read at DM_FX_SCALE) */
+static double normalize_with(or_filter* f, double Ss, double Qs, int have_sums)
 {
+    double S = 0;
     const uint64_t n = f->n;
     const uint64_t N = NG(f);
     double effective = 0;
@@ -1549,17 +1554,18 @@ static double normalize_with(or_filter* f, double S, double Q, int have_sums)
             const uint32_t J = dm_chunk_rows_cfg(N, f->cfg.sum_chunk_rows);
             int e = f->wexp;
             double* w2 = malloc(n * 8 + 8);
-            for (uint64_t i = 0; i < n; ++i) w2[i] = f->w[OD(i)] * f->w[OD(i)];
+            for (uint64_t i = 0; i < n; ++i) w2[i] = dm_stat_sq(f->w[OD(i)], e);
             or_acc AB[2];
             memset(AB, 0, sizeof(AB));
             chunk_reduce(f->w, OR_DSTRIDE, NULL, 0, n, J, &AB[0], DM_FX_SCALE - e);
-            chunk_reduce(w2, 1, NULL, 0, n, J, &AB[1], DM_FX_SCALE - 2 * e);
+            chunk_reduce(w2, 1, NULL, 0, n, J, &AB[1], DM_FX_SCALE);
             free(w2);
             combine_accs(f, AB, 2);
-            S = acc_value(&AB[0], DM_FX_SCALE - e);
-            Q = acc_value(&AB[1], DM_FX_SCALE - 2 * e);
+            Ss = acc_value(&AB[0], DM_FX_SCALE);
+            Qs = acc_value(&AB[1], DM_FX_SCALE);
         }
     }
+    if (f->sum_mode == OR_SUM_CONTRACT) S = dm_ldexp(Ss, f->wexp);
     f->info.weight_sum = S;
     f->info.uniform_reset = 0;
     if (S <= 0.0) {
@@ -1575,7 +1581,7 @@ static double normalize_with(or_filter* f, double S, double Q, int have_sums)
             f->w[OD(i)] /= S;
             effective += f->w[OD(i)] * f->w[OD(i)];
         }
-        if (f->sum_mode == OR_SUM_CONTRACT) effective = Q / (S * S);
+        if (f->sum_mode == OR_SUM_CONTRACT) effective = Qs / (Ss * Ss);
     }
     f->wexp = 1;
     return 1.0 / effective;

@@ -1399,7 +1399,7 @@ extern "C" int eslam_gpu_upload_particles(eslam_ctx* ctx, uint64_t n, const esla
             if (v > mx) mx = v;
         }
     }
-    return reset_ctl_for_new_particles(ctx, dm_weight_exp(mx));
+    return reset_ctl_for_new_particles(ctx, dm_stat_exp(mx));
 }
 
 extern "C" int eslam_gpu_download_particles(eslam_ctx* ctx, eslam_particles* p)
@@ -1473,7 +1473,7 @@ static int write_particles_local(eslam_ctx* ctx, uint64_t first, uint64_t count,
         double mx = 0;
         const int rc = max_weight_local(ctx, &mx);
         if (rc) return rc;
-        ctx->ctl_host->wexp = dm_weight_exp(mx);
+        ctx->ctl_host->wexp = dm_stat_exp(mx);
         return write_ctl(ctx);
     }
     return ESLAM_OK;
@@ -1511,7 +1511,7 @@ extern "C" int eslam_gpu_write_particles(eslam_ctx* ctx, uint64_t first, uint64_
     }
     if (rc) return rc;
     if (peer_failed) return fail(ctx, ESLAM_ERR_COMM, "write_particles failed on another rank");
-    ctx->ctl_host->wexp = dm_weight_exp(mx);
+    ctx->ctl_host->wexp = dm_stat_exp(mx);
     return write_ctl(ctx);
 }
 

@@ -3078,7 +3078,7 @@ __global__ void __launch_bounds__(kBlock) k_weight_stats(DevState s0, DevState s
         if (i >= n) continue;
         const double w = st.w[i];
         a = a + w;
-        b = b + w * w;
+        b = b + dm_stat_sq(w, wexp);        // (w 2^-wexp)^2: in range at any weight scale
     }
     __shared__ uint32_t s_limb[kWaves][2][4];
     __shared__ uint32_t s_flag[kWaves];
@@ -3091,7 +3091,7 @@ __global__ void __launch_bounds__(kBlock) k_weight_stats(DevState s0, DevState s
             v = wave_sum_butterfly(v);
             if (v != v) flag |= 1u << (q * DM_NBUCKETS);
             else if (!dm_isfinite(v)) flag |= 1u << (q * DM_NBUCKETS + 16);
-            else dm_fx128_limbs(v, q == 0 ? DM_FX_SCALE - wexp : DM_FX_SCALE - 2 * wexp, l);
+            else dm_fx128_limbs(v, q == 0 ? DM_FX_SCALE - wexp : DM_FX_SCALE, l);
         }
         if (lane == 0) for (int j = 0; j < 4; ++j) s_limb[wave][q][j] = l[j];
     }
@@ -3182,13 +3182,12 @@ __device__ __forceinline__ void finalize_block(Shard* __restrict__ recs, int nre
     }
     __syncthreads();
     {
-        // the 13 fixed-point -> double conversions, one per lane (same values as serially)
+        // the 13 fixed-point -> double conversions, one per lane (same values as serially).  The
+        // weight sums A_b and the sums of squares B_b are read scaled by 2^-wexp and 2^-2 wexp
+        // (accumulated at DM_FX_SCALE - wexp and DM_FX_SCALE - 2 wexp, or the squares already
+        // scaled: k_weight_stats), so the effective count below is in range at any weight scale
         const uint64_t flags_ = s[2 * DM_NBUCKETS * 4 + 7];
-        if (t < 2 * DM_NBUCKETS + 1) {
-            const int scale = t < DM_NBUCKETS ? DM_FX_SCALE - wexp_
-                            : (t < 2 * DM_NBUCKETS ? DM_FX_SCALE - 2 * wexp_ : DM_FX_SCALE);
-            s_acc[t] = acc_value(s + 4 * t, flags_, t, scale);
-        }
+        if (t < 2 * DM_NBUCKETS + 1) s_acc[t] = acc_value(s + 4 * t, flags_, t, DM_FX_SCALE);
         __syncthreads();
         // phase-B factors (0.9 fw)^(4 - n), one bucket per lane
         if (fp.mode == FIN_UPDATE && t < DM_NBUCKETS) {
@@ -3249,6 +3248,8 @@ __device__ __forceinline__ void finalize_block(Shard* __restrict__ recs, int nre
         Q = s_acc[DM_NBUCKETS];
         for (int b = 0; b < DM_NBUCKETS; ++b) ctl->f[b] = 1.0;
     }
+    const double Ss = S;                                // S 2^-wexp; Q stays scaled (2^-2 wexp)
+    S = dm_ldexp(Ss, wexp_);
     ctl->S = S;
     ctl->Q = Q;
     ctl->inv_n = 1.0 / N;
@@ -3260,7 +3261,7 @@ __device__ __forceinline__ void finalize_block(Shard* __restrict__ recs, int nre
             ctl->uniform = 1;
             eff = 1.0 / (1.0 / N);
         } else {
-            eff = 1.0 / (Q / (S * S));
+            eff = 1.0 / (Q / (Ss * Ss));
         }
         ctl->eff = eff;
         ctl->wexp = 1;

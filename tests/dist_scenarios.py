@@ -11,7 +11,8 @@ import synthetic as S
 
 FIELDS = ("x", "y", "orientation", "zpos", "zsigma", "weight", "mprob", "floating", "n_contact_points")
 SCENARIOS = ("forced", "natural", "upload", "hash", "config3", "config4", "maps", "edit", "records", "heirloom", "chunks",
-             "maps_rect", "maps_rect_trail", "maps_sq_trail", "hash_edges")
+             "maps_rect", "maps_rect_trail", "maps_sq_trail", "hash_edges", "weight_scales")
+WEIGHT_SCALES_K = -400                           # weight_scales: the uploaded weights' scale 2^k
 # `maps` on grids that are square in neither sense (rect_grids.py): maps_rect on the 150 x 110
 # grid of 0.10 x 0.08 m cells (a 9 x 11-tile window) with a scan reaching back over the mapped
 # cells, so migrating maps carry the shadow flag; maps_rect_trail on the empty prior of the same
@@ -164,6 +165,17 @@ def upload_arrays(n_global, lo, hi):
     return out
 
 
+def weight_scales_arrays(n_global, lo, hi):
+    """weight_scales: the shard [lo, hi) of weight_scale_cases' base particles, weights times
+    2^WEIGHT_SCALES_K -- far below the 2^-111 at which a clamped statistics exponent truncated"""
+    import weight_scale_cases as W
+    pa = W.particles(n_global, W.scaled(n_global, ("p", WEIGHT_SCALES_K)))
+    out = A.ParticleArrays(hi - lo)
+    for f in FIELDS:
+        getattr(out, f)[:] = getattr(pa, f)[lo:hi]
+    return out
+
+
 def hash_edges_zeros(n_global):
     """hash_edges: the global indices of the -0.0 (on the first rank) and of the +0.0 (on the
     last one) of the zero pair, whose other weights are negative: the best particle is the -0.0"""
@@ -303,6 +315,20 @@ def run_scenario(f, name, n_global, lo, hi, steps=6, info_fn=None):
         for k in range(2):                       # the copies on write of the shared received table
             f.map_update(S.scan_patches(x0=0.35 + 0.3 * k))
         rec["maps2/count"] = np.array([len(f.particle_map(g - lo)[0]) for g in range(lo, hi) if g % 97 == 0], np.uint32)
+        return rec
+    if name == "weight_scales":
+        # upload, sum, normalise, centroid and a resample after normalise at a weight scale of
+        # 2^-400: the statistics exponent agreed over the ranks (the largest weight of all shards)
+        f.upload(weight_scales_arrays(n_global, lo, hi))
+        rec["sum0"] = np.array([f.weights_sum()])
+        rec["best0"] = np.array([f.best_index()])
+        rec["eff0"] = np.array([f.normalize()])
+        _snap(rec, "norm", f, False)
+        pos, quat = f.centroid()
+        rec["centroid"] = np.array(list(pos) + list(quat))
+        _snap(rec, "centroid", f, False)
+        f.resample()
+        _snap(rec, "res", f, True)
         return rec
     if name == "upload":
         f.upload(upload_arrays(n_global, lo, hi))

@@ -119,7 +119,7 @@ def family(name, n, k=0):
     raise KeyError(name)
 
 
-TINY = ("denormal",)                     # families whose sum the contract truncates (weight_bound)
+TINY = ()                                # families whose sum the contract truncates (weight_bound): none, see check_respawn
 FAMILIES = ("zeros", "signed_zeros", "one_float", "round_tie", "denormal", "overflow", "negative", "boundary_tie",
             "dyadic", "nan")
 
@@ -210,15 +210,18 @@ def check_respawn(before, after, r, ref, avg, tiny=False, label=""):
 
     The weight the replaced particles get is ((S / N) avgFactor) rel.  Where every uploaded
     weight is a multiple of 2^-40 (of 2^100 in the overflow family) the contract's fixed-point sum
-    S is exact and the weight equals hash_ref's (math.fsum) bit for bit.  In the tiny-weight
-    family (tiny=True: float denormals, multiples of 2^-151 with a sum below 2^-120) the contract
-    truncates: the double sum of each chunk of 64 particles is exact (30 significant bits), and
+    S is exact and the weight equals hash_ref's (math.fsum) bit for bit.  So it does in the
+    denormal family (float denormals, multiples of 2^-151 with a sum below 2^-120): the fixed
+    point follows the largest weight (dm_stat_exp: e = -127, scale 239), so no chunk total is
+    truncated.  While the statistics' exponent was clamped at 1 the contract truncated there and
+    the family was compared within a bound (tiny=True, kept for a family that would need it):
+    the double sum of each chunk of 64 particles is exact (30 significant bits), and
     each chunk total is converted to fixed point as trunc(total 2^(DM_FX_SCALE - wexp)), losing
     less than 2^-(DM_FX_SCALE - wexp); there are at most N chunks, so
     0 <= fsum - S < N 2^-(DM_FX_SCALE - wexp).  Dividing by N, times avgFactor, times rel (three
     roundings of 2^-53 relative each, far below the bound's slack of 2^-40) gives
-    |weight - ref| <= 2^-(DM_FX_SCALE - wexp) avgFactor rel (1 + 2^-40), with wexp = 1 (the
-    largest weight is below 2)."""
+    |weight - ref| <= 2^-(DM_FX_SCALE - wexp) avgFactor rel (1 + 2^-40), wexp the exponent of the
+    largest weight."""
     n = before.n
     replaced = np.zeros(n, bool)
     replaced[r.order] = True

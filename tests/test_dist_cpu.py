@@ -97,6 +97,17 @@ def check_hash_edges(want, n_global, world):
         assert replaced > min(np.diff(g)), (replaced, g)
 
 
+def check_weight_scales(want, n_global):
+    """weight_scales is what it is there for: the one-context results lie within the bounds of
+    weights_ref (weight_scale_cases.py) at the scale 2^-400, no uniform reset among them"""
+    import weight_scale_cases as W
+    from dist_scenarios import WEIGHT_SCALES_K
+    J = W.rows_of(0, n_global)
+    w_in = W.scaled(n_global, ("p", WEIGHT_SCALES_K))
+    W.check_normalized(w_in, float(want["sum0"][0]), float(want["eff0"][0]), want["norm/weight"], J, "weight_scales")
+    assert int(want["best0"][0]) == int(np.argmax(w_in)) and len(set(want["res/anc"].tolist())) > 1
+
+
 def single_oracle(name, n_global):
     cfg = scenario_config(name, n_global)
     f = O.OracleFilter(cfg, O.SUM_CONTRACT)
@@ -112,13 +123,16 @@ def single_oracle(name, n_global):
                                                  ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
                                                  ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
-                                                 ("hash_edges", 1500, 3)])
+                                                 ("hash_edges", 1500, 3), ("weight_scales", 1000, 2),
+                                                 ("weight_scales", 1000, 3)])
 def test_sharded_oracle_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("oracle", name, n_global, world, str(tmp_path)))
     assert_same(got, want, f"{name} N={n_global} world={world}")
     if name == "hash_edges":
         check_hash_edges(want, n_global, world)
+    if name == "weight_scales":
+        check_weight_scales(want, n_global)
     if name in TRAIL_SCENARIOS:
         assert trail_tiles(name, want) > 0
     if name.startswith("maps"):

@@ -7,7 +7,7 @@ library's own RCCL communicator (eslam_gpu_set_comm_rccl)."""
 import numpy as np
 import pytest
 
-from test_dist_cpu import assert_same, check_hash_edges, launch, merge, single_oracle
+from test_dist_cpu import assert_same, check_hash_edges, check_weight_scales, launch, merge, single_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -21,13 +21,16 @@ pytestmark = pytest.mark.gpu
                                                  ("maps_rect", 3000, 2), ("maps_rect", 1500, 3),
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
                                                  ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
-                                                 ("hash_edges", 1500, 3)])
+                                                 ("hash_edges", 1500, 3), ("weight_scales", 1000, 2),
+                                                 ("weight_scales", 1000, 3)])
 def test_sharded_gpu_gloo_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("gpu", name, n_global, world, str(tmp_path), mem="host", timeout=400))
     assert_same(got, want, f"gpu {name} N={n_global} world={world}")
     if name == "hash_edges":
         check_hash_edges(want, n_global, world)
+    if name == "weight_scales":
+        check_weight_scales(want, n_global)
 
 
 @pytest.mark.parametrize("world", [2, 3])
