@@ -150,7 +150,18 @@ typedef struct eslam_step_input {
     double body2odometry_trans[3];
     /* outputs of the external odometry::FootContact after odometry.update(bs, orientation):
      * getPoseDelta().position, getPositionError()(2,2) and the Gaussian that
-     * getPoseDeltaSample2D() samples (mean dx, dy, dtheta; 3x3 covariance, row-major).     */
+     * getPoseDeltaSample2D() samples (mean dx, dy, dtheta; 3x3 covariance, row-major).
+     *
+     * The sampler draws mean + L z with L the lower Cholesky factor of sample_cov.  Only the
+     * LOWER triangle is read, sample_cov[i * 3 + j] with i >= j; the entries above the
+     * diagonal are never used for the factor (they need not mirror the lower ones).  A pivot
+     * that is not positive (a zero variance, a rank-deficient or slightly indefinite matrix)
+     * gives a zero column of L, never a NaN: the all-zero matrix samples the mean exactly.
+     *
+     * Accepted domain: every entry of sample_mean and of sample_cov (all nine) finite, and
+     * no diagonal entry of sample_cov negative.  eslam_gpu_project, eslam_gpu_update and
+     * eslam_gpu_step return ESLAM_ERR_INVALID_ARG for anything else, before any kernel runs
+     * and with the particles, the counters and the random streams unchanged.                */
     double pose_delta_trans[3];
     double position_error_zz;
     double sample_mean[3];

@@ -1253,9 +1253,19 @@ static void sample_from_hash(or_filter* f, const eslam_step_input* in)
     free(wi);
 }
 
+/* the accepted domain of the sampler's Gaussian (include/eslam_gpu.h, eslam_step_input): every
+ * entry of sample_mean and sample_cov finite, no negative variance */
+static int step_input_ok(const eslam_step_input* in)
+{
+    for (int i = 0; i < 3; ++i) if (!dm_isfinite(in->sample_mean[i])) return 0;
+    for (int i = 0; i < 9; ++i) if (!dm_isfinite(in->sample_cov[i])) return 0;
+    return !(in->sample_cov[0] < 0.0 || in->sample_cov[4] < 0.0 || in->sample_cov[8] < 0.0);
+}
+
 /* ---- project  src/PoseEstimator.cpp:184-242 --------------------------------------------- */
 int or_project(or_filter* f, const eslam_step_input* in)
 {
+    if (!step_input_ok(in)) return ESLAM_ERR_INVALID_ARG;
     if (!f->n) return ESLAM_ERR_NOT_INITIALISED;
     or_prep pp;
     or_prepare(in, &pp);
@@ -1944,6 +1954,7 @@ void or_resample_multinomial(or_filter* f, uint64_t samples)
 /* ---- PoseEstimator::update  src/PoseEstimator.cpp:244-255 ---------------------------------- */
 int or_update(or_filter* f, const eslam_step_input* in)
 {
+    if (!step_input_ok(in)) return ESLAM_ERR_INVALID_ARG;
     if (!f->n) return ESLAM_ERR_NOT_INITIALISED;
     or_phase ph;
     memset(&ph, 0, sizeof(ph));

@@ -3009,8 +3009,21 @@ static int take_update_error(eslam_ctx* ctx)
     return fail(ctx, ESLAM_ERR_ZERO_MEAS_VAR, "using a zero measurement variance leads to singularities");
 }
 
+// the accepted domain of the sampler's Gaussian (eslam_step_input): checked on the host, in front
+// of every launch, so no kernel sees a NaN pose delta or a NaN window margin
+static bool step_input_ok(const eslam_step_input* in)
+{
+    for (int i = 0; i < 3; ++i)
+        if (!dm_isfinite(in->sample_mean[i])) return false;
+    for (int i = 0; i < 9; ++i)
+        if (!dm_isfinite(in->sample_cov[i])) return false;
+    return !(in->sample_cov[0] < 0.0 || in->sample_cov[4] < 0.0 || in->sample_cov[8] < 0.0);
+}
+
 static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project, bool weight)
 {
+    if (!step_input_ok(in))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "step input: sample_mean and sample_cov must be finite, the variances not negative");
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
     if (check_poisoned(ctx)) return ESLAM_ERR_HIP;
     if (weight && !ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");

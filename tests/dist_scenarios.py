@@ -11,7 +11,7 @@ import synthetic as S
 
 FIELDS = ("x", "y", "orientation", "zpos", "zsigma", "weight", "mprob", "floating", "n_contact_points")
 SCENARIOS = ("forced", "natural", "upload", "hash", "config3", "config4", "maps", "edit", "records", "heirloom", "chunks",
-             "maps_rect", "maps_rect_trail", "maps_sq_trail", "hash_edges", "weight_scales")
+             "maps_rect", "maps_rect_trail", "maps_sq_trail", "hash_edges", "weight_scales", "full_cov")
 WEIGHT_SCALES_K = -400                           # weight_scales: the uploaded weights' scale 2^k
 # `maps` on grids that are square in neither sense (rect_grids.py): maps_rect on the 150 x 110
 # grid of 0.10 x 0.08 m cells (a 9 x 11-tile window) with a scan reaching back over the mapped
@@ -43,7 +43,7 @@ def scenario_config(name, n_global):
     cfg = A.default_config()
     cfg.seed = 1234
     cfg.flags |= A.FLAG_RECORD_ANCESTORS
-    if name in ("forced", "config3", "config4", "burst", "edit", "getter0", "records", "heirloom", "chunks") + MAPS_SCENARIOS:
+    if name in ("forced", "config3", "config4", "burst", "edit", "getter0", "records", "heirloom", "chunks", "full_cov") + MAPS_SCENARIOS:
         S.bench_config(cfg, n_global)
         if name in MAPS_SCENARIOS and name != "maps":
             cfg.flags |= A.FLAG_PARTICLE_MAPS
@@ -390,7 +390,13 @@ def run_scenario(f, name, n_global, lo, hi, steps=6, info_fn=None):
     elif name in TRAIL_SCENARIOS:                # straight ahead: both window axes of the rotated grid move
         stream = S.step_stream(TRAIL_STEPS, dx=TRAIL_DX, dyaw=0.0, tilt=True)
     else:
-        stream = S.step_stream(steps, tilt=(name in ("natural",) + MAPS_SCENARIOS))
+        stream = S.step_stream(steps, tilt=(name in ("natural", "full_cov") + MAPS_SCENARIOS))
+    if name == "full_cov":
+        # the odometry covariance with every off-diagonal term and a pose delta with every
+        # component (project_cases.py): the sampler's draws are keyed by the global index
+        import project_cases as PC
+        for k, st in enumerate(stream):
+            PC.full_covariance(st, k)
     scan = probe = None
     if name == "maps":
         scan, probe = S.scan_patches(), S.scan_patches(z=-0.15)

@@ -124,7 +124,7 @@ def single_oracle(name, n_global):
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
                                                  ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
                                                  ("hash_edges", 1500, 3), ("weight_scales", 1000, 2),
-                                                 ("weight_scales", 1000, 3)])
+                                                 ("weight_scales", 1000, 3), ("full_cov", 3000, 2)])
 def test_sharded_oracle_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("oracle", name, n_global, world, str(tmp_path)))

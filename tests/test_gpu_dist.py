@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
                                                  ("maps_rect_trail", 3000, 2), ("maps_rect_trail", 1500, 3),
                                                  ("maps_sq_trail", 3000, 2), ("hash_edges", 3000, 2),
                                                  ("hash_edges", 1500, 3), ("weight_scales", 1000, 2),
-                                                 ("weight_scales", 1000, 3)])
+                                                 ("weight_scales", 1000, 3), ("full_cov", 3000, 2)])
 def test_sharded_gpu_gloo_equals_single(oracle, tmp_path, name, n_global, world):
     want = single_oracle(name, n_global)
     got = merge(launch("gpu", name, n_global, world, str(tmp_path), mem="host", timeout=400))
