@@ -9,8 +9,9 @@ Machine-LICM is disabled for the kernels' translation unit only: it hoists the ~
 polynomial constants of the contact model out of the particle loop and drives
 k_project_weight to 256 VGPRs / occupancy 1.
 
-Provenance: the SHA-256 of every source, of every header they include (HEADERS: the three in
-csrc/ -- device-visible layouts, launcher declarations, buffer owners -- and the two public ones)
+Provenance: the SHA-256 of every source, of every header they include (HEADERS: the five in
+csrc/ -- device-visible layouts, launcher declarations, buffer owners, scratch layouts, the host
+side's context -- and the two public ones)
 and of every flag is compiled into the library (eslam_gpu_build_id()).  A build is skipped only when the existing library reports the hash
 of the current sources, so a run never loads a binary that was not built from them
 (tests/test_abi.py checks the shipped library the same way).
@@ -30,8 +31,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ESLAM_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["eslam_kernels.hip", "eslam_resample.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_snapshot.hip",
-           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_ctx.hip"]
+           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_ctx.hip", "eslam_host_comm.hip"]
 HEADERS = [os.path.join(CSRC, "eslam_internal.h"), os.path.join(CSRC, "eslam_launch.h"), os.path.join(CSRC, "eslam_buf.h"),
+           os.path.join(CSRC, "eslam_scratch.h"), os.path.join(CSRC, "eslam_ctx.h"),
            os.path.join(ROOT, "include", "eslam_gpu.h"), os.path.join(ROOT, "include", "eslam_detmath.h")]
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-mfma", "-Wall", "-Wno-unused-result", "-Wno-unused-function", f"-I{os.path.join(ROOT, 'include')}"]

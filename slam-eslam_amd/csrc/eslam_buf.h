@@ -1,7 +1,8 @@
 // eslam_buf.h -- host-only owners of the HIP resources the context keeps: device and pinned
 // buffers, events and the timing rings.  Each frees what it holds when it is reset, assigned
 // over or destroyed, so a lifetime is written once, at the member's declaration.  The structs
-// kernels take by value (eslam_internal.h) keep raw pointers and are filled from these.
+// kernels take by value (eslam_internal.h) keep raw pointers and are filled from these.  Also
+// the Carver, which lays the arrays of one block out in order.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -112,6 +113,28 @@ private:
 
 template <typename T> using Dev = Buf<T, Mem::Device>;
 template <typename T> using Pinned = Buf<T, Mem::Pinned>;
+
+// Arrays carved one after another from a block that starts at `base`, each rounded up to `align`
+// bytes (hipMalloc's blocks are 256-byte aligned, so every array is).  With a null base it only
+// measures: take() returns nullptr and bytes() is the block's size.  A layout is one function
+// of a Carver, run once to size the block and once to place the arrays.
+class Carver {
+public:
+    explicit Carver(void* base, uint64_t align = 256) : base_(static_cast<char*>(base)), align_(align) {}
+
+    void* take_bytes(uint64_t bytes)
+    {
+        void* p = base_ ? base_ + off_ : nullptr;
+        off_ += (bytes + align_ - 1) / align_ * align_;
+        return p;
+    }
+    template <class T> T* take(uint64_t count) { return static_cast<T*>(take_bytes(count * sizeof(T))); }
+    uint64_t bytes() const { return off_; }     // taken so far
+
+private:
+    char* base_;
+    uint64_t align_, off_ = 0;
+};
 
 // A move-only event, created on first use.
 class Event {

@@ -1,4 +1,5 @@
-// eslam_ctx.hip -- host side of libeslam_gpu: the C ABI of include/eslam_gpu.h.
+// eslam_ctx.hip -- host side of libeslam_gpu: the C ABI of include/eslam_gpu.h (the context itself
+// and what crosses the host files: eslam_ctx.h; the multi-GPU plumbing: eslam_host_comm.hip).
 //
 // Per-step host work is O(1): the reference's per-step scalar preparation
 // (src/PoseEstimator.cpp:186-194: yaw, removeYaw, the odometry z delta and variance,
@@ -7,8 +8,6 @@
 // touches particles runs on the GPU; the resample decision is taken on the device, so a
 // step is four asynchronous launches with no host round trip.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <dlfcn.h>
 
 #include <math.h>
 #include <stdlib.h>
@@ -22,12 +21,8 @@
 #include <functional>
 #include <vector>
 
-#include "eslam_internal.h"
-#include "eslam_launch.h"
-#include "eslam_buf.h"
-
-using namespace eslam_dev;
-using namespace eslam_buf;
+#include "eslam_ctx.h"
+#include "eslam_scratch.h"
 
 // ---------------------------------------------------------------------------------------
 // small Eigen / base-types restatements (host, per step)
@@ -161,17 +156,6 @@ void set_translation_pose(double ud[12], double x, double y, double z)
 
 }  // namespace
 
-// ---------------------------------------------------------------------------------------
-// context
-// ---------------------------------------------------------------------------------------
-// ESLAM_FLAG_PROCESS_STATICS: the reference's function-static hash-respawn counter
-// (src/PoseEstimator.cpp:239) and the C library's rand() (SurfaceHash::sample), shared by every
-// context of the process that sets the flag -- Q11.  Not locked, like the reference's statics.
-struct ProcessStatics {
-    uint64_t hash_event = 0;
-    dm_libc_rand_state libc;
-    ProcessStatics() { dm_libc_srand(&libc, 1); }
-};
 static ProcessStatics& process_statics()
 {
     static ProcessStatics ps;
@@ -180,221 +164,7 @@ static ProcessStatics& process_statics()
 // sharded contexts of this process with the flag: at most one.  Ranks driven from one process
 // would advance the shared counter once each per step and draw each other's rand() values, so
 // their respawns and hash indices would disagree (eslam_gpu_set_comm refuses a second one)
-static std::atomic<int> g_statics_sharded{0};
-
-// The owners of the context's device and pinned memory, grouped by what drops them together:
-// assigning an empty group over one frees its buffers (free_particles, free_local_maps,
-// free_debug, free_map).  The structs kernels take by value are filled from these.
-struct ParticleBufs {                        // alloc_particles
-    Dev<void> state_mem;
-    Dev<uint32_t> marks, anc;
-    Dev<uint32_t> tile_first;                // row_first: source of every 64-output row's first output
-    Dev<uint64_t> tile_sum;                  // per scan tile: exact fixed-point weight total (sharded K3a), or
-                                             // one GPU: tag << 61 | total published by K3 (zeroed at allocation)
-    Dev<uint2> range;                        // per particle: [lo, hi) of its global outputs
-    Dev<uint32_t> sid_mem;                   // 2 x cap: DevState::sid of both state buffers
-    Dev<uint32_t> cow;                       // owner, counts, free and sharing lists + the copy count
-    Dev<uint64_t> merge_cnt;                 // the map merge's statistics slots (2 x kMergeCounterSlots) and
-                                             // the copy-on-write copies since the last merge
-};
-struct LocalMapBufs {                        // local_maps_reset
-    Dev<int2> ctr;                           // the arrays of LocalMaps
-    Dev<float2> page;
-    Dev<uint64_t> owner;
-    Dev<uint32_t> slot, tgen, frees;
-    Dev<uint8_t> mark;
-    Dev<uint32_t> off;                       // per particle: its first page in its plan block (MergeParams::off)
-    Dev<MergeJob> job;                       // per particle: the plan's record (MergeParams::job)
-    Dev<uint16_t> codes;                     // per particle: the plan's cell codes (MergeParams::codes): a small
-                                             //   part's stride, grown for a large part's
-    Dev<uint32_t> poff;                      // per merge block: page offsets (+ total)
-    Dev<uint32_t> pgc;                       // the page collection's compaction counts
-    Dev<ScanPatch> match_sp;                 // processMap match: the sampled scan patches
-    Dev<void> census;                        // a snapshot's census: first, trank, tlist, firstref, prank, plist
-    Dev<uint32_t> counts;                    // the census' tile counts
-};
-struct DebugBufs {                           // the arrays of DebugRec
-    Dev<double> meas, cp;
-    Dev<uint8_t> ncp;
-    Dev<uint32_t> resampled;
-};
-struct GridBufs {                            // the shared grid's arrays (MapView, SmGrid)
-    Dev<uint32_t> cells, occ;
-    Dev<float2> patch;
-    Dev<float> height;                       // empty: all horizontal
-    Dev<uint4> cell_tab;
-    SmGrid view() const { return SmGrid{cells, patch, height, occ, cell_tab}; }
-};
-
-struct eslam_ctx {
-    eslam_config cfg;
-    int device = 0;
-    hipStream_t stream = nullptr;            // destroyed (if owned) after every member below is gone
-    bool own_stream = false;
-    // particles
-    uint64_t n = 0, cap = 0;
-    uint64_t gbase = 0, n_global = 0;
-    DevState st[2] = {};
-    ParticleBufs pt;
-    uint64_t* fin_word = nullptr;           // the fused finalize's epoch word (after the tile words)
-    uint32_t pub_stride = 0;                // ScanParams::pub_stride
-    uint64_t fin_epoch = 0;                 // fused finalize launches so far
-    uint32_t scan_tag = 0;                  // the last K3 launch's tag (1..7)
-    bool has_anc = false;
-    // per-particle maps (ESLAM_FLAG_PARTICLE_MAPS): the tables, pages and the copy-on-write scratch
-    LocalMaps lm = {};
-    LocalMapBufs lmb;
-    bool lm_ready = false;                   // lm sized for the current map and particle count
-    // the scan of a map update on the device (MergeParams::sp): two slots, each staged through
-    // pinned host memory; an update waits for the update before last to have read its slot
-    Pinned<ScanPatch> scan_host[2];
-    Dev<ScanPatch> scan_dev[2];
-    Event scan_ev[2];
-    uint32_t scan_slot = 0;
-    // logDebug records of the last update (ESLAM_FLAG_RECORD_CONTACTS / log_debug)
-    DebugRec dbg = {};
-    DebugBufs dbgb;
-    uint64_t dbg_cap = 0;
-    bool dbg_valid = false;
-    // statistics and control
-    Dev<Shard> shards;
-    Dev<Ctl> ctl;
-    Pinned<Ctl> ctl_host;
-    Pinned<uint32_t> fault_host;            // host-mapped: kFaultTimeout when a device wait gave up
-    bool poisoned = false;                  // the particle set is undefined until re-initialised
-    bool poison_pages = false;              // ... because the map pages ran out (kFaultPages)
-    uint32_t spin_limit = kSpinLimit;       // polls of K3's cross-block waits (debug: 0 gives up at once)
-    uint32_t debug_scan_items = 0;          // particles per thread of the one-GPU K3 (debug; 0: scan_items(n))
-    Dev<uint32_t> jump;
-    uint32_t jump_n = 1;                    // A^n_global, cached
-    uint64_t jump_n_for = 0;
-    Dev<double> scratch;                    // small device scratch (centroid, best index)
-    Pinned<double> scratch_host;
-    // map
-    bool has_map = false;
-    MapView map = {};
-    GridBufs grid;
-    uint64_t map_np = 0;                     // patches of the grid (cell_start[width * height])
-    uint64_t map_np_cap = 0;                 // patches grid.patch / grid.height have room for
-    // eslam_gpu_shared_map_update's scratch (SmScratch): one allocation, kept between calls
-    Dev<void> sm_mem;
-    // eslam_gpu_shared_map_update_sharded's exchange memory, kept between calls: kSmXHead bytes for
-    // the small all_gathers, then a run's staged pose records (one copy per rank) and the gathered
-    // run, at most (nranks + 1) x run particles x 40 bytes
-    Dev<void> sm_x;
-    // eslam_gpu_get_particle_grid / eslam_gpu_adopt_particle_map's scratch (PgScratch), kept between calls
-    Dev<void> pg_mem;
-    // ... and the arrays the last export composed into, kept for the next one (room for pg_out_cap
-    // patches on a grid of pg_out_cells cells; dropped with the map, handed over by an adoption)
-    GridBufs pg_out;
-    uint64_t pg_out_cap = 0, pg_out_cells = 0;
-    // eslam_gpu_scan_from_laser / _depth: the build's scratch (ScanWork) and the last
-    // built scan's patches (capacity in patches), both kept between calls
-    Dev<void> scan_mem;
-    Dev<eslam_scan_patch> scan_out;
-    uint64_t scan_count = 0;                 // patches of the last built scan
-    // eslam_gpu_save / eslam_gpu_load: two pinned and two device staging slots of
-    // snap_cap bytes with their events (the census scratch is dropped with the local maps)
-    Pinned<void> snap_host[2];
-    Dev<void> snap_dev[2];
-    uint64_t snap_cap = 0;
-    Event snap_ev[2];
-    uint32_t maxp = 4;
-    // host-side filter state
-    uint64_t proj_event = 0, init_event = 0, hash_event = 0;
-    double ud_pose[12];
-    double zcomp[4] = {1, 0, 0, 0};
-    // multi-GPU (eslam_gpu_set_comm): this context is shard [gbase, gbase + n) of n_global
-    bool sharded = false;
-    bool statics_sharded = false;            // counted in g_statics_sharded
-    eslam_comm comm = {};
-    std::vector<uint64_t> gall;             // first global index of every rank (+ n_global)
-    Dev<Shard> recs;                        // gathered records of all ranks
-    Dev<uint64_t> mg;                       // MgBlock (device)
-    void* rccl = nullptr;                   // ncclComm_t of eslam_gpu_set_comm_rccl (owned)
-    Pinned<uint64_t> mg_host;               // host-mapped (k_segments_multi writes the totals there)
-    uint64_t seg_epoch = 0;                 // the last k_segments_multi launch's epoch (mg_host[kHostEpoch])
-    Dev<void> sendbuf, recvbuf;
-    // per-particle maps on a sharded filter: the migrated particles' maps (a MapPayHdr per
-    // record, then their pages as MapPayPage, in the records' order) and whether their tables
-    // are still owed to them
-    Dev<void> sendpay, recvpay, sendhdr, recvhdr;
-    Dev<uint32_t> payoff;                    // header prefix (send side, then receive side)
-    Dev<uint32_t> rhead;                     // received records: the record carrying each one's map
-    uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
-    Dev<double> cent;                        // getCentroid's chunk records (sharded: sized by set_comm)
-    Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)
-    bool cow_pending = false;
-    // a sharded update's exchange left for the next call: the segments kernel's
-    // epoch and plan; the next step runs its own-output chunks before it completes it
-    bool xpend = false;
-    uint64_t xpend_epoch = 0;
-    PlanParams xpend_pp = {};
-    hipStream_t xstream = nullptr;           // the deferred exchange's stream (overlaps the own chunks)
-    Event ev_seg;                            // recorded after the segments kernel
-    Event ev_x;                              // recorded after the exchange's expand
-    Pinned<void> stage;                      // pinned staging (host-memory comm)
-    // SurfaceHash (useHash)
-    double map_scale[2] = {1, 1};
-    bool has_hash = false;
-    uint64_t hash_n = 0;
-    Dev<double> d_hash;                      // 4 x hash_n: x, y, theta, z
-    Dev<uint32_t> d_hash_blist;              // pose indices grouped by bucket, sweep order
-    std::vector<uint32_t> hash_bstart;       // bins^2 + 1
-    std::vector<int32_t> hash_bucket;        // per pose (sweep order)
-    dm_libc_rand_state libc;                 // rand() of SurfaceHash::sample (glibc, seed 1)
-    // the hash-respawn counter and rand() in use: this context's own, or the process's
-    // (ESLAM_FLAG_PROCESS_STATICS: the reference's function statics, Q11)
-    uint64_t* hash_ev = nullptr;
-    dm_libc_rand_state* libcp = nullptr;
-    Dev<void> hsend, hrecv, hsort;           // sharded respawn: candidate pairs out / in; their sort's arrays + scratch
-    Dev<uint32_t> d_sort;                    // keys, vals, keys_out, order (4 x sort_cap)
-    uint64_t sort_cap = 0;
-    Dev<void> sort_tmp;
-    size_t sort_tmp_bytes = 0;
-    Dev<uint32_t> d_draws;
-    // eslam_gpu_resample_stratified / _multinomial to another count: the cumulative sum, its
-    // coarse level, the draws' ancestors and the compaction's counts (resample_to), kept between calls
-    Dev<char> rs_mem;
-    // diagnostics
-    std::string err;
-    bool timing = false;
-    Event ev[5];                            // events of the step being recorded
-    EventRing ring{5, 4};                   // 5 events per recorded step (timing mode)
-    EventRing mring{5, 4};                  // 5 events per recorded map update (timing mode)
-    EventRing xring{2, 1};                  // 2 events per recorded map match (timing mode)
-    eslam_kernel_times times = {};
-};
-
-#define HIPCHK(ctx, expr)                                                                    \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return ESLAM_ERR_HIP;                                                            \
-        }                                                                                    \
-    } while (0)
-
-static int settle(eslam_ctx* ctx);       // completes a deferred sharded exchange (run_update_tail_multi)
-
-// multi-GPU scratch block (uint64 words, device + pinned host mirror)
-namespace mg {
-constexpr int kTotal = 0;                                   // this rank's fixed-point weight total
-constexpr int kTotals = kTotal + 1;                         // [kMaxRanks] gathered totals
-constexpr int kMirror = kTotals + kMaxRanks;                // [3] resample, minstd_start, scan_shift (k_finalize)
-constexpr int kCounts = kMirror + 3;                        // [kMaxRanks] records sent to each rank
-constexpr int kCountsAll = kCounts + kMaxRanks;             // [kMaxRanks^2] gathered counts
-constexpr int kSendOff = kCountsAll + kMaxRanks * kMaxRanks;   // [kMaxRanks + 1]
-constexpr int kSdEd = kSendOff + kMaxRanks + 1;             // [2 kMaxRanks]
-constexpr int kFirstLast = kSdEd + 2 * kMaxRanks;           // [2 kMaxRanks]
-constexpr int kBest = kFirstLast + 2 * kMaxRanks;           // [2] local best (key, global index)
-constexpr int kBestAll = kBest + 2;                         // [2 kMaxRanks]
-constexpr int kMaxW = kBestAll + 2 * kMaxRanks;             // local max weight (bits)
-constexpr int kMaxWAll = kMaxW + 1;                         // [kMaxRanks]
-constexpr int kHostEpoch = kMaxWAll + kMaxRanks;           // (mg_host only) the segments kernel's epoch
-constexpr int kChunks = kHostEpoch + 1;                     // [2] own-output chunks of the slice (PlanParams::chunk_sel)
-constexpr int kWords = kChunks + 2;
-}  // namespace mg
+std::atomic<int> eslam_host::g_statics_sharded{0};
 
 // timing mode (EventRing): event k (0..4) of the current step; event k (0..4) of the current map
 // update (start, gather, copy on write, plan, merge); event k (0: start, 1: end) of the current
@@ -402,12 +172,6 @@ constexpr int kWords = kChunks + 2;
 static void rec(eslam_ctx* ctx, int k) { ctx->ring.record(ctx->timing, k, ctx->stream); }
 static void mrec(eslam_ctx* ctx, int k) { ctx->mring.record(ctx->timing, k, ctx->stream); }
 static void xrec(eslam_ctx* ctx, int k) { ctx->xring.record(ctx->timing, k, ctx->stream); }
-
-static int fail(eslam_ctx* ctx, int code, const char* msg)
-{
-    if (ctx) ctx->err = msg;
-    return code;
-}
 
 extern "C" int eslam_gpu_abi_version(void) { return ESLAM_ABI_VERSION; }
 
@@ -607,7 +371,7 @@ static void free_local_maps(eslam_ctx* ctx)
     ctx->lm_ready = false;
 }
 
-static void free_particles(eslam_ctx* ctx)
+void eslam_host::free_particles(eslam_ctx* ctx)
 {
     free_debug(ctx);
     free_local_maps(ctx);
@@ -626,8 +390,6 @@ static void free_map(eslam_ctx* ctx)
     ctx->map_np = ctx->map_np_cap = 0;
     ctx->has_map = false;
 }
-
-namespace { void rccl_release(eslam_ctx* ctx); }
 
 extern "C" void eslam_gpu_destroy(eslam_ctx* ctx)
 {
@@ -685,16 +447,19 @@ struct ParticleSet {
 static hipError_t alloc_particle_set(const eslam_ctx* ctx, uint64_t cap, ParticleSet& ps)
 {
 #define ESLAM_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
-    const uint64_t per = 7 * al(cap * 8) + al(cap);
-    ESLAM_TRY(ps.pt.state_mem.alloc(2 * per));
-    for (int k = 0; k < 2; ++k) {
-        char* p = ps.pt.state_mem.as<char>() + k * per;
-        DevState& s = ps.st[k];
-        double** f[7] = {&s.x, &s.y, &s.th, &s.z, &s.zs, &s.w, &s.mprob};
-        for (int j = 0; j < 7; ++j) { *f[j] = (double*)p; p += al(cap * 8); }
-        s.flags = (uint8_t*)p;
-    }
+    auto carve = [&](Carver& c) {
+        for (int k = 0; k < 2; ++k) {
+            DevState& s = ps.st[k];
+            double** f[7] = {&s.x, &s.y, &s.th, &s.z, &s.zs, &s.w, &s.mprob};
+            for (int j = 0; j < 7; ++j) *f[j] = c.take<double>(cap);
+            s.flags = c.take<uint8_t>(cap);
+        }
+    };
+    Carver size(nullptr);
+    carve(size);
+    ESLAM_TRY(ps.pt.state_mem.alloc(size.bytes()));
+    Carver place(ps.pt.state_mem.get());
+    carve(place);
     const uint64_t ntiles = (cap + kBlock - 1) / kBlock;                // the smallest scan tile (scan_items)
     ESLAM_TRY(ps.pt.marks.alloc(cap * 4));
     ESLAM_TRY(ps.pt.tile_first.alloc(((cap + kRow - 1) / kRow) * 4));
@@ -817,61 +582,6 @@ static int local_maps_reset(eslam_ctx* ctx)
     return ESLAM_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// multi-GPU plumbing: the three exchanges of an update go through the user's collectives
-// ---------------------------------------------------------------------------------------
-// a buffer of at least `bytes`, contents not kept (Buf::grow: the old block is freed first)
-template <typename B>
-static int grow(eslam_ctx* ctx, B& buf, uint64_t bytes)
-{
-    HIPCHK(ctx, buf.grow(bytes, ctx->stream));
-    return ESLAM_OK;
-}
-
-// all_gather of `bytes` per rank from device memory into device memory
-static int comm_allgather(eslam_ctx* ctx, const void* dsend, void* drecv, uint64_t bytes)
-{
-    const eslam_comm& c = ctx->comm;
-    if (c.device_memory) {
-        if (c.allgather(c.user, dsend, drecv, bytes, (void*)ctx->stream) != 0)
-            return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
-        return ESLAM_OK;
-    }
-    int rc = grow(ctx, ctx->stage, bytes * (c.nranks + 1));
-    if (rc) return rc;
-    char* h = ctx->stage.as<char>();
-    HIPCHK(ctx, hipMemcpyAsync(h, dsend, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (c.allgather(c.user, h, h + bytes, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
-    HIPCHK(ctx, hipMemcpyAsync(drecv, h + bytes, bytes * c.nranks, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));     // the staging buffer is reused
-    return ESLAM_OK;
-}
-
-static int comm_alltoallv(eslam_ctx* ctx, const void* dsend, const uint64_t* sb, void* drecv, const uint64_t* rb,
-                          hipStream_t stream = nullptr)
-{
-    const eslam_comm& c = ctx->comm;
-    if (!stream) stream = ctx->stream;
-    if (c.device_memory) {
-        if (c.alltoallv(c.user, dsend, sb, drecv, rb, (void*)stream) != 0)
-            return fail(ctx, ESLAM_ERR_COMM, "alltoallv callback failed");
-        return ESLAM_OK;
-    }
-    uint64_t ts = 0, tr = 0;
-    for (int r = 0; r < c.nranks; ++r) { ts += sb[r]; tr += rb[r]; }
-    int rc = grow(ctx, ctx->stage, ts + tr + 64);
-    if (rc) return rc;
-    char* h = ctx->stage.as<char>();
-    char* hr = h + ((ts + 63) & ~63ull);
-    if (ts) HIPCHK(ctx, hipMemcpyAsync(h, dsend, ts, hipMemcpyDeviceToHost, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    if (c.alltoallv(c.user, h, sb, hr, rb, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "alltoallv callback failed");
-    if (tr) HIPCHK(ctx, hipMemcpyAsync(drecv, hr, tr, hipMemcpyHostToDevice, stream));
-    HIPCHK(ctx, hipStreamSynchronize(stream));
-    return ESLAM_OK;
-}
-
 static PlanParams plan_params(eslam_ctx* ctx)
 {
     PlanParams pp;
@@ -884,202 +594,6 @@ static PlanParams plan_params(eslam_ctx* ctx)
     pp.n_local = ctx->n;
     pp.J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
     return pp;
-}
-
-// sharded getCentroid: this rank's chunk records (padded to the largest shard), all ranks'
-// (G x that), and the tree's two ping-pong levels over the global chunks; 5 doubles a record
-static uint64_t centroid_bytes(const uint64_t* gall, int G, uint32_t J)
-{
-    const uint64_t csz = 64ull * J;
-    uint64_t maxch = 1, total = 0;
-    for (int r = 0; r < G; ++r) {
-        const uint64_t c = (gall[r + 1] - gall[r] + csz - 1) / csz;
-        maxch = c > maxch ? c : maxch;
-        total += c;
-    }
-    return (maxch + (uint64_t)G * maxch + 2 * (total ? total : 1)) * 5 * sizeof(double);
-}
-
-extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64_t n_global, const uint64_t* shard_gbase)
-{
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    free_particles(ctx);
-    if (ctx->statics_sharded) g_statics_sharded.fetch_sub(1);
-    ctx->statics_sharded = false;
-    if (!comm) {
-        ctx->sharded = false;
-        ctx->gall.clear();
-        ctx->gbase = 0;
-        ctx->n_global = 0;
-        return ESLAM_OK;
-    }
-    if (!shard_gbase || !comm->allgather || !comm->alltoallv || comm->nranks < 1 || comm->nranks > kMaxRanks ||
-        comm->rank < 0 || comm->rank >= comm->nranks)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: bad communicator (1 <= nranks <= 16)");
-    if (n_global == 0 || n_global > (1ull << 30) - 64)     // resample mark encoding (kMarkOwn)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: n_global must be in [1, 2^30 - 64]");
-    const uint64_t csz = 64ull * dm_chunk_rows_cfg(n_global, ctx->cfg.sum_chunk_rows);
-    if (shard_gbase[0] != 0 || shard_gbase[comm->nranks] != n_global)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: shard_gbase must run from 0 to n_global");
-    for (int r = 0; r < comm->nranks; ++r) {
-        if (shard_gbase[r + 1] <= shard_gbase[r])
-            return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: every shard needs at least one particle");
-        if (shard_gbase[r] % csz)
-            return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm: shard starts must be multiples of the summation chunk");
-    }
-    if (!ctx->mg) {
-        HIPCHK(ctx, ctx->recs.alloc(sizeof(Shard) * kNShard * kMaxRanks));
-        HIPCHK(ctx, ctx->mg.alloc(mg::kWords * 8));
-        HIPCHK(ctx, ctx->mg_host.alloc(mg::kWords * 8));
-        HIPCHK(ctx, hipMemset(ctx->recs, 0, sizeof(Shard) * kNShard * kMaxRanks));
-        HIPCHK(ctx, hipMemset(ctx->mg, 0, mg::kWords * 8));
-    }
-    {
-        // getCentroid's buffer (centroid_bytes): sized by the shard table, allocated here so
-        // the per-step getCentroid of a Rock task allocates nothing
-        const uint64_t need = centroid_bytes(shard_gbase, comm->nranks, dm_chunk_rows_cfg(n_global, ctx->cfg.sum_chunk_rows));
-        if (need > ctx->cent.cap()) HIPCHK(ctx, ctx->cent.alloc(need));
-    }
-    if ((ctx->cfg.flags & ESLAM_FLAG_PROCESS_STATICS) && comm->nranks > 1) {
-        if (g_statics_sharded.fetch_add(1) != 0) {
-            g_statics_sharded.fetch_sub(1);
-            return fail(ctx, ESLAM_ERR_INVALID_ARG,
-                        "eslam_gpu_set_comm: ESLAM_FLAG_PROCESS_STATICS allows one sharded context per process "
-                        "(ranks in one process would share the respawn counter and rand())");
-        }
-        ctx->statics_sharded = true;
-    }
-    ctx->comm = *comm;
-    ctx->sharded = true;
-    ctx->gall.assign(shard_gbase, shard_gbase + comm->nranks + 1);
-    ctx->n_global = n_global;
-    ctx->gbase = shard_gbase[comm->rank];
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// RCCL transport (eslam_gpu_set_comm_rccl): the eslam_comm callbacks implemented in C++ on
-// the context's stream, RCCL resolved at run time (the process's librccl.so.1 -- the one
-// torch loaded, if any -- so one RCCL serves both)
-// ---------------------------------------------------------------------------------------
-namespace {
-struct RcclApi {
-    bool ok = false;
-    decltype(&ncclGetUniqueId) get_unique_id = nullptr;
-    decltype(&ncclCommInitRank) comm_init_rank = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy = nullptr;
-    decltype(&ncclAllGather) all_gather = nullptr;
-    decltype(&ncclSend) send = nullptr;
-    decltype(&ncclRecv) recv = nullptr;
-    decltype(&ncclGroupStart) group_start = nullptr;
-    decltype(&ncclGroupEnd) group_end = nullptr;
-    decltype(&ncclGetErrorString) error_string = nullptr;
-};
-
-const RcclApi& rccl_api()
-{
-    static RcclApi api = [] {
-        RcclApi a;
-        void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) return a;
-#define ESLAM_SYM(f, name) a.f = reinterpret_cast<decltype(a.f)>(dlsym(h, name))
-        ESLAM_SYM(get_unique_id, "ncclGetUniqueId");
-        ESLAM_SYM(comm_init_rank, "ncclCommInitRank");
-        ESLAM_SYM(comm_destroy, "ncclCommDestroy");
-        ESLAM_SYM(all_gather, "ncclAllGather");
-        ESLAM_SYM(send, "ncclSend");
-        ESLAM_SYM(recv, "ncclRecv");
-        ESLAM_SYM(group_start, "ncclGroupStart");
-        ESLAM_SYM(group_end, "ncclGroupEnd");
-        ESLAM_SYM(error_string, "ncclGetErrorString");
-#undef ESLAM_SYM
-        a.ok = a.get_unique_id && a.comm_init_rank && a.comm_destroy && a.all_gather && a.send && a.recv &&
-               a.group_start && a.group_end && a.error_string;
-        return a;
-    }();
-    return api;
-}
-
-int rccl_allgather_cb(void* user, const void* send, void* recv, uint64_t bytes, void* stream)
-{
-    eslam_ctx* ctx = static_cast<eslam_ctx*>(user);
-    const RcclApi& a = rccl_api();
-    return a.all_gather(send, recv, bytes, ncclUint8, static_cast<ncclComm_t>(ctx->rccl), static_cast<hipStream_t>(stream)) ==
-                   ncclSuccess ? 0 : 1;
-}
-
-int rccl_alltoallv_cb(void* user, const void* send, const uint64_t* send_bytes, void* recv, const uint64_t* recv_bytes,
-                      void* stream)
-{
-    eslam_ctx* ctx = static_cast<eslam_ctx*>(user);
-    const RcclApi& a = rccl_api();
-    const ncclComm_t comm = static_cast<ncclComm_t>(ctx->rccl);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    uint64_t so = 0, ro = 0;
-    if (a.group_start() != ncclSuccess) return 1;
-    int bad = 0;
-    for (int r = 0; r < ctx->comm.nranks; ++r) {
-        if (send_bytes[r]) bad |= a.send(static_cast<const char*>(send) + so, send_bytes[r], ncclUint8, r, comm, st) != ncclSuccess;
-        if (recv_bytes[r]) bad |= a.recv(static_cast<char*>(recv) + ro, recv_bytes[r], ncclUint8, r, comm, st) != ncclSuccess;
-        so += send_bytes[r];
-        ro += recv_bytes[r];
-    }
-    bad |= a.group_end() != ncclSuccess;
-    return bad;
-}
-
-void rccl_release(eslam_ctx* ctx)
-{
-    if (ctx->rccl) rccl_api().comm_destroy(static_cast<ncclComm_t>(ctx->rccl));
-    ctx->rccl = nullptr;
-}
-}  // namespace
-
-extern "C" int eslam_gpu_rccl_unique_id(uint8_t id[ESLAM_RCCL_ID_BYTES])
-{
-    if (!id) return ESLAM_ERR_INVALID_ARG;
-    const RcclApi& a = rccl_api();
-    if (!a.ok) return ESLAM_ERR_UNSUPPORTED;
-    ncclUniqueId u;
-    if (a.get_unique_id(&u) != ncclSuccess) return ESLAM_ERR_COMM;
-    static_assert(sizeof(u) == ESLAM_RCCL_ID_BYTES, "ncclUniqueId size");
-    memcpy(id, &u, sizeof(u));
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_set_comm_rccl(eslam_ctx* ctx, int32_t nranks, int32_t rank, const uint8_t id[ESLAM_RCCL_ID_BYTES],
-                                       uint64_t n_global, const uint64_t* shard_gbase)
-{
-    if (!ctx || !id) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    const RcclApi& a = rccl_api();
-    if (!a.ok) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "eslam_gpu_set_comm_rccl: librccl.so.1 not found");
-    if (nranks < 1 || nranks > kMaxRanks || rank < 0 || rank >= nranks)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_set_comm_rccl: bad communicator (1 <= nranks <= 16)");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    rccl_release(ctx);
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    ncclComm_t comm = nullptr;
-    const ncclResult_t r = a.comm_init_rank(&comm, nranks, u, rank);
-    if (r != ncclSuccess)
-        return fail(ctx, ESLAM_ERR_COMM, (std::string("ncclCommInitRank: ") + a.error_string(r)).c_str());
-    ctx->rccl = comm;
-    eslam_comm c;
-    memset(&c, 0, sizeof(c));
-    c.user = ctx;
-    c.rank = rank;
-    c.nranks = nranks;
-    c.device_memory = 1;
-    c.allgather = rccl_allgather_cb;
-    c.alltoallv = rccl_alltoallv_cb;
-    const int rc = eslam_gpu_set_comm(ctx, &c, n_global, shard_gbase);
-    if (rc) rccl_release(ctx);
-    return rc;
 }
 
 extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
@@ -1867,13 +1381,10 @@ static bool sm_alloc_grid(GridBufs* g, uint64_t ncell, uint64_t cap, bool height
 // the run scratch for `rec` records and `ncell` cells, carved from one allocation the context keeps
 static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t scan_patches, SmScratch* s, ScanPatch** sp)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     const size_t sort_bytes = eslam_sm_sort_bytes(rec);
-    const uint64_t off_keys = 0, off_vals = off_keys + up((rec + 1) * 4), off_ko = off_vals + up(rec * 4),
-                   off_ord = off_ko + up(rec * 4), off_app = off_ord + up(rec * 4), off_add = off_app + up(rec * sizeof(float2)),
-                   off_seg = off_add + up(ncell * 4), off_tch = off_seg + up(ncell * 4), off_cnt = off_tch + up(ncell * 4),
-                   off_sort = off_cnt + up(kSmCounters * 8), off_sp = off_sort + up(sort_bytes),
-                   total = off_sp + up(scan_patches * sizeof(ScanPatch));
+    Carver size(nullptr);
+    carve_sm(size, rec, ncell, scan_patches, sort_bytes, s, sp);
+    const uint64_t total = size.bytes();
     if (total > ctx->sm_mem.cap()) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->sm_mem.alloc(total) != hipSuccess) {
@@ -1881,66 +1392,14 @@ static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t sca
             return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the run scratch (lower max_records)");
         }
     }
-    char* m = ctx->sm_mem.as<char>();
-    s->keys = (uint32_t*)(m + off_keys);
-    s->vals = (uint32_t*)(m + off_vals);
-    s->keys_out = (uint32_t*)(m + off_ko);
-    s->order = (uint32_t*)(m + off_ord);
-    s->app = (float2*)(m + off_app);
-    s->add = (uint32_t*)(m + off_add);
-    s->segpos = (uint32_t*)(m + off_seg);
-    s->touched = (uint32_t*)(m + off_tch);
-    s->cnt = (uint64_t*)(m + off_cnt);
-    s->sort_tmp = m + off_sort;
-    s->sort_tmp_bytes = sort_bytes;
-    *sp = (ScanPatch*)(m + off_sp);
+    Carver place(ctx->sm_mem.get());
+    carve_sm(place, rec, ncell, scan_patches, sort_bytes, s, sp);
     return ESLAM_OK;
 }
 
 // ---- the merge on a sharded filter (eslam_gpu_shared_map_update_sharded): every rank merges
 // every run into its own copy of the grid, from the run's poses gathered in global order
 constexpr uint64_t kSmPoseBytes = kSmPoseWords * 8;
-constexpr uint64_t kSmXHead = 4096;          // ctx->sm_x starts with the small all_gathers' words
-
-// all_gather of `words` 64-bit words per rank between host arrays (device-memory callbacks:
-// through the head of ctx->sm_x)
-static int sm_allgather_words(eslam_ctx* ctx, const uint64_t* send, uint64_t* recv, uint32_t words)
-{
-    const eslam_comm& c = ctx->comm;
-    const uint64_t bytes = 8ull * words;
-    static_assert(8ull * 4 * (kMaxRanks + 1) <= kSmXHead, "the head holds four words per rank");
-    if (!c.device_memory) {
-        if (c.allgather(c.user, send, recv, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
-        return ESLAM_OK;
-    }
-    char* d = ctx->sm_x.as<char>();
-    HIPCHK(ctx, hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = comm_allgather(ctx, d, d + bytes, bytes);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(recv, d + bytes, bytes * c.nranks, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ESLAM_OK;
-}
-
-// ESLAM_OK on a rank means every rank passed `rc` = ESLAM_OK.  A failing rank keeps its own code
-// (and message); the others return ESLAM_ERR_COMM.
-static int sm_agree(eslam_ctx* ctx, int rc)
-{
-    const std::string msg = ctx->err;
-    const uint64_t mine = (uint64_t)(int64_t)rc;
-    uint64_t all[kMaxRanks] = {};
-    const int crc = sm_allgather_words(ctx, &mine, all, 1);
-    if (rc) {
-        ctx->err = msg;
-        return rc;
-    }
-    if (crc) return crc;
-    for (int r = 0; r < ctx->comm.nranks; ++r)
-        if (all[r])
-            return fail(ctx, ESLAM_ERR_COMM,
-                        ("shared_map_update_sharded: rank " + std::to_string(r) + " failed (" + std::to_string((int64_t)all[r]) + ")").c_str());
-    return ESLAM_OK;
-}
 
 // the pose records of the run's particles [i0, i0 + np) (global), in global order, into `recv`:
 // every rank stages its part of the run once per rank and the all_to_all_v hands every rank
@@ -2000,13 +1459,10 @@ static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t c
         if (count && ncell >= 0xffffffffull)
             return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
         if (const int rc_ = settle(ctx)) return rc_;           // a deferred sharded exchange first
-        if (ctx->sm_x.cap() < kSmXHead && ctx->sm_x.alloc(kSmXHead) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update_sharded: no device memory for the exchange");
-        }
         const uint64_t mine[3] = {count, max_records, sm_patch_hash(patches, count)};
         uint64_t all[3 * kMaxRanks] = {};
-        if (const int rc_ = sm_allgather_words(ctx, mine, all, 3)) return rc_;
+        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's buffer");
+        if (const int rc_ = host_allgather(ctx, mine, all, sizeof(mine))) return rc_;
         for (int r = 0; r < ctx->comm.nranks; ++r)
             if (memcmp(all + 3 * r, mine, sizeof(mine)) != 0)
                 return fail(ctx, ESLAM_ERR_INVALID_ARG,
@@ -2031,12 +1487,12 @@ static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t c
             // the staged copies (one per rank) and the gathered run
             const uint64_t G = ctx->comm.nranks, out = (G * per * kSmPoseBytes + 255) & ~255ull;
             hipError_t he_ = hipSuccess;
-            rc = ctx->sm_x.grow_keep(kSmXHead + out + per * kSmPoseBytes, 1, ctx->stream, &he_);
+            rc = ctx->sm_x.grow_keep(out + per * kSmPoseBytes, 1, ctx->stream, &he_);
             if (rc == ESLAM_ERR_OUT_OF_MEMORY)
                 return fail(ctx, rc, "shared_map_update_sharded: no device memory for the exchange (lower max_records)");
             if (rc) HIPCHK(ctx, he_);
-            x_send = reinterpret_cast<double*>(ctx->sm_x.as<char>() + kSmXHead);
-            x_recv = reinterpret_cast<double*>(ctx->sm_x.as<char>() + kSmXHead + out);
+            x_send = reinterpret_cast<double*>(ctx->sm_x.as<char>());
+            x_recv = reinterpret_cast<double*>(ctx->sm_x.as<char>() + out);
         }
         if (!rc) rc = materialize(ctx);                       // the particles as they stand
         if (rc) return rc;
@@ -2048,7 +1504,7 @@ static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t c
         return ESLAM_OK;
     };
     int rc = setup();
-    if (sh) rc = sm_agree(ctx, rc);                           // an allocation can fail on one rank only
+    if (sh) rc = agree(ctx, rc, "shared_map_update_sharded");   // an allocation can fail on one rank only
     if (rc) return rc;
     GridBufs spare;
     uint64_t spare_cap = 0;
@@ -2099,7 +1555,7 @@ static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t c
                 he = hipSuccess;
                 rc = ESLAM_ERR_HIP;
             }
-            rc = sm_agree(ctx, rc);
+            rc = agree(ctx, rc, "shared_map_update_sharded");
         }
         if (he != hipSuccess || rc) break;
         if (placed) {
@@ -2870,7 +2326,7 @@ static int exchange_tail(eslam_ctx* ctx, uint64_t epoch, PlanParams& pp, uint64_
 }
 
 // complete a deferred exchange before anything else reads the particles or the marks
-static int settle(eslam_ctx* ctx)
+int eslam_host::settle(eslam_ctx* ctx)
 {
     if (!ctx->xpend) return ESLAM_OK;
     ctx->xpend = false;
@@ -3339,11 +2795,11 @@ static int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resam
     if (rc) return rc;
     // everything the call allocates, first: a failure returns with the filter as it was
     const uint64_t tn = eslam_resample_tiles(n), ts = eslam_resample_tiles(samples);
-    auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
-    const uint64_t o_coarse = up(n * 8), o_cnt = o_coarse + up(tn * 8), o_anc = o_cnt + 256, o_out = o_anc + up(samples * 4),
-                   o_kept = o_out + (multi ? up(samples * 4) : 0), bytes = o_kept + up((ts + 1) * 4);
+    ResampleScratch rs;
+    Carver size(nullptr);
+    carve_resample(size, n, tn, samples, ts, multi, &rs);
     hipError_t he = hipSuccess;
-    rc = ctx->rs_mem.grow_keep(bytes, 1, ctx->stream, &he);
+    rc = ctx->rs_mem.grow_keep(size.bytes(), 1, ctx->stream, &he);
     if (rc == ESLAM_ERR_HIP) return fail(ctx, rc, hipGetErrorString(he));
     if (rc) return fail(ctx, rc, "resample: no device memory for the cumulative sum and the draws");
     const bool growing = samples > ctx->cap;
@@ -3356,13 +2812,10 @@ static int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resam
         }
         HIPCHK(ctx, hipDeviceSynchronize());     // the new buffers' resets, before the stream uses them
     }
-    char* m = ctx->rs_mem;
-    uint64_t* C = reinterpret_cast<uint64_t*>(m);
-    uint64_t* coarse = reinterpret_cast<uint64_t*>(m + o_coarse);
-    uint64_t* counter = reinterpret_cast<uint64_t*>(m + o_cnt);
-    uint32_t* anc = reinterpret_cast<uint32_t*>(m + o_anc);
-    uint32_t* anc_kept = multi ? reinterpret_cast<uint32_t*>(m + o_out) : anc;
-    uint32_t* kept = reinterpret_cast<uint32_t*>(m + o_kept);
+    Carver place(ctx->rs_mem.get());
+    carve_resample(place, n, tn, samples, ts, multi, &rs);
+    uint64_t *const C = rs.C, *const coarse = rs.coarse, *const counter = rs.counter;
+    uint32_t *const anc = rs.anc, *const anc_kept = rs.anc_kept, *const kept = rs.kept;
     ctx->dbg_valid = false;                      // the records no longer follow the particles
     const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
     HIPCHK(ctx, eslam_launch_weight_stats(ctx->st[0], ctx->st[1], n, J, ctx->ctl, ctx->shards, ctx->stream));
@@ -3723,46 +3176,6 @@ const char* const kSnapStreamSharded =
     "snapshot: a sharded filter is one file written and read by offset (eslam_gpu_save_at / eslam_gpu_load_at); "
     "a sequential stream cannot carry a part of it";
 
-// all_gather of `bytes` of host memory per rank
-int snap_allgather(eslam_ctx* ctx, const void* send, void* recv, uint64_t bytes)
-{
-    const eslam_comm& c = ctx->comm;
-    if (!c.device_memory) {
-        if (c.allgather(c.user, send, recv, bytes, nullptr) != 0) return fail(ctx, ESLAM_ERR_COMM, "allgather callback failed");
-        return ESLAM_OK;
-    }
-    Dev<char> d;
-    if (d.alloc(bytes * (c.nranks + 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the all_gather");
-    }
-    HIPCHK(ctx, hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = comm_allgather(ctx, d, d + bytes, bytes);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(recv, d + bytes, bytes * c.nranks, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ESLAM_OK;
-}
-
-// the last collective of a sharded save or load: ESLAM_OK on a rank means every rank succeeded.
-// A failing rank keeps its own code (and message); the others return ESLAM_ERR_COMM.
-int snap_agree(eslam_ctx* ctx, int rc)
-{
-    if (!ctx->sharded) return rc;
-    const std::string msg = ctx->err;
-    std::vector<int64_t> all(ctx->comm.nranks, 0);
-    const int64_t mine = rc;
-    const int crc = snap_allgather(ctx, &mine, all.data(), 8);
-    if (rc) {
-        ctx->err = msg;
-        return rc;
-    }
-    if (crc) return crc;
-    for (int r = 0; r < ctx->comm.nranks; ++r)
-        if (all[r]) return fail(ctx, ESLAM_ERR_COMM, ("snapshot: rank " + std::to_string(r) + " failed (" + std::to_string(all[r]) + ")").c_str());
-    return ESLAM_OK;
-}
-
 int snap_staging(eslam_ctx* ctx, uint64_t bytes)
 {
     for (int k = 0; k < 2; ++k)
@@ -3807,23 +3220,16 @@ int snap_read_count(eslam_ctx* ctx, const uint32_t* dev, uint64_t* out)
 int snap_census(eslam_ctx* ctx, SnapPlan& pl)
 {
     const LocalMaps& lm = ctx->lm;
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
-    const uint64_t o_first = 0, o_trank = o_first + up(lm.ntables * 4), o_tlist = o_trank + up(lm.ntables * 4),
-                   o_fref = o_tlist + up(ctx->cap * 4), o_prank = o_fref + up(lm.npages * 8), o_plist = o_prank + up(lm.npages * 4),
-                   total = o_plist + up(lm.npages * 4);
+    SnapCensus& c = pl.cen;
+    Carver size(nullptr);
+    carve_census(size, lm.ntables, ctx->cap, lm.npages, &c);
     // kept until the maps are dropped (free_local_maps)
-    if (!ctx->lmb.census && ctx->lmb.census.alloc(total) != hipSuccess) {
+    if (!ctx->lmb.census && ctx->lmb.census.alloc(size.bytes()) != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the census");
     }
-    char* m = ctx->lmb.census.as<char>();
-    SnapCensus& c = pl.cen;
-    c.first = (uint32_t*)(m + o_first);
-    c.trank = (uint32_t*)(m + o_trank);
-    c.tlist = (uint32_t*)(m + o_tlist);
-    c.firstref = (uint64_t*)(m + o_fref);
-    c.prank = (uint32_t*)(m + o_prank);
-    c.plist = (uint32_t*)(m + o_plist);
+    Carver place(ctx->lmb.census.get());
+    carve_census(place, lm.ntables, ctx->cap, lm.npages, &c);
     const uint64_t n = ctx->n, ttiles = snap_tiles(n);
     int rc = grow(ctx, ctx->lmb.counts, (ttiles + 1) * 4);
     if (rc) return rc;
@@ -3863,7 +3269,8 @@ int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
         const int G = ctx->comm.nranks, me = ctx->comm.rank;
         const uint64_t mine[6] = {(uint64_t)(int64_t)rc, pl.T, pl.P, pl.h.n_patches, pl.sc.update_count, pl.sc.minstd};
         std::vector<uint64_t> all(6 * (size_t)G, 0);
-        const int crc = snap_allgather(ctx, mine, all.data(), sizeof(mine));
+        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's buffer");
+        const int crc = host_allgather(ctx, mine, all.data(), sizeof(mine));
         if (rc) {
             ctx->err = msg;
             return rc;
@@ -4066,7 +3473,7 @@ int snap_save(eslam_ctx* ctx, const SnapSink& w, bool positional, uint64_t chunk
         rc = fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: the buffer is smaller than the snapshot (eslam_gpu_snapshot_size)");
     else
         rc = snap_write_pieces(ctx, pl, w, chunk, &chunks);
-    rc = snap_agree(ctx, rc);
+    rc = agree(ctx, rc, "snapshot");
     if (rc) return rc;
     snap_fill_info(pl.h, chunks, info);
     return ESLAM_OK;
@@ -4630,7 +4037,7 @@ int snap_load(eslam_ctx* ctx, const SnapSource& r, bool positional, uint64_t chu
     }
     if (!rc) rc = snap_load_body(ctx, rd, h);
     if (rc) (void)hipStreamSynchronize(ctx->stream);
-    rc = snap_agree(ctx, rc);                // sharded: no rank goes on with a filter another rank could not load
+    rc = agree(ctx, rc, "snapshot");                // sharded: no rank goes on with a filter another rank could not load
     if (rc) {
         // the context reads as "no particles"; set_map + init_* or another load starts it over
         const std::string msg = ctx->err;

@@ -18,6 +18,7 @@
 
 #include "eslam_internal.h"
 #include "eslam_launch.h"
+#include "eslam_scratch.h"
 
 namespace eslam_dev {
 
@@ -167,20 +168,13 @@ static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kB
 
 extern "C" size_t eslam_pgrid_work_bytes(uint32_t width, uint32_t height, void* mem, PgScratch* s)
 {
-    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
     const uint64_t tx = ((uint64_t)width + 7) / 8, ty = ((uint64_t)height + 7) / 8, ncell = (uint64_t)width * height;
     const uint64_t blocks = blocks_for(ncell + 1);
-    const uint64_t off_dir = 0, off_bsum = off_dir + up(tx * ty * 4), off_own = off_bsum + up((blocks + 1) * 4),
-                   total = off_own + up(8);
-    if (mem && s) {
-        char* m = static_cast<char*>(mem);
-        s->dir = reinterpret_cast<uint32_t*>(m + off_dir);
-        s->bsum = reinterpret_cast<uint32_t*>(m + off_bsum);
-        s->own = reinterpret_cast<uint64_t*>(m + off_own);
-        s->tx = (uint32_t)tx;
-        s->ty = (uint32_t)ty;
-    }
-    return total;
+    eslam_buf::Carver c(mem);
+    PgScratch p = {};
+    eslam_host::carve_pgrid(c, tx, ty, blocks, &p);
+    if (mem && s) *s = p;
+    return c.bytes();
 }
 
 // the directory of the table *sidp names, the blocks' composed counts in s->bsum and the own

@@ -20,6 +20,7 @@
 
 #include "eslam_internal.h"
 #include "eslam_launch.h"
+#include "eslam_scratch.h"
 
 namespace eslam_dev {
 
@@ -164,32 +165,16 @@ static int scan_passes(uint32_t ncell)
     return (bits + 7) / 8;
 }
 
-static uint64_t up256(uint64_t b) { return (b + 255) & ~(uint64_t)255; }
-
 // the scratch of a build of n points: its size, and its arrays within `mem` (may be null: size only)
 extern "C" size_t eslam_scan_work_bytes(uint64_t n, void* mem, ScanWork* w)
 {
     size_t sort_bytes = 0;
     (void)eslam_radix_sort_pairs_passes(nullptr, nullptr, nullptr, nullptr, n, nullptr, &sort_bytes, 4, nullptr);
-    const uint64_t u = up256((n + 1) * 4), d = up256((n ? n : 1) * 8);
-    uint64_t off = 0;
-    char* m = (char*)mem;
+    eslam_buf::Carver c(mem);
     ScanWork s = {};
-    s.a = (uint32_t*)(m + off); off += u;
-    s.b = (uint32_t*)(m + off); off += u;
-    s.c = (uint32_t*)(m + off); off += u;
-    s.d = (uint32_t*)(m + off); off += u;
-    s.e = (uint32_t*)(m + off); off += u;
-    s.raw = (uint32_t*)(m + off); off += u;
-    s.pz = (double*)(m + off); off += d;
-    s.var = (double*)(m + off); off += d;
-    s.sz = (double*)(m + off); off += d;
-    s.sv = (double*)(m + off); off += d;
-    s.cnt = (uint64_t*)(m + off); off += up256(kScanCounters * 8);
-    s.sort_tmp = m + off; off += up256(sort_bytes);
-    s.sort_tmp_bytes = sort_bytes;
+    eslam_host::carve_scan(c, n, sort_bytes, &s);
     if (mem && w) *w = s;
-    return off;
+    return c.bytes();
 }
 
 // stage 1: the points, both sorts, the segment heads.  Afterwards w->b[n] holds the segment count

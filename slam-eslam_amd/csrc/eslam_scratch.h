@@ -1,0 +1,91 @@
+// eslam_scratch.h -- host-only: the layouts of the scratch blocks that are carved from one device
+// allocation each.  A layout is a function of a Carver (eslam_buf.h) that names every array once,
+// in the block's order; its caller runs it over a null base for the block's size and over the
+// block for the pointers.  Plain functions of sizes, so tests/cpp/test_buf.cpp checks them
+// without a device.
+#pragma once
+
+#include "eslam_internal.h"
+#include "eslam_buf.h"
+
+namespace eslam_host {
+
+using eslam_buf::Carver;
+
+// eslam_gpu_shared_map_update's run scratch: `rec` records, `ncell` cells, the sort's
+// `sort_bytes` (eslam_sm_sort_bytes) and the scan's patches
+inline void carve_sm(Carver& c, uint64_t rec, uint64_t ncell, uint64_t scan_patches, size_t sort_bytes, eslam_dev::SmScratch* s,
+                     eslam_dev::ScanPatch** sp)
+{
+    s->keys = c.take<uint32_t>(rec + 1);
+    s->vals = c.take<uint32_t>(rec);
+    s->keys_out = c.take<uint32_t>(rec);
+    s->order = c.take<uint32_t>(rec);
+    s->app = c.take<float2>(rec);
+    s->add = c.take<uint32_t>(ncell);
+    s->segpos = c.take<uint32_t>(ncell);
+    s->touched = c.take<uint32_t>(ncell);
+    s->cnt = c.take<uint64_t>(eslam_dev::kSmCounters);
+    s->sort_tmp = c.take_bytes(sort_bytes);
+    s->sort_tmp_bytes = sort_bytes;
+    *sp = c.take<eslam_dev::ScanPatch>(scan_patches);
+}
+
+// a resample of n particles (tn tiles) to `samples` (ts tiles): the cumulative sum, its coarse
+// level, the counter's line, the draws' ancestors, the compacted ancestors (the multinomial draw
+// only; otherwise the draws' own) and the compaction's counts
+struct ResampleScratch {
+    uint64_t *C, *coarse, *counter;
+    uint32_t *anc, *anc_kept, *kept;
+};
+inline void carve_resample(Carver& c, uint64_t n, uint64_t tn, uint64_t samples, uint64_t ts, bool multi, ResampleScratch* s)
+{
+    s->C = c.take<uint64_t>(n);
+    s->coarse = c.take<uint64_t>(tn);
+    s->counter = c.take<uint64_t>(1);
+    s->anc = c.take<uint32_t>(samples);
+    s->anc_kept = multi ? c.take<uint32_t>(samples) : s->anc;
+    s->kept = c.take<uint32_t>(ts + 1);
+}
+
+// a snapshot's census over `ntables` pool tables, `cap` particles and `npages` pool pages
+// (SnapCensus::counts is a buffer of its own)
+inline void carve_census(Carver& c, uint64_t ntables, uint64_t cap, uint64_t npages, eslam_dev::SnapCensus* s)
+{
+    s->first = c.take<uint32_t>(ntables);
+    s->trank = c.take<uint32_t>(ntables);
+    s->tlist = c.take<uint32_t>(cap);
+    s->firstref = c.take<uint64_t>(npages);
+    s->prank = c.take<uint32_t>(npages);
+    s->plist = c.take<uint32_t>(npages);
+}
+
+// a scan build of n points with the radix sort's `sort_bytes`
+inline void carve_scan(Carver& c, uint64_t n, size_t sort_bytes, eslam_dev::ScanWork* s)
+{
+    s->a = c.take<uint32_t>(n + 1);
+    s->b = c.take<uint32_t>(n + 1);
+    s->c = c.take<uint32_t>(n + 1);
+    s->d = c.take<uint32_t>(n + 1);
+    s->e = c.take<uint32_t>(n + 1);
+    s->raw = c.take<uint32_t>(n + 1);
+    s->pz = c.take<double>(n ? n : 1);
+    s->var = c.take<double>(n ? n : 1);
+    s->sz = c.take<double>(n ? n : 1);
+    s->sv = c.take<double>(n ? n : 1);
+    s->cnt = c.take<uint64_t>(eslam_dev::kScanCounters);
+    s->sort_tmp = c.take_bytes(sort_bytes);
+    s->sort_tmp_bytes = sort_bytes;
+}
+
+// a particle-grid composition on tx x ty tiles with `blocks` blocks of cells
+inline void carve_pgrid(Carver& c, uint64_t tx, uint64_t ty, uint64_t blocks, eslam_dev::PgScratch* s)
+{
+    s->dir = c.take<uint32_t>(tx * ty);
+    s->bsum = c.take<uint32_t>(blocks + 1);
+    s->own = c.take<uint64_t>(1);
+    s->tx = (uint32_t)tx;
+    s->ty = (uint32_t)ty;
+}
+
+}  // namespace eslam_host

@@ -1,5 +1,6 @@
 // test_buf.cpp -- the owners of csrc/eslam_buf.h against counting, malloc-backed stand-ins for the
-// HIP calls they make (no HIP library is linked; built with ASan + UBSan by tests/test_buf.py).
+// HIP calls they make (no HIP library is linked; built with ASan + UBSan by tests/test_buf.py);
+// its Carver, and the scratch layouts of csrc/eslam_scratch.h that are written with it.
 // Every check prints on failure; the program exits non-zero if one failed or if an allocation or
 // an event is still live at the end.
 #include <stdio.h>
@@ -10,6 +11,7 @@
 #include <utility>
 
 #include "../../slam-eslam_amd/csrc/eslam_buf.h"
+#include "../../slam-eslam_amd/csrc/eslam_scratch.h"
 
 namespace {
 
@@ -280,8 +282,161 @@ static void test_events()
     CHECK(g_events.empty());                     // every event destroyed with its ring
 }
 
+static bool aligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % 256 == 0; }
+
+static void test_carver()
+{
+    // a null base only measures
+    Carver m(nullptr);
+    CHECK(m.bytes() == 0);
+    CHECK(m.take<uint32_t>(5) == nullptr && m.bytes() == 256);
+    CHECK(m.take_bytes(257) == nullptr && m.bytes() == 768);
+    CHECK(m.take<double>(0) == nullptr && m.bytes() == 768);     // a count of 0 takes nothing
+    CHECK(m.take_bytes(0) == nullptr && m.bytes() == 768);
+    CHECK(m.take_bytes(13) == nullptr && m.bytes() == 1024);
+    CHECK(m.take<uint64_t>(3) == nullptr && m.bytes() == 1280);
+    // the same takes over a block: the same size, every array aligned and clear of the next
+    char* block = static_cast<char*>(aligned_alloc(256, m.bytes()));
+    Carver p(block);
+    uint32_t* a = p.take<uint32_t>(5);
+    char* b = static_cast<char*>(p.take_bytes(257));
+    double* z = p.take<double>(0);
+    void* z2 = p.take_bytes(0);
+    char* odd = static_cast<char*>(p.take_bytes(13));
+    uint64_t* w = p.take<uint64_t>(3);                           // after an odd-sized region
+    CHECK(p.bytes() == m.bytes());
+    CHECK(aligned(a) && aligned(b) && aligned(z) && aligned(odd) && aligned(w));
+    CHECK((char*)a == block && b == block + 256 && (char*)z == block + 768 && z2 == (void*)z && odd == block + 768 &&
+          (char*)w == block + 1024);
+    CHECK((char*)(a + 5) <= b && b + 257 <= odd && odd + 13 <= (char*)w && (char*)(w + 3) <= block + p.bytes());
+    for (int k = 0; k < 5; ++k) a[k] = 1u;                       // the sanitizers see every store
+    for (int k = 0; k < 257; ++k) b[k] = 2;
+    for (int k = 0; k < 13; ++k) odd[k] = 3;
+    for (int k = 0; k < 3; ++k) w[k] = 4u;
+    CHECK(a[4] == 1u && b[0] == 2 && b[256] == 2 && odd[12] == 3 && w[0] == 4u && w[2] == 4u);
+    free(block);
+    // another alignment
+    alignas(64) char small[192];
+    Carver q(small, 64);
+    CHECK(q.take_bytes(1) == small && q.take<uint64_t>(9) == (uint64_t*)(small + 64) && q.bytes() == 192);
+}
+
+// A layout's arrays over a block of its measured size, as offsets from the block's start.
+struct Placed {
+    char* block;
+    uint64_t bytes;
+    explicit Placed(uint64_t b) : block(static_cast<char*>(aligned_alloc(256, b ? b : 256))), bytes(b) {}
+    ~Placed() { free(block); }
+    uint64_t off(const void* p) const { return (uint64_t)(static_cast<const char*>(p) - block); }
+};
+
+// The five scratch layouts of csrc/eslam_scratch.h against the offsets the hand-written chains of
+// `off_*` constants gave before the Carver (restated here as plain arithmetic): no array moved.
+static void test_layouts()
+{
+    using namespace eslam_host;
+    using namespace eslam_dev;
+    auto up = [](uint64_t b) { return (b + 255) & ~(uint64_t)255; };
+    const uint64_t counts[3] = {1, 63, 257};
+    static_assert(sizeof(float2) == 8 && sizeof(ScanPatch) == 32 && kSmCounters == 8 && kScanCounters == 4, "unit sizes");
+    for (uint64_t x : counts)
+        for (uint64_t y : counts)
+            for (uint64_t v : counts) {
+                {   // sm_scratch: x records, y cells, v scan patches
+                    const uint64_t rec = x, ncell = y, sort_bytes = 1000 + 7 * x;
+                    const uint64_t off_keys = 0, off_vals = off_keys + up((rec + 1) * 4), off_ko = off_vals + up(rec * 4),
+                                   off_ord = off_ko + up(rec * 4), off_app = off_ord + up(rec * 4), off_add = off_app + up(rec * 8),
+                                   off_seg = off_add + up(ncell * 4), off_tch = off_seg + up(ncell * 4),
+                                   off_cnt = off_tch + up(ncell * 4), off_sort = off_cnt + up(8 * 8),
+                                   off_sp = off_sort + up(sort_bytes), total = off_sp + up(v * 32);
+                    SmScratch s = {};
+                    ScanPatch* sp = nullptr;
+                    Carver size(nullptr);
+                    carve_sm(size, rec, ncell, v, sort_bytes, &s, &sp);
+                    CHECK(size.bytes() == total && s.keys == nullptr && sp == nullptr);
+                    Placed b(total);
+                    Carver place(b.block);
+                    carve_sm(place, rec, ncell, v, sort_bytes, &s, &sp);
+                    CHECK(place.bytes() == total);
+                    CHECK(b.off(s.keys) == off_keys && b.off(s.vals) == off_vals && b.off(s.keys_out) == off_ko &&
+                          b.off(s.order) == off_ord && b.off(s.app) == off_app && b.off(s.add) == off_add &&
+                          b.off(s.segpos) == off_seg && b.off(s.touched) == off_tch && b.off(s.cnt) == off_cnt &&
+                          b.off(s.sort_tmp) == off_sort && s.sort_tmp_bytes == sort_bytes && b.off(sp) == off_sp);
+                }
+                for (int multi = 0; multi < 2; ++multi) {   // resample_to: x particles, y samples
+                    const uint64_t n = x, samples = y, tn = (n + 255) / 256 + v, ts = (samples + 255) / 256 + v;
+                    const uint64_t o_coarse = up(n * 8), o_cnt = o_coarse + up(tn * 8), o_anc = o_cnt + 256,
+                                   o_out = o_anc + up(samples * 4), o_kept = o_out + (multi ? up(samples * 4) : 0),
+                                   bytes = o_kept + up((ts + 1) * 4);
+                    ResampleScratch r = {};
+                    Carver size(nullptr);
+                    carve_resample(size, n, tn, samples, ts, multi != 0, &r);
+                    CHECK(size.bytes() == bytes && r.C == nullptr && r.anc_kept == nullptr);
+                    Placed b(bytes);
+                    Carver place(b.block);
+                    carve_resample(place, n, tn, samples, ts, multi != 0, &r);
+                    CHECK(place.bytes() == bytes);
+                    CHECK(b.off(r.C) == 0 && b.off(r.coarse) == o_coarse && b.off(r.counter) == o_cnt && b.off(r.anc) == o_anc &&
+                          b.off(r.anc_kept) == (multi ? o_out : o_anc) && b.off(r.kept) == o_kept);
+                }
+                {   // snap_census: x tables, y particles (the capacity), v pages
+                    const uint64_t ntables = x, cap = y, npages = v;
+                    const uint64_t o_first = 0, o_trank = o_first + up(ntables * 4), o_tlist = o_trank + up(ntables * 4),
+                                   o_fref = o_tlist + up(cap * 4), o_prank = o_fref + up(npages * 8),
+                                   o_plist = o_prank + up(npages * 4), total = o_plist + up(npages * 4);
+                    SnapCensus c = {};
+                    Carver size(nullptr);
+                    carve_census(size, ntables, cap, npages, &c);
+                    CHECK(size.bytes() == total && c.first == nullptr);
+                    Placed b(total);
+                    Carver place(b.block);
+                    carve_census(place, ntables, cap, npages, &c);
+                    CHECK(place.bytes() == total && c.counts == nullptr);
+                    CHECK(b.off(c.first) == o_first && b.off(c.trank) == o_trank && b.off(c.tlist) == o_tlist &&
+                          b.off(c.firstref) == o_fref && b.off(c.prank) == o_prank && b.off(c.plist) == o_plist);
+                }
+                {   // the particle-grid work block: x x y tiles, v blocks
+                    const uint64_t tx = x, ty = y, blocks = v;
+                    const uint64_t off_dir = 0, off_bsum = off_dir + up(tx * ty * 4), off_own = off_bsum + up((blocks + 1) * 4),
+                                   total = off_own + up(8);
+                    PgScratch g = {};
+                    Carver size(nullptr);
+                    carve_pgrid(size, tx, ty, blocks, &g);
+                    CHECK(size.bytes() == total && g.dir == nullptr);
+                    Placed b(total);
+                    Carver place(b.block);
+                    carve_pgrid(place, tx, ty, blocks, &g);
+                    CHECK(place.bytes() == total && g.tx == tx && g.ty == ty);
+                    CHECK(b.off(g.dir) == off_dir && b.off(g.bsum) == off_bsum && b.off(g.own) == off_own);
+                }
+            }
+    const uint64_t points[4] = {0, 1, 63, 257};
+    for (uint64_t n : points) {   // the scan work block: n points (0: the doubles still have one element)
+        const uint64_t sort_bytes = 777 + n;
+        const uint64_t u = up((n + 1) * 4), d = up((n ? n : 1) * 8);
+        uint64_t off = 0, at[12];
+        for (int k = 0; k < 6; ++k) { at[k] = off; off += u; }       // a, b, c, d, e, raw
+        for (int k = 6; k < 10; ++k) { at[k] = off; off += d; }      // pz, var, sz, sv
+        at[10] = off; off += up(4 * 8);                              // cnt
+        at[11] = off; off += up(sort_bytes);                         // sort_tmp
+        ScanWork w = {};
+        Carver size(nullptr);
+        carve_scan(size, n, sort_bytes, &w);
+        CHECK(size.bytes() == off && w.a == nullptr && w.sort_tmp == nullptr);
+        Placed b(off);
+        Carver place(b.block);
+        carve_scan(place, n, sort_bytes, &w);
+        CHECK(place.bytes() == off && w.sort_tmp_bytes == sort_bytes);
+        CHECK(b.off(w.a) == at[0] && b.off(w.b) == at[1] && b.off(w.c) == at[2] && b.off(w.d) == at[3] && b.off(w.e) == at[4] &&
+              b.off(w.raw) == at[5] && b.off(w.pz) == at[6] && b.off(w.var) == at[7] && b.off(w.sz) == at[8] &&
+              b.off(w.sv) == at[9] && b.off(w.cnt) == at[10] && b.off(w.sort_tmp) == at[11]);
+    }
+}
+
 int main()
 {
+    test_carver();
+    test_layouts();
     test_lifetime();
     test_move();
     test_grow();

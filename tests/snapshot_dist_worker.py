@@ -1,7 +1,11 @@
-"""One gloo rank of tests/test_gpu_snapshot_sharded.py: a sharded GPU filter runs a short
+"""One rank of tests/test_gpu_snapshot_sharded.py: a sharded GPU filter runs a short
 program of scenario steps and positional saves and loads of one shared file.
 
-    RANK=r WORLD_SIZE=w ESLAM_DIST_STORE=file python tests/snapshot_dist_worker.py SCENARIO N_GLOBAL OUT.npz PROGRAM
+    RANK=r WORLD_SIZE=w ESLAM_DIST_STORE=file python tests/snapshot_dist_worker.py SCENARIO N_GLOBAL OUT.npz PROGRAM [MEM]
+
+MEM (as in tests/dist_worker.py): 'host' (the default) exchanges host buffers over gloo; 'device'
+exchanges device buffers through the torch.distributed callbacks (nccl); 'rccl' goes over the
+library's own RCCL communicator (eslam_gpu_set_comm_rccl).
 
 PROGRAM is a JSON list of operations:
     ["prepare"]                 set_map and the scenario's initialisation of this rank's shard
@@ -81,18 +85,25 @@ def refusals(rec, dist, comm, name, n_global, good, other):
 
 def main():
     name, n_global, out, program = sys.argv[1], int(sys.argv[2]), sys.argv[3], json.loads(sys.argv[4])
+    mem = sys.argv[5] if len(sys.argv) > 5 else "host"
+    import torch
     import torch.distributed as dist
     import eslam_dist
     from snapshot_shard_scenarios import advance, config, prepare
     rank = int(os.environ["RANK"])
-    dist.init_process_group("gloo", init_method="file://" + os.environ["ESLAM_DIST_STORE"], rank=rank,
-                            world_size=int(os.environ["WORLD_SIZE"]))
-    comm = eslam_dist.TorchComm(device_memory=False)
+    if mem in ("device", "rccl"):
+        torch.cuda.set_device(0)
+    dist.init_process_group("nccl" if mem in ("device", "rccl") else "gloo", init_method="file://" + os.environ["ESLAM_DIST_STORE"],
+                            rank=rank, world_size=int(os.environ["WORLD_SIZE"]))
+    comm = eslam_dist.TorchComm(device_memory=(mem in ("device", "rccl")))
     rec = {}
     if program[0][0] == "refusals":
         refusals(rec, dist, comm, name, n_global, program[0][1], program[0][2])
     else:
-        f = eslam_dist.ShardedGpuFilter(config(name, n_global), n_global, comm, device=0)
+        if mem == "rccl":
+            f = eslam_dist.RcclShardedGpuFilter(config(name, n_global), n_global, rank, comm.nranks, device=0)
+        else:
+            f = eslam_dist.ShardedGpuFilter(config(name, n_global), n_global, comm, device=0)
         lo, hi = f.bounds[rank], f.bounds[rank + 1]
         for k, op in enumerate(program):
             if op[0] == "prepare":

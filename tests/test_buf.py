@@ -1,4 +1,5 @@
-"""The owning buffer, event and event-ring types of csrc/eslam_buf.h (CPU only): tests/cpp/test_buf.cpp
+"""The owning buffer, event and event-ring types and the Carver of csrc/eslam_buf.h, and the scratch
+layouts of csrc/eslam_scratch.h (CPU only): tests/cpp/test_buf.cpp
 supplies counting, malloc-backed stand-ins for the HIP calls they make and is built with ASan and
 UBSan into tests/cpp/_build/ (git-ignored), so a double free, a leak or a use after free in the
 owners fails here, with no HIP library linked and no GPU."""
@@ -8,7 +9,9 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "test_buf.cpp")
 EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_buf")
-DEPS = [SRC, os.path.join(ROOT, "slam-eslam_amd", "csrc", "eslam_buf.h"), os.path.join(ROOT, "include", "eslam_gpu.h")]
+CSRC = os.path.join(ROOT, "slam-eslam_amd", "csrc")
+DEPS = [SRC, os.path.join(CSRC, "eslam_buf.h"), os.path.join(CSRC, "eslam_scratch.h"), os.path.join(CSRC, "eslam_internal.h"),
+        os.path.join(ROOT, "include", "eslam_gpu.h"), os.path.join(ROOT, "include", "eslam_detmath.h")]
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
 CXXFLAGS = ["-std=c++17", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM_INCLUDE}", "-fsanitize=address,undefined",
             "-fno-sanitize-recover=undefined", "-g", "-O1", "-Wall", "-Wextra"]

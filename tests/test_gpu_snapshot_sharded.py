@@ -23,9 +23,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SMALL = 4096                                     # chunk_bytes: runs and rows split across many chunks
 
 
-def launch(name, n_global, world, tmp, program, tag, timeout=240):
+def launch(name, n_global, world, tmp, program, tag, timeout=240, mem="host"):
     """Run the ranks on `program`; they meet through a FileStore in `tmp`.  Every rank is under a
-    time limit, and its expiry kills all of them."""
+    time limit, and its expiry kills all of them.  mem: the worker's exchange ('host', 'device' or 'rccl')."""
     store = os.path.join(tmp, f"store_{tag}")
     if os.path.exists(store):
         os.remove(store)
@@ -34,7 +34,7 @@ def launch(name, n_global, world, tmp, program, tag, timeout=240):
         out = os.path.join(tmp, f"{tag}_{r}.npz")
         env = dict(os.environ, RANK=str(r), LOCAL_RANK="0", WORLD_SIZE=str(world), ESLAM_DIST_STORE=store, OMP_NUM_THREADS="1")
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "snapshot_dist_worker.py"), name, str(n_global), out,
-                                       json.dumps(program)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+                                       json.dumps(program), mem], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
         outs.append(out)
     logs = []
     for p in procs:
@@ -273,6 +273,38 @@ def test_one_context(gpu_mod, tmp_path, name):
     assert save_at_bytes(g, len(want[1]))[0] == want[1]
     assert_infos([rec], want[2], "one rank")
     g.close()
+
+
+def test_one_rank_device_memory_and_rccl(gpu_mod, tmp_path):
+    """the host-word collectives' device-memory branch (the plan's counts and the agreements go
+    through the context's small device buffer): one rank loads the one-GPU blob and saves it in
+    4 KiB chunks, continues and saves again, with device-memory callbacks and over the library's
+    own RCCL communicator.  Both write the host-memory run's bytes, and end where the one-GPU
+    filter does.  The three one-rank groups run one after another: a worker that fails ends the
+    test before the next one starts."""
+    name, n_global = "maps", 1500
+    b, e, rec = single(gpu_mod, name, n_global)
+    tmp = str(tmp_path)
+    fb = os.path.join(tmp, "B.snap")
+    open(fb, "wb").write(b)
+    k = SC.SAVE_AT[name]
+    mems = ("host", "device", "rccl")
+    files = {m: (os.path.join(tmp, f"S_{m}.snap"), os.path.join(tmp, f"E_{m}.snap")) for m in mems}
+
+    def run(m):
+        fs, fe = files[m]
+        return launch(name, n_global, 1, tmp, [["load", fb, SMALL], ["save", fs, SMALL], ["steps", k, k + SC.MORE],
+                                               ["save", fe, SMALL]], f"one_{m}", mem=m)
+
+    parts = {m: run(m) for m in mems}            # launch() asserts every worker's exit status
+    host_s, host_e = (blob_of(p) for p in files["host"])
+    assert_same_filter(host_e, e, "host, one rank")
+    for m in ("device", "rccl"):
+        assert blob_of(files[m][0]) == host_s, f"{m}: the blob saved after the load"
+        assert blob_of(files[m][1]) == host_e, f"{m}: the blob saved after three more steps"
+        assert_same_filter(blob_of(files[m][1]), e, f"{m}, one rank")
+        assert_infos(parts[m], rec, m)
+        assert list(parts[m][0]["op1/save"][:2]) == [len(host_s), n_global]
 
 
 def test_refusals_and_agreement(gpu_mod, tmp_path):
