@@ -2179,4 +2179,119 @@ DM_FN void dm_scan_cluster_patch(const double* z, const double* var, uint32_t le
     *stdev = dm_sqrt(1.0 / sw + sd / sw);
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* the pose distribution's 2-D Gaussian mixture over (x, y)                */
+/* ------------------------------------------------------------------------------------ */
+/* One pass sums, per component k, S0 Sx Sy Sxx Sxy Syy at rec[6 k ..], then W = sum of the
+ * scaled weights at rec[6 K] and Lambda = sum of scaled weight x log-likelihood at
+ * rec[6 K + 1], all in the canonical chunk order.  Coordinates are relative to the centre of
+ * the valid particles' bounding box, weights scaled by 2^-E (E = dm_stat_exp(max w)).      */
+#define DM_GMM_MAX 8
+#define DM_GMM_REC(K) (6 * (K) + 2)
+#define DM_LOG_2PI 1.8378770664093453   /* RN(log(2 pi)) */
+
+typedef struct dm_gmm_comp {
+    double weight, mx, my;                  /* pi, and the mean relative to the centre        */
+    double cxx, cxy, cyy;                   /* the covariance                                 */
+    double axx, axy, ayy, det;              /* A = cov + min_variance I and its determinant   */
+    double lc;                              /* dm_log(pi) - 0.5 dm_log(det)                   */
+    int32_t live;                           /* takes part in the E-step                       */
+    int32_t set;                            /* the last M-step formed its parameters (else 0s) */
+} dm_gmm_comp;
+
+/* a particle is fitted when x, y and w are finite and w > 0 */
+DM_FN int dm_gmm_valid(double x, double y, double w)
+{
+    return dm_isfinite(x) && dm_isfinite(y) && dm_isfinite(w) && w > 0.0;
+}
+
+/* the initial component of a particle at a on the longer axis [amin, amin + K h] */
+DM_FN int dm_gmm_hard(double a, double amin, double h, int K)
+{
+    if (!(h > 0.0)) return 0;
+    const double f = dm_floor((a - amin) / h);
+    return f >= (double)(K - 1) ? K - 1 : (int)f;
+}
+
+/* M-step: the parameters of the sums S (6 per component).  c[k].live on entry: the component
+ * was live in the pass that formed S (all 1 before the first call); a dead one stays dead.
+ * Returns the live components.                                                             */
+DM_FN int dm_gmm_mstep(const double* S, int K, double min_variance, dm_gmm_comp* c)
+{
+    double tot = 0.0;
+    for (int k = 0; k < K; ++k) tot = tot + S[6 * k];
+    int nlive = 0;
+    for (int k = 0; k < K; ++k) {
+        const double* s = S + 6 * k;
+        dm_gmm_comp* p = &c[k];
+        if (!p->live || s[0] == 0.0) {
+            p->weight = p->mx = p->my = p->cxx = p->cxy = p->cyy = 0.0;
+            p->axx = p->axy = p->ayy = p->det = p->lc = 0.0;
+            p->live = p->set = 0;
+            continue;
+        }
+        p->set = 1;
+        p->weight = s[0] / tot;
+        p->mx = s[1] / s[0];
+        p->my = s[2] / s[0];
+        p->cxx = s[3] / s[0] - p->mx * p->mx;
+        p->cxy = s[4] / s[0] - p->mx * p->my;
+        p->cyy = s[5] / s[0] - p->my * p->my;
+        p->axx = p->cxx + min_variance;
+        p->axy = p->cxy;
+        p->ayy = p->cyy + min_variance;
+        p->det = p->axx * p->ayy - p->axy * p->axy;
+        if (!dm_isfinite(p->det) || !(p->det > 0.0)) {
+            p->lc = 0.0;
+            p->live = 0;
+            continue;
+        }
+        p->lc = dm_log(p->weight) - 0.5 * dm_log(p->det);
+        ++nlive;
+    }
+    return nlive;
+}
+
+/* E-step of one particle at (xp, yp) relative to the centre: r[k] the responsibilities (0 for a
+ * dead component); returns the particle's log-likelihood.  At least one component is live.   */
+DM_FN double dm_gmm_estep(const dm_gmm_comp* c, int K, double xp, double yp, double* r)
+{
+    double M = 0.0;
+    int any = 0;
+    DM_UNROLL
+    for (int k = 0; k < K; ++k) {
+        r[k] = 0.0;
+        if (!c[k].live) continue;
+        const double dx = xp - c[k].mx, dy = yp - c[k].my;
+        const double q = ((c[k].ayy * (dx * dx) - ((2.0 * c[k].axy) * dx) * dy) + c[k].axx * (dy * dy)) / c[k].det;
+        const double lp = (c[k].lc - 0.5 * q) - DM_LOG_2PI;
+        r[k] = lp;
+        M = (!any || lp > M) ? lp : M;
+        any = 1;
+    }
+    double s = 0.0;
+    DM_UNROLL
+    for (int k = 0; k < K; ++k) {
+        if (!c[k].live) continue;
+        r[k] = dm_exp(r[k] - M);
+        s = s + r[k];
+    }
+    DM_UNROLL
+    for (int k = 0; k < K; ++k)
+        if (c[k].live) r[k] = r[k] / s;
+    return M + dm_log(s);
+}
+
+/* one particle's terms added to the sums of component k (t = scaled weight x responsibility) */
+DM_FN void dm_gmm_add(double* s, double t, double xp, double yp)
+{
+    const double tx = t * xp, ty = t * yp;
+    s[0] = s[0] + t;
+    s[1] = s[1] + tx;
+    s[2] = s[2] + ty;
+    s[3] = s[3] + tx * xp;
+    s[4] = s[4] + tx * yp;
+    s[5] = s[5] + ty * yp;
+}
+
 #endif /* ESLAM_DETMATH_H */

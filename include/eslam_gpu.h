@@ -620,6 +620,56 @@ int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index);  /* :160
  * position[3] + quaternion (w,x,y,z)                                                        */
 int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double orientation[4]);
 
+/* ---- PoseDistribution::gmm (src/PoseParticle.hpp:88-114): a 2-D Gaussian mixture over (x, y) --
+ * Fitted by EM on the device over the particles as they stand (a deferred exchange is settled
+ * and a pending gather run first) and their current weights at any scale, normalised or not.
+ * envire's GaussianMixture / ExpectationMaximization are not in the reference tree: the rule is
+ * this build's own, all fp64 through eslam_detmath.h, every sum in getCentroid's
+ * order, so one GPU, a sharded filter and the CPU restatement give the same bits.  In short:
+ * particles with finite x, y, w and w > 0 are fitted (the others skipped and counted); weights
+ * are scaled by 2^-weight_exp and coordinates taken relative to the bounding box's centre; the
+ * particles start in `components` equal slabs along the box's longer axis (slab order is the
+ * order of `out`); then up to max_iterations fused E+M passes, stopping when the mean
+ * log-likelihood moves by at most `tolerance` between two passes (from the second pass on).
+ * A component that gathers no weight, or whose covariance + min_variance I is not positive
+ * definite, is dead: it takes no further part and reports weight 0, mean 0, covariance 0 (from
+ * the next M-step on).  The fit changes nothing in the filter: particles, weights (no in-place
+ * normalise, unlike eslam_gpu_get_centroid), RNG, maps and pose hash are as before.  Synchronous;
+ * needs particles, no map.
+ * ESLAM_ERR_INVALID_ARG (checked before any launch or collective): a null ctx, params or out;
+ * components 0 or > ESLAM_GMM_MAX_COMPONENTS; tolerance negative or NaN; min_variance not finite
+ * or <= 0.  ESLAM_ERR_NOT_INITIALISED: no particles.  A poisoned filter returns its fault.
+ * No fitted particle: ESLAM_OK, components_live 0, every output zero.
+ * Sharded filters: a collective in SPMD order.  The ranks first compare their parameters (one
+ * all_gather of host words; a mismatch is ESLAM_ERR_INVALID_ARG on every rank); every rank
+ * returns the one-GPU result bit for bit and takes the same stop decision.                  */
+#define ESLAM_GMM_MAX_COMPONENTS 8
+typedef struct eslam_gmm_params {
+    uint32_t components;       /* K, 1..ESLAM_GMM_MAX_COMPONENTS                               */
+    uint32_t max_iterations;   /* 0: the initial assignment's parameters, log_likelihood NaN   */
+    double tolerance;          /* on the mean log-likelihood of successive passes              */
+    double min_variance;       /* added to the covariances' diagonal in the E-step (m^2)       */
+} eslam_gmm_params;
+void eslam_gmm_params_default(eslam_gmm_params* p);   /* 3 components, 10 iterations, 1e-5, 1e-6 */
+typedef struct eslam_gmm_component {
+    double weight;
+    double mean[2];
+    double cov[3];             /* xx, xy, yy */
+} eslam_gmm_component;
+typedef struct eslam_gmm_info {
+    uint32_t components_live;  /* components that would take part in a further E-step          */
+    uint32_t iterations;       /* fused passes run                                             */
+    uint32_t converged;        /* the stop test passed                                         */
+    uint32_t live_mask;        /* bit k: component k (out[k]) is live; components_live bits set */
+    uint64_t particles_used, particles_skipped;
+    double log_likelihood;     /* weighted mean log-likelihood measured by the last pass, i.e. */
+                               /* of the parameters BEFORE the last M-step (NaN: no pass ran)  */
+    double centre[2];          /* the bounding box's centre the sums were taken around         */
+    int32_t weight_exp;        /* E with 2^(E-1) <= max w < 2^E                                */
+} eslam_gmm_info;
+int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* params, eslam_gmm_component* out /* params->components */,
+                           eslam_gmm_info* info /* may be NULL */);
+
 /* ---- resume state: RNG + the filter scalars (bit-exact resume with the particles) ------- */
 typedef struct eslam_rng_state {
     uint32_t minstd_x;                     /* ParticleFilter::rand_gen state                */

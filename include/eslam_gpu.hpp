@@ -461,9 +461,39 @@ struct PoseParticle {                     // src/PoseParticle.hpp:52-86
     double weight = 0;
 };
 
-struct PoseDistribution {                 // src/PoseParticle.hpp:88-114 (without the GMM)
+// The 2-D Gaussian mixture over the particles' (x, y) (PoseDistribution::GMM, src/PoseParticle.hpp:
+// 88-114: envire's GaussianMixture<double, 2>), read as the viewer reads it
+// (viz/ParticleVisualization.cpp:98-107): params[i].weight, params[i].dist.mean, params[i].dist.cov.
+// Fitted on the device by eslam_gpu_fit_pose_gmm (the rule is this build's own).
+struct Matrix2d {
+    double m[4] = {0, 0, 0, 0};           // row-major
+    double& operator()(int r, int c) { return m[r * 2 + c]; }
+    double operator()(int r, int c) const { return m[r * 2 + c]; }
+};
+struct Gaussian2D {
+    Vector2d mean;
+    Matrix2d cov;
+};
+struct GaussianMixture2D {
+    struct Parameter {
+        double weight = 0;
+        Gaussian2D dist;
+    };
+    std::vector<Parameter> params;        // the live components only, in slab order
+    // of the fit that filled it (eslam_gmm_info): log_likelihood is that of the parameters before
+    // the last M-step
+    eslam_gmm_info info = {};
+};
+struct GmmParams {                        // eslam_gmm_params_default
+    unsigned components = 3, maxIterations = 10;
+    double tolerance = 1e-5, minVariance = 1e-6;
+};
+
+struct PoseDistribution {                 // src/PoseParticle.hpp:88-114
+    typedef GaussianMixture2D GMM;
     double time = 0;
     std::vector<PoseParticle> particles;
+    GMM gmm;                              // empty unless asked for (getPoseDistribution(stride, GmmParams))
     Quaterniond orientation;
     BodyContactState bodyState;
 };
@@ -990,6 +1020,33 @@ public:
         check(ctx_, eslam_gpu_get_centroid(ctx_, p, q));
         return Pose(Vector3d(p[0], p[1], p[2]), Quaterniond(q[0], q[1], q[2], q[3]));
     }
+    // the pose with its uncertainty: the Gaussian mixture over (x, y) of the particles as they
+    // stand, fitted on the device (eslam_gpu_fit_pose_gmm); the filter is unchanged (no
+    // normalisation, unlike getCentroid).  Live components only.
+    GaussianMixture2D fitGmm(const GmmParams& gp = GmmParams()) const
+    {
+        flush();
+        eslam_gmm_params p;
+        p.components = gp.components;
+        p.max_iterations = gp.maxIterations;
+        p.tolerance = gp.tolerance;
+        p.min_variance = gp.minVariance;
+        eslam_gmm_component c[ESLAM_GMM_MAX_COMPONENTS] = {};
+        GaussianMixture2D g;
+        // components outside [1, 8] are refused before `c` is written
+        check(ctx_, eslam_gpu_fit_pose_gmm(ctx_, &p, c, &g.info));
+        for (unsigned k = 0; k < gp.components; ++k) {
+            if (!(g.info.live_mask >> k & 1u)) continue;      // the library's own liveness decision
+            GaussianMixture2D::Parameter q;
+            q.weight = c[k].weight;
+            q.dist.mean = Vector2d(c[k].mean[0], c[k].mean[1]);
+            q.dist.cov(0, 0) = c[k].cov[0];
+            q.dist.cov(0, 1) = q.dist.cov(1, 0) = c[k].cov[1];
+            q.dist.cov(1, 1) = c[k].cov[2];
+            g.params.push_back(q);
+        }
+        return g;
+    }
 
     // getParticles(): the particles as a vector the caller may edit, like the reference's
     // std::vector<Particle>& (src/ParticleFilter.hpp:150-153; processMap edits weights through
@@ -1478,6 +1535,14 @@ public:
         d.time = last_state_.time;
         return d;
     }
+    // ... with d.gmm fitted on the device over all particles, whatever the stride
+    PoseDistribution getPoseDistribution(size_t stride, const GmmParams& gp)
+    {
+        PoseDistribution d = getPoseDistribution(stride);
+        d.gmm = estimator().fitGmm(gp);
+        return d;
+    }
+    GaussianMixture2D fitGmm(const GmmParams& gp = GmmParams()) { return estimator().fitGmm(gp); }
 
     PoseEstimator& estimator()
     {

@@ -169,6 +169,7 @@ struct eslam_ctx {
     Dev<uint32_t> rhead;                     // received records: the record carrying each one's map
     uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
     Dev<double> cent;                        // getCentroid's chunk records (sharded: sized by set_comm)
+    Dev<double> gmm;                         // eslam_gpu_fit_pose_gmm's words, chunk records and exchange, grown on demand
     Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)
     bool cow_pending = false;
     // a sharded update's exchange left for the next call: the segments kernel's

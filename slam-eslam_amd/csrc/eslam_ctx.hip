@@ -2968,6 +2968,203 @@ extern "C" int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double
     return ESLAM_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// PoseDistribution::gmm: the 2-D Gaussian mixture over (x, y), fitted on the device
+// ---------------------------------------------------------------------------------------
+extern "C" void eslam_gmm_params_default(eslam_gmm_params* p)
+{
+    if (!p) return;
+    p->components = 3;
+    p->max_iterations = 10;
+    p->tolerance = 1e-5;
+    p->min_variance = 1e-6;
+}
+
+namespace {
+// the fit's arrays within ctx->gmm: pass B's words (sharded: then every rank's), this rank's chunk
+// records padded to the largest shard and all ranks' (sharded only), and the tree's two levels
+// over the global chunks
+struct GmmBufs {
+    uint64_t* words;
+    uint64_t* words_all;
+    uint64_t* part;                      // pass B: every wave's words
+    double* mine;
+    double* all;
+    double* a;
+    double* b;
+    uint64_t maxch = 1, total = 0;
+    std::vector<uint64_t> nch;
+};
+
+uint64_t gmm_carve(const eslam_ctx* ctx, uint32_t R, uint32_t J, void* base, GmmBufs* g)
+{
+    const int G = ctx->sharded ? ctx->comm.nranks : 1;
+    const uint64_t csz = 64ull * J;
+    g->nch.assign(G, 0);
+    g->maxch = 1;
+    g->total = 0;
+    for (int r = 0; r < G; ++r) {
+        const uint64_t n = ctx->sharded ? ctx->gall[r + 1] - ctx->gall[r] : ctx->n;
+        g->nch[r] = (n + csz - 1) / csz;
+        g->maxch = g->nch[r] > g->maxch ? g->nch[r] : g->maxch;
+        g->total += g->nch[r];
+    }
+    Carver c(base);
+    g->words = c.take<uint64_t>(kGmmWords);
+    g->words_all = c.take<uint64_t>((uint64_t)kGmmWords * G);
+    g->part = c.take<uint64_t>((uint64_t)kGmmBoundsBlocks * kWaves * kGmmWords);
+    g->mine = c.take<double>(ctx->sharded ? g->maxch * R : 0);
+    g->all = c.take<double>(ctx->sharded ? (uint64_t)G * g->maxch * R : 0);
+    g->a = c.take<double>((g->total ? g->total : 1) * R);
+    g->b = c.take<double>((g->total ? g->total : 1) * R);
+    return c.bytes();
+}
+
+// one pass: the chunk records of this context (sharded: of every rank, all-gathered into global
+// chunk order), then the one-GPU tree; rec = the pass' DM_GMM_REC(K) sums
+int gmm_pass(eslam_ctx* ctx, int K, bool hard, const GmmPass& P, uint32_t J, const GmmBufs& g, double* rec)
+{
+    const uint32_t R = DM_GMM_REC(K);
+    hipError_t e = hipSuccess;
+    if (!ctx->sharded) {
+        e = eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, g.a, ctx->stream);
+    } else {
+        e = hipMemsetAsync(g.mine, 0, g.maxch * R * sizeof(double), ctx->stream);
+        if (e == hipSuccess) e = eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, g.mine, ctx->stream);
+        if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
+        const int rc = comm_allgather(ctx, g.mine, g.all, g.maxch * R * sizeof(double));
+        if (rc) return rc;
+        uint64_t off = 0;
+        for (int r = 0; r < ctx->comm.nranks && e == hipSuccess; ++r) {
+            if (g.nch[r]) e = hipMemcpyAsync(g.a + off * R, g.all + (uint64_t)r * g.maxch * R, g.nch[r] * R * sizeof(double),
+                                             hipMemcpyDeviceToDevice, ctx->stream);
+            off += g.nch[r];
+        }
+    }
+    if (e == hipSuccess) e = eslam_launch_gmm_tree(g.a, g.b, g.total, R, ctx->scratch_host, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
+    memcpy(rec, ctx->scratch_host.get(), R * sizeof(double));
+    return ESLAM_OK;
+}
+}  // namespace
+
+extern "C" int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* params, eslam_gmm_component* out,
+                                      eslam_gmm_info* info)
+{
+    if (!ctx || !params || !out) return ESLAM_ERR_INVALID_ARG;
+    if (params->components < 1 || params->components > ESLAM_GMM_MAX_COMPONENTS)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: components must be in [1, 8]");
+    if (!(params->tolerance >= 0.0)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: tolerance must not be negative or NaN");
+    if (!dm_isfinite(params->min_variance) || !(params->min_variance > 0.0))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: min_variance must be finite and positive");
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
+    const int K = (int)params->components;
+    const uint32_t R = DM_GMM_REC(K);
+    static_assert(DM_GMM_MAX == ESLAM_GMM_MAX_COMPONENTS, "component limit");
+    static_assert((kMaxRanks + 1) * kGmmWords * 8 <= 4096 && DM_GMM_REC(DM_GMM_MAX) * 8 <= 4096, "scratch_host holds a readback");
+    if (ctx->sharded) {
+        // the ranks' parameters, compared before anything depends on them
+        uint64_t mine[3], all[3 * kMaxRanks];
+        mine[0] = (uint64_t)params->components | (uint64_t)params->max_iterations << 32;
+        mine[1] = dm_bits(params->tolerance);
+        mine[2] = dm_bits(params->min_variance);
+        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's words");
+        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
+        if (rc) return rc;
+        for (int r = 0; r < ctx->comm.nranks; ++r)
+            if (memcmp(&all[3 * r], mine, sizeof(mine)) != 0)
+                return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: the ranks' parameters differ");
+    }
+    int rc = materialize(ctx);                       // the particles as they stand
+    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
+    GmmBufs g;
+    if (!rc) rc = grow(ctx, ctx->gmm, gmm_carve(ctx, R, J, nullptr, &g));
+    // sharded: a rank whose gather or allocation failed must not leave the others in the passes'
+    // collectives (a failure inside a pass is a HIP or transport error no rank recovers from)
+    rc = agree(ctx, rc, "fit_pose_gmm");
+    if (rc) return rc;
+    gmm_carve(ctx, R, J, ctx->gmm.get(), &g);
+
+    // pass B: order-free words, reduced over the ranks identically everywhere
+    const int G = ctx->sharded ? ctx->comm.nranks : 1;
+    HIPCHK(ctx, eslam_launch_gmm_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, g.part, g.words, ctx->stream));
+    if (ctx->sharded) {
+        rc = comm_allgather(ctx, g.words, g.words_all, kGmmWords * sizeof(uint64_t));
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->sharded ? g.words_all : g.words, (uint64_t)G * kGmmWords * sizeof(uint64_t),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t B[kGmmWords] = {};
+    for (int r = 0; r < G; ++r) {
+        const uint64_t* w = ctx->scratch_host.as<const uint64_t>() + (uint64_t)r * kGmmWords;
+        for (int q = kGmmMaxW; q <= kGmmMaxY; ++q) B[q] = B[q] > w[q] ? B[q] : w[q];
+        B[kGmmUsed] += w[kGmmUsed];
+        B[kGmmSkipped] += w[kGmmSkipped];
+    }
+
+    const double nan_ = dm_from_bits(0x7ff8000000000000ull);
+    dm_gmm_comp comp[DM_GMM_MAX];
+    memset(comp, 0, sizeof(comp));
+    memset(out, 0, sizeof(eslam_gmm_component) * K);
+    eslam_gmm_info inf;
+    memset(&inf, 0, sizeof(inf));
+    inf.particles_used = B[kGmmUsed];
+    inf.particles_skipped = B[kGmmSkipped];
+    if (!B[kGmmUsed]) {                              // no fitted particle: everything zero
+        if (info) *info = inf;
+        return ESLAM_OK;
+    }
+    GmmPass P;
+    memset(&P, 0, sizeof(P));
+    const double xmin = gmm_unkey(~B[kGmmMinX]), xmax = gmm_unkey(B[kGmmMaxX]);
+    const double ymin = gmm_unkey(~B[kGmmMinY]), ymax = gmm_unkey(B[kGmmMaxY]);
+    P.E = dm_stat_exp(gmm_unkey(B[kGmmMaxW]));
+    P.cx = 0.5 * xmin + 0.5 * xmax;
+    P.cy = 0.5 * ymin + 0.5 * ymax;
+    P.axis = (xmax - xmin) >= (ymax - ymin) ? 0 : 1;
+    P.amin = P.axis ? ymin : xmin;
+    P.h = ((P.axis ? ymax : xmax) - P.amin) / (double)K;
+
+    // pass 0: the hard assignment; then the fused E+M passes
+    double rec[DM_GMM_REC(DM_GMM_MAX)];
+    rc = gmm_pass(ctx, K, true, P, J, g, rec);
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) comp[k].live = 1;
+    int nlive = dm_gmm_mstep(rec, K, params->min_variance, comp);
+    double L = nan_, Lprev = nan_;
+    for (uint32_t t = 1; t <= params->max_iterations && nlive > 0; ++t) {
+        memcpy(P.c, comp, sizeof(comp));
+        rc = gmm_pass(ctx, K, false, P, J, g, rec);
+        if (rc) return rc;
+        L = rec[6 * K + 1] / rec[6 * K];
+        nlive = dm_gmm_mstep(rec, K, params->min_variance, comp);
+        inf.iterations = t;
+        if (t >= 2 && dm_fabs(L - Lprev) <= params->tolerance) { inf.converged = 1; break; }
+        Lprev = L;
+    }
+    for (int k = 0; k < K; ++k) {
+        if (!comp[k].set) continue;
+        out[k].weight = comp[k].weight;
+        out[k].mean[0] = comp[k].mx + P.cx;
+        out[k].mean[1] = comp[k].my + P.cy;
+        out[k].cov[0] = comp[k].cxx;
+        out[k].cov[1] = comp[k].cxy;
+        out[k].cov[2] = comp[k].cyy;
+    }
+    inf.components_live = (uint32_t)nlive;
+    for (int k = 0; k < K; ++k) inf.live_mask |= comp[k].live ? 1u << k : 0u;
+    inf.log_likelihood = L;
+    inf.centre[0] = P.cx;
+    inf.centre[1] = P.cy;
+    inf.weight_exp = P.E;
+    if (info) *info = inf;
+    return ESLAM_OK;
+}
+
 extern "C" int eslam_gpu_get_rng_state(eslam_ctx* ctx, eslam_rng_state* st)
 {
     if (!ctx || !st) return ESLAM_ERR_INVALID_ARG;

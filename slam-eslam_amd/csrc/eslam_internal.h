@@ -610,5 +610,30 @@ __host__ __device__ inline void own_chunks(uint64_t O0, uint64_t O1, uint64_t W0
     *c_hi = ch < cl ? cl : ch;
 }
 
+// The pose distribution's Gaussian mixture (eslam_gmm.hip).
+// Pass B's words: integer maxima of ordered keys (a minimum as the maximum of ~key) and counts,
+// all zero before the kernel; the maxima mean something only when kGmmUsed is non-zero.
+constexpr int kGmmMaxW = 0, kGmmMinX = 1, kGmmMaxX = 2, kGmmMinY = 3, kGmmMaxY = 4, kGmmUsed = 5, kGmmSkipped = 6;
+constexpr int kGmmWords = 8;
+constexpr int kGmmBoundsBlocks = 1024;       // blocks of pass B at most (each wave leaves kGmmWords words)
+// finite doubles (-0.0 excluded) in unsigned integer order, and back
+__host__ __device__ inline uint64_t gmm_key(double v)
+{
+    const uint64_t b = dm_bits(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__host__ __device__ inline double gmm_unkey(uint64_t k)
+{
+    return dm_from_bits((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
+}
+// one pass' arguments: the centre, the weight scale 2^-E, the hard assignment's axis (0: x) and
+// slabs [amin + k h, ...), and the parameters of the E-step
+struct GmmPass {
+    double cx, cy;
+    double amin, h;
+    int32_t E, axis;
+    dm_gmm_comp c[DM_GMM_MAX];
+};
+
 
 }  // namespace eslam_dev

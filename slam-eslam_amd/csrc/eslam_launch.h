@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All nine .hip files include it, the defining one too: the
+// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All ten .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -71,6 +71,13 @@ hipError_t eslam_launch_centroid_chunks(DevState s0, DevState s1, uint64_t n, ui
 hipError_t eslam_launch_centroid_tree(double* a, double* b, uint64_t m, double* out, hipStream_t stream);
 hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* tmp, double* out,
                                  hipStream_t stream);
+
+// ---- eslam_gmm.hip (the pose distribution's Gaussian mixture: pass B, a pass' chunk records, the tree)
+hipError_t eslam_launch_gmm_bounds(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint64_t* part, uint64_t* out,
+                                   hipStream_t stream);
+hipError_t eslam_launch_gmm_pass(int K, int hard, DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, const GmmPass* P,
+                                 double* chunk_out, hipStream_t stream);
+hipError_t eslam_launch_gmm_tree(double* a, double* b, uint64_t m, uint32_t R, double* out, hipStream_t stream);
 
 // ---- eslam_resample.hip (resample to a count: the cumulative sum, the draws' searches, the gather)
 uint64_t eslam_resample_tiles(uint64_t items);

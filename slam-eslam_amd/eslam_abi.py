@@ -286,6 +286,46 @@ class ResampleInfo(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+GMM_MAX_COMPONENTS = 8
+
+
+class GmmParams(C.Structure):
+    """eslam_gmm_params (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("components", C.c_uint32),
+        ("max_iterations", C.c_uint32),
+        ("tolerance", C.c_double),
+        ("min_variance", C.c_double),
+    ]
+
+
+class GmmComponent(C.Structure):
+    """eslam_gmm_component: weight, mean (x, y), covariance (xx, xy, yy)."""
+    _fields_ = [
+        ("weight", C.c_double),
+        ("mean", C.c_double * 2),
+        ("cov", C.c_double * 3),
+    ]
+
+
+class GmmInfo(C.Structure):
+    """eslam_gmm_info (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("components_live", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("converged", C.c_uint32),
+        ("live_mask", C.c_uint32),
+        ("particles_used", C.c_uint64),
+        ("particles_skipped", C.c_uint64),
+        ("log_likelihood", C.c_double),
+        ("centre", C.c_double * 2),
+        ("weight_exp", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: (list(getattr(self, f)) if f == "centre" else getattr(self, f)) for f, _ in self._fields_}
+
+
 class RngState(C.Structure):
     _fields_ = [
         ("minstd_x", C.c_uint32),

@@ -108,6 +108,11 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_resample_multinomial.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
     L.eslam_gpu_get_best_particle_index.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.eslam_gpu_get_centroid.argtypes = [vp, dp, dp]
+    # a library without it is an error at the call
+    if hasattr(L, "eslam_gpu_fit_pose_gmm"):
+        L.eslam_gmm_params_default.argtypes = [C.POINTER(A.GmmParams)]
+        L.eslam_gmm_params_default.restype = None
+        L.eslam_gpu_fit_pose_gmm.argtypes = [vp, C.POINTER(A.GmmParams), C.POINTER(A.GmmComponent), C.POINTER(A.GmmInfo)]
     L.eslam_gpu_get_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_set_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_get_ancestors.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64]
@@ -448,6 +453,21 @@ class GpuFilter:
         q = (C.c_double * 4)()
         self._check(self.L.eslam_gpu_get_centroid(self.h, p, q))
         return list(p), list(q)
+
+    def fit_pose_gmm(self, components=3, max_iterations=10, tolerance=1e-5, min_variance=1e-6):
+        """eslam_gpu_fit_pose_gmm: the 2-D Gaussian mixture over the particles' (x, y) by EM on the
+        device; the filter is unchanged.  Returns (weights[K], means[K, 2],
+        covs[K, 3] as xx, xy, yy, GmmInfo) in slab order, dead components as zeros.  A collective
+        on a sharded filter."""
+        p = A.GmmParams(components, max_iterations, tolerance, min_variance)
+        out = (A.GmmComponent * max(int(components), 1))()
+        info = A.GmmInfo()
+        self._check(self.L.eslam_gpu_fit_pose_gmm(self.h, C.byref(p), out, C.byref(info)))
+        k = int(components)
+        weights = np.array([out[i].weight for i in range(k)], dtype=np.float64)
+        means = np.array([list(out[i].mean) for i in range(k)], dtype=np.float64).reshape(k, 2)
+        covs = np.array([list(out[i].cov) for i in range(k)], dtype=np.float64).reshape(k, 3)
+        return weights, means, covs, info
 
     def ancestors(self):
         n = self.count()
