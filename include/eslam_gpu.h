@@ -606,7 +606,8 @@ int eslam_gpu_resample(eslam_ctx* ctx);        /* resample() -> resample_stratif
  * advanced; within it a copy names its ancestor's table and shares its pages until a map update
  * writes them.  A sharded filter accepts only a stratified call with samples == n_global (the
  * sharded eslam_gpu_resample); anything else is ESLAM_ERR_UNSUPPORTED on every rank, before any
- * collective.  info may be NULL.                                                            */
+ * collective.  The collective forms that take a sharded filter to any count are
+ * eslam_gpu_resample_stratified_sharded / _multinomial_sharded below.  info may be NULL.    */
 typedef struct {
     uint64_t n_before;   /* particles before the call                                  */
     uint64_t n_after;    /* particles after it                                         */
@@ -615,6 +616,41 @@ typedef struct {
 } eslam_resample_info;
 int eslam_gpu_resample_stratified(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
 int eslam_gpu_resample_multinomial(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
+/* The same two calls on a sharded filter (eslam_gpu_set_comm), to any count.  Collective: every
+ * rank calls in the same order with the same `samples`.  Afterwards the ranks' shards, in rank
+ * order, are bit for bit the particle set one context holding the same global particles has after
+ * eslam_gpu_resample_stratified / _multinomial(samples): every field, the weights (carried, or
+ * 1.0 / (double)n_before with n_before the old global count), the ancestors (old global
+ * indices), the minstd state (moved on by `samples` draws on every rank) and info (global
+ * n_before, n_after, overruns, dropped, the same on every rank).
+ * The new layout: the filter is sharded by eslam_gpu_shard_bounds(n_after, nranks,
+ * cfg.sum_chunk_rows), as though eslam_gpu_set_comm had been called with that table before the
+ * particles were set: the local count, n_global, the rank's first index and every buffer sized
+ * by the table follow it, and so do the summation chunk rows.  A rank whose new shard exceeds its
+ * capacity allocates the larger particle set before anything changes.  Every later call works
+ * at the new count.  A deferred exchange of the previous update is settled first.
+ * Refused on every rank alike, before any collective, with nothing changed:
+ *   ESLAM_ERR_INVALID_ARG   samples == 0 or samples > 2^30 - 64 (eslam_gpu_set_comm's limit);
+ *                           stratified: a count eslam_gpu_shard_bounds cannot split over the ranks
+ *   ESLAM_ERR_UNSUPPORTED   ESLAM_FLAG_PARTICLE_MAPS (the tables and pages would have to travel)
+ * A multinomial call learns n_after from its draws; every rank counts the same dropped draws.
+ * n_after == 0 or a count that cannot be split is ESLAM_ERR_INVALID_ARG on every rank with
+ * nothing changed, the minstd state included (it is committed only with the new particle set;
+ * the one-GPU call moves it first).  A rank that cannot allocate tells the others in the call's
+ * small all_gathers before any rank changes anything: it returns its own code, the others
+ * ESLAM_ERR_COMM, the filter is as it was on all of them.
+ * On a context that is not sharded these are the plain calls.  A stratified call at n_global on
+ * the canonical table is the sharded eslam_gpu_resample.                                    */
+int eslam_gpu_resample_stratified_sharded(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
+int eslam_gpu_resample_multinomial_sharded(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info);
+/* The canonical shard table of an n_global-particle filter over nranks ranks: near-equal shards
+ * whose starts are multiples of the summation chunk (64 x the chunk rows of n_global;
+ * sum_chunk_rows: eslam_config::sum_chunk_rows, 0 for the default).  bounds_out takes nranks + 1
+ * entries, from 0 to n_global.  ESLAM_ERR_INVALID_ARG when n_global has fewer chunks than there
+ * are ranks (a shard would be empty).  Pure host code: no context, no GPU.                   */
+int eslam_gpu_shard_bounds(uint64_t n_global, int32_t nranks, uint32_t sum_chunk_rows, uint64_t* bounds_out);
+/* the context's current table (nranks + 1 entries; capacity: the entries bounds_out has room for) */
+int eslam_gpu_get_shard_bounds(eslam_ctx* ctx, uint64_t* bounds_out, uint32_t capacity);
 int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index);  /* :160-173 (Q16)  */
 /* PoseEstimator::getCentroid src/PoseEstimator.cpp:354-383 (normalises in place, Q15):
  * position[3] + quaternion (w,x,y,z)                                                        */

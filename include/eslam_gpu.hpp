@@ -990,18 +990,27 @@ public:
     // resample_stratified(samples) / resample_multinomial(samples)  src/ParticleFilter.hpp:85-148:
     // to any count; getParticles() has the new size afterwards (eslam_gpu_resample_stratified /
     // _multinomial: the limits with per-particle maps and sharded filters, and samples == 0, are
-    // errors there and exceptions here)
+    // errors there and exceptions here).  On a sharded estimator these are the collectives
+    // eslam_gpu_resample_stratified_sharded / _multinomial_sharded: every rank calls with the
+    // same count, the filter is laid out by the canonical table of the new count afterwards
+    // (shardBounds()), and getParticles() has the rank's new local size.
     void resample_stratified(size_t samples)
     {
         flush();
         invalidate();
-        check(ctx_, eslam_gpu_resample_stratified(ctx_, samples, &last_resample_));
+        if (sharded())
+            check(ctx_, eslam_gpu_resample_stratified_sharded(ctx_, samples, &last_resample_));
+        else
+            check(ctx_, eslam_gpu_resample_stratified(ctx_, samples, &last_resample_));
     }
     void resample_multinomial(size_t samples)
     {
         flush();
         invalidate();
-        check(ctx_, eslam_gpu_resample_multinomial(ctx_, samples, &last_resample_));
+        if (sharded())
+            check(ctx_, eslam_gpu_resample_multinomial_sharded(ctx_, samples, &last_resample_));
+        else
+            check(ctx_, eslam_gpu_resample_multinomial(ctx_, samples, &last_resample_));
     }
     const eslam_resample_info& lastResample() const { return last_resample_; }
     size_t getBestParticleIndex() const
@@ -1166,6 +1175,24 @@ public:
     }
     bool sharded() const { return sharded_; }
     int rank() const { return rank_; }
+    // the sharded estimator's current shard table: the first global index of every rank + the
+    // global count (eslam_gpu_get_shard_bounds); a resample to another count changes it
+    std::vector<uint64_t> shardBounds() const
+    {
+        uint64_t b[17] = {};
+        check(ctx_, eslam_gpu_get_shard_bounds(ctx_, b, 17));
+        size_t ranks = 1;
+        while (ranks < 16 && b[ranks + 1] > b[ranks]) ++ranks;
+        return std::vector<uint64_t>(b, b + ranks + 1);
+    }
+    // the canonical table of an nGlobal-particle filter over nranks ranks (eslam_gpu_shard_bounds)
+    static std::vector<uint64_t> canonicalShardBounds(uint64_t nGlobal, int nranks, uint32_t sumChunkRows = 0)
+    {
+        std::vector<uint64_t> b((size_t)(nranks > 0 ? nranks : 0) + 1);
+        if (eslam_gpu_shard_bounds(nGlobal, nranks, sumChunkRows, b.data()) != ESLAM_OK)
+            throw std::runtime_error("eslam_gpu_shard_bounds: the count cannot be split over the ranks");
+        return b;
+    }
 
     // the device's snapshot as one file written and read by offset (eslam_gpu_save_at /
     // eslam_gpu_load_at): on a sharded estimator collectives, every rank writing and reading its

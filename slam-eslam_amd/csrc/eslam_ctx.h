@@ -280,6 +280,9 @@ int host_allgather(eslam_ctx* ctx, const void* send, void* recv, uint64_t bytes)
 // ESLAM_ERR_COMM with "<what>: rank R failed (C)".
 int agree(eslam_ctx* ctx, int rc, const char* what);
 uint64_t centroid_bytes(const uint64_t* gall, int G, uint32_t J);
+// a shard table's buffers (may fail; nothing else changes), and the table itself (eslam_host_comm.hip)
+int reserve_shard_table(eslam_ctx* ctx, int nranks, uint64_t n_global, const uint64_t* shard_gbase);
+int apply_shard_table(eslam_ctx* ctx, int nranks, int rank, uint64_t n_global, const uint64_t* shard_gbase);
 void rccl_release(eslam_ctx* ctx);
 
 }  // namespace eslam_host

@@ -2871,6 +2871,197 @@ extern "C" int eslam_gpu_resample_multinomial(eslam_ctx* ctx, uint64_t samples, 
     return resample_to(ctx, samples, true, info);
 }
 
+// The same on a sharded filter, to any count (DESIGN.md 5 "Resample to a count, sharded";
+// eslam_resample.hip k_rss_*).  Collective.  The exchanges: the statistics all_gather of the
+// exact global sum; one all_gather of the ranks' 8-byte fixed-point totals; one of the records
+// every rank sends to every rank (G words); one all_to_all_v of the records.  The two small
+// all_gathers carry the ranks' status too (~0 for a rank that could not allocate), so a
+// rank-local failure ends the call on every rank before anything has changed.  Nothing of the
+// filter changes before the commit at the end: the minstd state included.
+static int resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
+{
+    if (!ctx) {
+        if (info) memset(info, 0, sizeof(*info));
+        return ESLAM_ERR_INVALID_ARG;
+    }
+    if (!ctx->sharded) return resample_to(ctx, samples, multi, info);
+    if (info) memset(info, 0, sizeof(*info));
+    // every refusal the arguments, the flags and the table decide: before any collective (settle is one)
+    if (samples == 0 || samples > (1ull << 30) - 64)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample_sharded: samples must be in [1, 2^30 - 64]");
+    if (particle_maps(ctx))
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "resample_sharded: per-particle maps do not travel with a count-changing resample");
+    const int G = ctx->comm.nranks, me = ctx->comm.rank;
+    uint64_t nb[kMaxRanks + 1] = {};
+    if (!multi && eslam_gpu_shard_bounds(samples, G, ctx->cfg.sum_chunk_rows, nb) != ESLAM_OK)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample_sharded: samples cannot be split into nranks chunk-aligned shards");
+    if (const int rc_ = settle(ctx)) return rc_;
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (check_poisoned(ctx)) return ESLAM_ERR_HIP;
+    // the current count on the canonical table: the sharded resample itself
+    if (!multi && samples == ctx->n_global && std::equal(nb, nb + G + 1, ctx->gall.begin()))
+        return resample_to(ctx, samples, false, info);
+    const uint64_t n = ctx->n, n_before = ctx->n_global;
+    // the exact global sum (the statistics all_gather + FIN_SUM); runs a pending gather first
+    int rc = standalone(ctx, FIN_SUM);
+    if (rc) return rc;
+    // this rank's C and total.  A rank without memory for them gathers ~0: every rank stops
+    const uint64_t tn = eslam_resample_tiles(n), ts = eslam_resample_tiles(samples);
+    ResampleShardScratch rs;
+    Carver size(nullptr);
+    carve_resample_sharded(size, n, tn, ts, multi, &rs);
+    hipError_t he = hipSuccess;
+    int mine = ctx->rs_mem.grow_keep(size.bytes(), 1, ctx->stream, &he);
+    if (mine == ESLAM_ERR_HIP) return fail(ctx, mine, hipGetErrorString(he));
+    uint64_t* h = ctx->mg_host;
+    if (!mine) {
+        Carver place(ctx->rs_mem.get());
+        carve_resample_sharded(place, n, tn, ts, multi, &rs);
+        HIPCHK(ctx, eslam_launch_rss_cumsum(ctx->st[0], ctx->st[1], n, ctx->ctl, rs.coarse, rs.C, rs.counter, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->mg + mg::kTotal, rs.coarse + (tn - 1), 8, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        h[mg::kTotal] = ~0ull;
+        HIPCHK(ctx, hipMemcpyAsync(ctx->mg + mg::kTotal, &h[mg::kTotal], 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = comm_allgather(ctx, ctx->mg + mg::kTotal, ctx->mg + mg::kTotals, 8);
+    if (rc) return rc;
+    uint64_t tot[kMaxRanks];
+    HIPCHK(ctx, hipMemcpyAsync(tot, ctx->mg + mg::kTotals, 8ull * G, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    auto peer_failed = [&](const uint64_t* words, uint64_t stride) -> int {
+        for (int r = 0; r < G; ++r)
+            if (words[(uint64_t)r * stride] == ~0ull) return r;
+        return -1;
+    };
+    if (mine) return fail(ctx, mine, "resample_sharded: no device memory for the cumulative sum");
+    if (const int r = peer_failed(tot, 1); r >= 0)
+        return fail(ctx, ESLAM_ERR_COMM, ("resample_sharded: rank " + std::to_string(r) + " failed (no device memory)").c_str());
+    RsPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    for (int r = 0; r < G; ++r) {
+        if (r < me) pl.off += tot[r];
+        pl.gtotal += tot[r];
+    }
+    pl.total = tot[me];
+    pl.n = n;
+    pl.ntiles = tn;
+    pl.samples = samples;
+    pl.inv_samples = 1.0 / (double)samples;
+    pl.gbase = ctx->gbase;
+    pl.G = G;
+    pl.me = me;
+    pl.set_weight = multi ? 1u : 0u;
+    pl.weight = 1.0 / (double)n_before;
+    // multinomial: the dropped draws fix n_after and the table; every rank counts the same
+    uint64_t beyond = 0, n_after = samples;
+    if (multi) {
+        HIPCHK(ctx, eslam_launch_rss_census(&pl, ctx->ctl, ctx->jump, rs.kept, rs.counter, ctx->stream));
+        HIPCHK(ctx, eslam_launch_scan_excl(rs.kept, ts + 1, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(&beyond, rs.counter + kRsBeyond, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        n_after = samples - beyond;
+        if (n_after == 0 || eslam_gpu_shard_bounds(n_after, G, ctx->cfg.sum_chunk_rows, nb) != ESLAM_OK)
+            return fail(ctx, ESLAM_ERR_INVALID_ARG,
+                        "resample_sharded: the kept draws cannot be split into nranks chunk-aligned shards (nothing changed)");
+    }
+    for (int d = 0; d <= G; ++d) pl.nb[d] = nb[d];
+    // the records this rank sends to every rank
+    const DevState none = {};
+    HIPCHK(ctx, eslam_launch_rss_route(multi ? 1 : 0, 0, &pl, ctx->st[0], ctx->st[1], none, ctx->ctl, ctx->jump, rs.coarse, rs.C,
+                                       rs.kept, nullptr, nullptr, rs.counter, ctx->stream));
+    uint64_t cnt[kMaxRanks] = {}, nrecv = 0;
+    HIPCHK(ctx, hipMemcpyAsync(cnt, rs.counter + kRsCount, 8ull * G, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(&nrecv, rs.counter + kRsRecv, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (!multi) HIPCHK(ctx, hipMemcpyAsync(&beyond, rs.counter + kRsBeyond, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t nsend = 0;
+    for (int d = 0; d < G; ++d) {
+        pl.send_off[d] = nsend;
+        nsend += cnt[d];
+    }
+    pl.send_off[G] = nsend;
+    // everything the call still allocates, before the counts are exchanged: the larger particle
+    // set, the records' buffers (every rank evaluates every draw, so it has counted the records
+    // it will receive itself), the new table's buffers
+    const uint64_t n_new = nb[me + 1] - nb[me];
+    const bool growing = n_new > ctx->cap;
+    ParticleSet ps;
+    const uint64_t R = eslam_record_bytes();
+    if (growing && alloc_particle_set(ctx, n_new, ps) != hipSuccess) {
+        (void)hipGetLastError();
+        ps = ParticleSet{};
+        mine = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "resample_sharded: no device memory for the larger particle set");
+    }
+    if (growing && !mine) HIPCHK(ctx, hipDeviceSynchronize());     // the new buffers' resets, before the stream uses them
+    if (!mine && (mine = ctx->sendbuf.grow_keep((nsend ? nsend : 1) * R, 1, ctx->stream, &he)) != ESLAM_OK)
+        fail(ctx, mine, "resample_sharded: no device memory for the records to send");
+    if (!mine && (mine = ctx->recvbuf.grow_keep((nrecv ? nrecv : 1) * R, 1, ctx->stream, &he)) != ESLAM_OK)
+        fail(ctx, mine, "resample_sharded: no device memory for the records to receive");
+    if (!mine) mine = reserve_shard_table(ctx, G, n_after, nb);
+    const std::string msg = ctx->err;
+    for (int d = 0; d < G; ++d) h[mg::kCounts + d] = mine ? ~0ull : cnt[d];
+    HIPCHK(ctx, hipMemcpyAsync(ctx->mg + mg::kCounts, &h[mg::kCounts], 8ull * G, hipMemcpyHostToDevice, ctx->stream));
+    rc = comm_allgather(ctx, ctx->mg + mg::kCounts, ctx->mg + mg::kCountsAll, 8ull * G);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(&h[mg::kCountsAll], ctx->mg + mg::kCountsAll, 8ull * G * G, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (mine) return fail(ctx, mine, msg.c_str());
+    if (const int r = peer_failed(&h[mg::kCountsAll], (uint64_t)G); r >= 0)
+        return fail(ctx, ESLAM_ERR_COMM, ("resample_sharded: rank " + std::to_string(r) + " failed (no device memory)").c_str());
+    uint64_t sb[kMaxRanks], rb[kMaxRanks], told = 0;
+    for (int r = 0; r < G; ++r) {
+        const uint64_t c = h[mg::kCountsAll + r * G + me];
+        sb[r] = cnt[r] * R;
+        rb[r] = c * R;
+        told += c;
+    }
+    if (told != nrecv) return fail(ctx, ESLAM_ERR_COMM, "resample_sharded: the ranks' record counts disagree");
+    rc = read_ctl(ctx);
+    if (rc) return rc;
+    Ctl* c = ctx->ctl_host;
+    const uint32_t base = c->base ^ c->flip;
+    const DevState out = growing ? ps.st[0] : ctx->st[base ^ 1u];
+    const bool record = keep_ancestors(ctx);
+    uint32_t* anc_out = record ? (growing ? ps.pt.anc.get() : ctx->pt.anc.get()) : nullptr;
+    ctx->dbg_valid = false;                      // the records no longer follow the particles
+    HIPCHK(ctx, eslam_launch_rss_route(multi ? 1 : 0, 1, &pl, ctx->st[0], ctx->st[1], out, ctx->ctl, ctx->jump, rs.coarse, rs.C,
+                                       rs.kept, ctx->sendbuf, anc_out, rs.counter, ctx->stream));
+    rc = comm_alltoallv(ctx, ctx->sendbuf, sb, ctx->recvbuf, rb);
+    if (rc) return rc;
+    HIPCHK(ctx, eslam_launch_rss_expand(ctx->recvbuf, nrecv, out, n_new, anc_out, ctx->stream));
+    // K3's tile words carry the tag of the launch that wrote them (resample_to)
+    if (!growing)
+        HIPCHK(ctx, hipMemsetAsync(ctx->pt.tile_sum, 0, ((uint64_t)kPubReplicas * ctx->pub_stride + 16) * 8, ctx->stream));
+    c->base = growing ? 0u : base ^ 1u;
+    c->flip = 0;
+    c->gather = 0;
+    c->minstd = dm_mulmod31(dm_minstd_pow(samples), c->minstd);    // moved on by exactly `samples` draws
+    rc = write_ctl(ctx);                         // waits for the expand: the old set may go
+    if (rc) return rc;
+    if (growing) adopt_particle_set(ctx, ps, n_new);
+    rc = apply_shard_table(ctx, G, me, n_after, nb);                // reserved above: cannot fail
+    if (rc) return rc;
+    ctx->n = n_new;
+    ctx->has_anc = record;
+    if (info) {
+        info->n_before = n_before;
+        info->n_after = n_after;
+        if (multi) info->dropped = beyond;
+        else info->overruns = beyond;
+    }
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_resample_stratified_sharded(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)
+{
+    return resample_sharded(ctx, samples, false, info);
+}
+
+extern "C" int eslam_gpu_resample_multinomial_sharded(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)
+{
+    return resample_sharded(ctx, samples, true, info);
+}
+
 extern "C" int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index)
 {
     if (!ctx || !index) return ESLAM_ERR_INVALID_ARG;

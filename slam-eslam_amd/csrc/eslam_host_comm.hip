@@ -108,6 +108,32 @@ uint64_t eslam_host::centroid_bytes(const uint64_t* gall, int G, uint32_t J)
     return (maxch + (uint64_t)G * maxch + 2 * (total ? total : 1)) * 5 * sizeof(double);
 }
 
+// A shard table takes effect in two parts, shared by eslam_gpu_set_comm and the resample of a
+// sharded filter to another count.  reserve: everything sized by the table that may fail
+// (getCentroid's buffer, allocated here so the per-step getCentroid of a Rock task allocates
+// nothing), with the context's table still the old one.  apply: reserve, then the table itself:
+// gall, n_global and gbase; the cached A^n_global follows n_global (fin_params).  Neither
+// touches the particles.
+int eslam_host::reserve_shard_table(eslam_ctx* ctx, int nranks, uint64_t n_global, const uint64_t* shard_gbase)
+{
+    const uint64_t need = centroid_bytes(shard_gbase, nranks, dm_chunk_rows_cfg(n_global, ctx->cfg.sum_chunk_rows));
+    if (need <= ctx->cent.cap()) return ESLAM_OK;
+    hipError_t he = hipSuccess;
+    const int rc = ctx->cent.grow_keep(need, 1, ctx->stream, &he);
+    if (rc == ESLAM_ERR_HIP) return fail(ctx, rc, hipGetErrorString(he));
+    if (rc) return fail(ctx, rc, "no device memory for getCentroid's chunk records");
+    return ESLAM_OK;
+}
+
+int eslam_host::apply_shard_table(eslam_ctx* ctx, int nranks, int rank, uint64_t n_global, const uint64_t* shard_gbase)
+{
+    if (const int rc = reserve_shard_table(ctx, nranks, n_global, shard_gbase)) return rc;
+    ctx->gall.assign(shard_gbase, shard_gbase + nranks + 1);
+    ctx->n_global = n_global;
+    ctx->gbase = shard_gbase[rank];
+    return ESLAM_OK;
+}
+
 extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64_t n_global, const uint64_t* shard_gbase)
 {
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
@@ -146,12 +172,7 @@ extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64
     }
     // host_allgather's buffer: its own words and every rank's, so no collective allocates
     if (!ctx->hostx) HIPCHK(ctx, ctx->hostx.alloc(kHostXBytes * (kMaxRanks + 1)));
-    {
-        // getCentroid's buffer (centroid_bytes): sized by the shard table, allocated here so
-        // the per-step getCentroid of a Rock task allocates nothing
-        const uint64_t need = centroid_bytes(shard_gbase, comm->nranks, dm_chunk_rows_cfg(n_global, ctx->cfg.sum_chunk_rows));
-        if (need > ctx->cent.cap()) HIPCHK(ctx, ctx->cent.alloc(need));
-    }
+    if (const int rc_ = reserve_shard_table(ctx, comm->nranks, n_global, shard_gbase)) return rc_;
     if ((ctx->cfg.flags & ESLAM_FLAG_PROCESS_STATICS) && comm->nranks > 1) {
         if (g_statics_sharded.fetch_add(1) != 0) {
             g_statics_sharded.fetch_sub(1);
@@ -163,9 +184,31 @@ extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64
     }
     ctx->comm = *comm;
     ctx->sharded = true;
-    ctx->gall.assign(shard_gbase, shard_gbase + comm->nranks + 1);
-    ctx->n_global = n_global;
-    ctx->gbase = shard_gbase[comm->rank];
+    return apply_shard_table(ctx, comm->nranks, comm->rank, n_global, shard_gbase);
+}
+
+// the canonical table: near-equal shards whose starts are multiples of the summation chunk
+extern "C" int eslam_gpu_shard_bounds(uint64_t n_global, int32_t nranks, uint32_t sum_chunk_rows, uint64_t* bounds_out)
+{
+    if (!bounds_out || nranks < 1 || n_global == 0) return ESLAM_ERR_INVALID_ARG;
+    const uint64_t csz = 64ull * dm_chunk_rows_cfg(n_global, sum_chunk_rows);
+    const uint64_t chunks = (n_global + csz - 1) / csz, G = (uint64_t)nranks;
+    if (chunks < G) return ESLAM_ERR_INVALID_ARG;      // fewer chunks than ranks: some shard would be empty
+    for (uint64_t r = 0; r < G; ++r) {
+        const uint64_t b = (chunks * r / G) * csz;
+        bounds_out[r] = b < n_global ? b : n_global;
+    }
+    bounds_out[G] = n_global;
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_get_shard_bounds(eslam_ctx* ctx, uint64_t* bounds_out, uint32_t capacity)
+{
+    if (!ctx || !bounds_out) return ESLAM_ERR_INVALID_ARG;
+    if (!ctx->sharded) return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_get_shard_bounds: the context is not sharded");
+    if (capacity < ctx->gall.size())
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "eslam_gpu_get_shard_bounds: room for nranks + 1 entries is needed");
+    memcpy(bounds_out, ctx->gall.data(), ctx->gall.size() * sizeof(uint64_t));
     return ESLAM_OK;
 }
 

@@ -266,6 +266,29 @@ struct alignas(8) Rec {
 };
 static_assert(sizeof(Rec) == 72, "record size");
 
+// A resample to a count on a sharded filter (eslam_resample.hip, DESIGN.md 5 "Resample to a
+// count, sharded"): what every draw's routing needs.  This rank owns the thresholds in
+// (off, off + total] (rank 0 also T = 0) of the global fixed-point sum gtotal; the new shard table
+// nb[] names the rank of every output; the records for rank d start at send_off[d].  A migrating
+// particle travels as a Rec whose lohi is its output's index within the destination's new shard
+// and whose src is flags | old global index << 8.
+struct RsPlan {
+    uint64_t off, total, gtotal;
+    uint64_t n, ntiles;                  // this rank's particles and their tiles of C
+    uint64_t samples;
+    double inv_samples;
+    uint64_t gbase;                      // this rank's first particle in the old global indexing
+    uint64_t nb[kMaxRanks + 1];          // the new table
+    uint64_t send_off[kMaxRanks + 1];    // records: first of every destination (+ their count)
+    int32_t G, me;
+    uint32_t set_weight, pad;            // multinomial: every output's weight is `weight`
+    double weight;
+};
+// the call's counters (uint64 words): draws beyond the sum, records per destination, fill cursors,
+// records this rank will receive (its outputs whose ancestors other ranks hold)
+constexpr int kRsBeyond = 0, kRsCount = 1, kRsCursor = kRsCount + kMaxRanks, kRsRecv = kRsCursor + kMaxRanks,
+              kRsWords = kRsRecv + 1;
+
 // multi-GPU mark encoding (monotone in output order): records from lower ranks,
 // then this rank's own particles, then records from higher ranks
 constexpr uint32_t kMarkOwn = 1u << 30, kMarkHigh = 1u << 31;

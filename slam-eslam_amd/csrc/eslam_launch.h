@@ -89,6 +89,16 @@ hipError_t eslam_launch_rs_draw(int multinomial, uint64_t n, uint64_t samples, c
 hipError_t eslam_launch_rs_compact(uint64_t samples, const uint32_t* anc, const uint32_t* offs, uint32_t* out, hipStream_t stream);
 hipError_t eslam_launch_rs_gather(DevState s0, DevState s1, const Ctl* ctl, DevState out, uint64_t m, const uint32_t* anc,
                                   int set_weight, double weight, uint32_t* anc_out, hipStream_t stream);
+// ... on a sharded filter: C over the rank's shard, the draws routed by the all-gathered totals
+hipError_t eslam_launch_rss_cumsum(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint64_t* coarse, uint64_t* C,
+                                   uint64_t* counter, hipStream_t stream);
+hipError_t eslam_launch_rss_census(const RsPlan* pl, const Ctl* ctl, const uint32_t* jt, uint32_t* kept, uint64_t* counter,
+                                   hipStream_t stream);
+hipError_t eslam_launch_rss_route(int multinomial, int fill, const RsPlan* pl, DevState s0, DevState s1, DevState out,
+                                  const Ctl* ctl, const uint32_t* jt, const uint64_t* coarse, const uint64_t* C,
+                                  const uint32_t* offs, void* send, uint32_t* anc_out, uint64_t* counter, hipStream_t stream);
+hipError_t eslam_launch_rss_expand(const void* recv, uint64_t nrecv, DevState out, uint64_t n_out, uint32_t* anc_out,
+                                   hipStream_t stream);
 
 // ---- eslam_hash.hip
 hipError_t eslam_launch_hash_sweep(const dm_hash_grid* g, const double* pts, const double* orient, uint32_t steps, int32_t* out,

@@ -48,6 +48,21 @@ inline void carve_resample(Carver& c, uint64_t n, uint64_t tn, uint64_t samples,
     s->kept = c.take<uint32_t>(ts + 1);
 }
 
+// the same on a sharded filter, per rank: C and its coarse level over the rank's own n particles,
+// the call's counters (kRsWords), and, for the multinomial draw only, the kept draws of every
+// tile of global draws (far below one 32-bit word per global draw); no word per draw otherwise
+struct ResampleShardScratch {
+    uint64_t *C, *coarse, *counter;
+    uint32_t* kept;
+};
+inline void carve_resample_sharded(Carver& c, uint64_t n, uint64_t tn, uint64_t ts, bool multi, ResampleShardScratch* s)
+{
+    s->C = c.take<uint64_t>(n);
+    s->coarse = c.take<uint64_t>(tn);
+    s->counter = c.take<uint64_t>(eslam_dev::kRsWords);
+    s->kept = multi ? c.take<uint32_t>(ts + 1) : nullptr;
+}
+
 // a snapshot's census over `ntables` pool tables, `cap` particles and `npages` pool pages
 // (SnapCensus::counts is a buffer of its own)
 inline void carve_census(Carver& c, uint64_t ntables, uint64_t cap, uint64_t npages, eslam_dev::SnapCensus* s)

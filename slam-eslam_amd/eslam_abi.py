@@ -449,6 +449,24 @@ def shard_bounds(n_global, nranks, fixed=0):
     return g
 
 
+SHARD_BOUNDS_ARGTYPES = [C.c_uint64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+
+
+def shard_bounds_c(lib, n_global, nranks, fixed=0):
+    """eslam_gpu_shard_bounds of a loaded library: shard_bounds in C (what a resample of a sharded
+    filter to another count lays the filter out by).  ValueError where shard_bounds raises."""
+    if nranks < 1:
+        raise ValueError("nranks must be at least 1")
+    fn = lib.eslam_gpu_shard_bounds
+    fn.argtypes = SHARD_BOUNDS_ARGTYPES
+    fn.restype = C.c_int
+    out = (C.c_uint64 * (nranks + 1))()
+    rc = fn(n_global, nranks, fixed, out)
+    if rc != 0:
+        raise ValueError(f"{n_global} particles cannot be split into {nranks} chunk-aligned shards ({rc})")
+    return [int(v) for v in out]
+
+
 def default_config(lib=None):
     """eslam_config_default() restated (src/Configuration.hpp:85-111 defaults)."""
     import math

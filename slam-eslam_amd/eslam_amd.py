@@ -106,6 +106,12 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_resample.argtypes = [vp]
     L.eslam_gpu_resample_stratified.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
     L.eslam_gpu_resample_multinomial.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
+    # a library without them is an error at the call
+    if hasattr(L, "eslam_gpu_resample_stratified_sharded"):
+        L.eslam_gpu_resample_stratified_sharded.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
+        L.eslam_gpu_resample_multinomial_sharded.argtypes = [vp, C.c_uint64, C.POINTER(A.ResampleInfo)]
+        L.eslam_gpu_shard_bounds.argtypes = A.SHARD_BOUNDS_ARGTYPES
+        L.eslam_gpu_get_shard_bounds.argtypes = [vp, C.POINTER(C.c_uint64), C.c_uint32]
     L.eslam_gpu_get_best_particle_index.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.eslam_gpu_get_centroid.argtypes = [vp, dp, dp]
     # a library without it is an error at the call
@@ -442,6 +448,29 @@ class GpuFilter:
         info = A.ResampleInfo()
         self._check(self.L.eslam_gpu_resample_multinomial(self.h, samples, C.byref(info)))
         return info
+
+    def resample_stratified_sharded(self, samples):
+        """eslam_gpu_resample_stratified_sharded: resample_stratified(samples) on a sharded filter,
+        to any count.  A collective: every rank passes the same samples.  Afterwards the filter is
+        sharded by shard_bounds_c(n_after, nranks) (get_shard_bounds).  On a filter that is not
+        sharded it is resample_stratified.  Returns the ResampleInfo (global counts)."""
+        info = A.ResampleInfo()
+        self._check(self.L.eslam_gpu_resample_stratified_sharded(self.h, samples, C.byref(info)))
+        return info
+
+    def resample_multinomial_sharded(self, samples):
+        """eslam_gpu_resample_multinomial_sharded: resample_multinomial(samples) on a sharded
+        filter (see resample_stratified_sharded); n_after is samples less the dropped draws."""
+        info = A.ResampleInfo()
+        self._check(self.L.eslam_gpu_resample_multinomial_sharded(self.h, samples, C.byref(info)))
+        return info
+
+    def get_shard_bounds(self):
+        """eslam_gpu_get_shard_bounds: the sharded filter's current table, nranks + 1 entries"""
+        out = (C.c_uint64 * (A.MAX_RANKS + 1))()
+        self._check(self.L.eslam_gpu_get_shard_bounds(self.h, out, A.MAX_RANKS + 1))
+        b = [int(v) for v in out]
+        return b[:b.index(max(b)) + 1]
 
     def best_index(self):
         i = C.c_uint64()

@@ -113,6 +113,17 @@ class TorchComm:
             return 1
 
 
+def _resample_sharded(sf, call, samples):
+    """the collective resample of a sharded filter wrapper, then its attributes from the new table"""
+    rank = sf.bounds.index(sf.gbase)
+    info = call(samples)
+    sf.bounds = sf.f.get_shard_bounds()
+    sf.n_global = sf.bounds[-1]
+    sf.gbase = sf.bounds[rank]
+    sf.n_local = sf.bounds[rank + 1] - sf.gbase
+    return info
+
+
 class ShardedGpuFilter:
     """The GPU filter of one rank of an n_global-particle filter sharded over the group."""
 
@@ -136,6 +147,17 @@ class ShardedGpuFilter:
 
     def __getattr__(self, name):
         return getattr(self.f, name)
+
+    def resample_stratified_sharded(self, samples):
+        """resample_stratified(samples) on the sharded filter, to any count (a collective);
+        bounds, n_global, gbase and n_local follow the new table.  Returns the ResampleInfo.
+        (resample_stratified / resample_multinomial stay the context's plain calls, which refuse
+        a sharded filter every count but its own.)"""
+        return _resample_sharded(self, self.f.resample_stratified_sharded, samples)
+
+    def resample_multinomial_sharded(self, samples):
+        """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
+        return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
 
     def close(self):
         """Collective: every rank completes the exchange it may still owe, then frees its context."""
@@ -173,6 +195,17 @@ class RcclShardedGpuFilter:
 
     def __getattr__(self, name):
         return getattr(self.f, name)
+
+    def resample_stratified_sharded(self, samples):
+        """resample_stratified(samples) on the sharded filter, to any count (a collective);
+        bounds, n_global, gbase and n_local follow the new table.  Returns the ResampleInfo.
+        (resample_stratified / resample_multinomial stay the context's plain calls, which refuse
+        a sharded filter every count but its own.)"""
+        return _resample_sharded(self, self.f.resample_stratified_sharded, samples)
+
+    def resample_multinomial_sharded(self, samples):
+        """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
+        return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
 
     def close(self):
         """Collective: every rank completes the exchange it may still owe, then frees its context."""
