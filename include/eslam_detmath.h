@@ -2294,4 +2294,61 @@ DM_FN void dm_gmm_add(double* s, double t, double xp, double yp)
     s[5] = s[5] + ty * yp;
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* KLD-sampling: the pose lattice over (x, y, yaw) and the sample bound    */
+/* ------------------------------------------------------------------------------------ */
+#define DM_INV_2PI 1.59154943091895345608e-01   /* 0x3fc45f306dc9c883: RN(1 / (2 pi)) */
+
+/* The lattice indices of a particle: cells of 1 / inv metres anchored at the world origin and
+ * theta_bins yaw bins per turn.  Returns 0 (skipped) unless x, y, theta and w are finite,
+ * w > 0 and both cell indices fit an int32.                                                */
+DM_FN int dm_kld_index(double x, double y, double theta, double w, double inv, uint32_t theta_bins, int32_t* ix, int32_t* iy,
+                       uint32_t* it)
+{
+    if (!dm_isfinite(x) || !dm_isfinite(y) || !dm_isfinite(theta) || !dm_isfinite(w) || !(w > 0.0)) return 0;
+    const double fx = dm_floor(x * inv), fy = dm_floor(y * inv);
+    if (!(fx >= -2147483648.0 && fx <= 2147483647.0 && fy >= -2147483648.0 && fy <= 2147483647.0)) return 0;
+    double u = theta * DM_INV_2PI;
+    u -= dm_floor(u);
+    uint32_t t = (uint32_t)dm_floor(u * (double)theta_bins);
+    if (t == theta_bins) t = 0;                 /* u rounded to 1.0 */
+    *ix = (int32_t)fx;
+    *iy = (int32_t)fy;
+    *it = t;
+    return 1;
+}
+
+/* Fox's bound on the sample count for k occupied bins (Wilson-Hilferty), in this order */
+DM_FN double dm_kld_bound(uint64_t k, double epsilon, double z_quantile)
+{
+    if (k <= 1) return 0.0;
+    const double km1 = (double)(k - 1);
+    const double a = 2.0 / (9.0 * km1);
+    const double t = (1.0 - a) + dm_sqrt(a) * z_quantile;
+    return (km1 / (2.0 * epsilon)) * t * t * t;
+}
+
+/* The target count of a bound: its ceiling, raised to n_min (bit 0 of *clamped), cut to `limit`
+ * (bit 1; a non-finite bound or one at or above 2^63 counts as above any limit), cut to
+ * `capacity` when that is non-zero (bit 2), held at n_global when it differs from it by at most
+ * min_change x n_global (bit 3).                                                           */
+DM_FN uint64_t dm_kld_samples(double bound, uint64_t n_min, uint64_t limit, uint64_t capacity, uint64_t n_global,
+                              double min_change, uint32_t* clamped)
+{
+    uint32_t c = 0;
+    uint64_t s;
+    if (!dm_isfinite(bound) || !(bound < 9223372036854775808.0)) s = ~0ull;
+    else {
+        const double f = dm_floor(bound);
+        s = bound > 0.0 ? (uint64_t)f + (f < bound ? 1u : 0u) : 0;
+    }
+    if (s < n_min) { s = n_min; c |= 1u; }
+    if (s > limit) { s = limit; c |= 2u; }
+    if (capacity && s > capacity) { s = capacity; c |= 4u; }
+    const uint64_t d = s > n_global ? s - n_global : n_global - s;
+    if ((double)d <= min_change * (double)n_global) { s = n_global; c |= 8u; }
+    *clamped = c;
+    return s;
+}
+
 #endif /* ESLAM_DETMATH_H */

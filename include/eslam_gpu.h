@@ -706,6 +706,78 @@ typedef struct eslam_gmm_info {
 int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* params, eslam_gmm_component* out /* params->components */,
                            eslam_gmm_info* info /* may be NULL */);
 
+/* ---- KLD-sampling (Fox 2003): the particle count the posterior needs --------------------------
+ * The reference takes `samples` from its caller (src/ParticleFilter.hpp); the rule is this
+ * build's own.  A fixed lattice over (x, y, yaw) is anchored at the world origin;
+ * the occupied bins k of the particles as they stand (a deferred exchange is settled and a
+ * pending gather run first) are counted on the device, exactly, and the smallest count whose
+ * Kullback-Leibler distance to the posterior stays below epsilon with probability 1 - delta is
+ * computed on the host.  Everything is fp64 without contraction through eslam_detmath.h
+ * (dm_kld_index, dm_kld_bound, dm_kld_samples), so one GPU, a sharded filter and the CPU
+ * restatement (tests/c/kld_ref.c) give the same info bit for bit.
+ *   counted   x, y, theta and w finite, w > 0, and both cell indices fit an int32; every other
+ *             particle is skipped (particles_skipped)
+ *   lattice   inv = 1.0 / bin_xy; ix = (int32) floor(x * inv), iy likewise; u = theta *
+ *             DM_INV_2PI, u -= floor(u), it = (uint32) floor(u * theta_bins), it == theta_bins
+ *             (u rounded to 1.0) wraps to 0
+ *   box       origin = the minima of ix and iy over the counted particles (sharded: global),
+ *             bins = {nx, ny, theta_bins} with nx = ix1 - ix0 + 1; a particle's bit is
+ *             ((iy - iy0) * nx + (ix - ix0)) * theta_bins + it of a bitmap of nx * ny * theta_bins
+ *             bits.  More bits than max_bins (0: 2^27 bits, 16 MiB): ESLAM_ERR_UNSUPPORTED ("cloud
+ *             too spread for the bin size"), info filled as far as the box, nothing changed
+ *   k         bins_occupied, the bitmap's population count
+ *   bound     k <= 1: 0.  Else a = 2.0 / (9.0 * (k - 1)), t = (1.0 - a) + sqrt(a) * z_quantile,
+ *             bound = ((k - 1) / (2.0 * epsilon)) * t * t * t
+ *   samples   ceil(bound), then in this order, each step that applies setting its bit in clamped:
+ *             bit 0 raised to n_min; bit 1 cut to n_max (0: none) and to the largest count the
+ *             resample accepts (2^32 - 2; sharded 2^30 - 64) -- a non-finite bound or one at or
+ *             above 2^63 counts as above both; bit 2 cut to the capacity on a filter with
+ *             ESLAM_FLAG_PARTICLE_MAPS; bit 3 held at the current global count n when
+ *             |samples - n| <= min_change * n (in fp64)
+ * No counted particle: ESLAM_OK, k 0, origin 0, bins {0, 0, theta_bins}, samples from bound 0.
+ * eslam_gpu_kld_count changes nothing in the filter (particles, weights, RNG, maps, hash);
+ * synchronous; needs particles, no map.
+ * eslam_gpu_resample_kld counts, then resamples to info.samples: eslam_gpu_resample_stratified /
+ * _multinomial (params->multinomial), on a sharded filter the _sharded calls.  Whatever that
+ * resample refuses comes back with its own code and nothing changed (a sharded count with fewer
+ * summation chunks than ranks, no memory to grow).  A stratified call at an unchanged count is
+ * eslam_gpu_resample.  A sharded filter with ESLAM_FLAG_PARTICLE_MAPS cannot change its count,
+ * and the count is known only after the collectives: the call is ESLAM_ERR_UNSUPPORTED before
+ * any collective unless n_min == n_max == the current global count.  Both infos may be NULL.
+ * ESLAM_ERR_INVALID_ARG (before any launch or collective): a null ctx, params or (kld_count)
+ * info; bin_xy not finite or <= 0; theta_bins outside 1..4096; multinomial > 1; epsilon not
+ * finite or <= 0; z_quantile not finite or < 0; n_min 0; n_max non-zero and below n_min;
+ * min_change negative or NaN.  ESLAM_ERR_NOT_INITIALISED: no particles.
+ * Sharded filters: both calls are collectives in SPMD order.  The ranks compare their parameters
+ * (one all_gather of host words: a mismatch is ESLAM_ERR_INVALID_ARG on every rank), all-gather
+ * the six words of box and counts, agree that every rank has the bitmap's memory, all-gather
+ * the bitmaps and OR them.  Every rank gets the one-GPU info bit for bit.                   */
+typedef struct eslam_kld_params {
+    double bin_xy;        /* metres, finite, > 0                                   */
+    uint32_t theta_bins;  /* yaw bins per turn, 1..4096                            */
+    uint32_t multinomial; /* 0 stratified, 1 multinomial (eslam_gpu_resample_kld)  */
+    double epsilon;       /* KL bound, finite, > 0                                 */
+    double z_quantile;    /* upper 1 - delta quantile of N(0,1), finite, >= 0      */
+    uint64_t n_min;       /* >= 1                                                  */
+    uint64_t n_max;       /* 0 = only the call's own limits; else >= n_min         */
+    double min_change;    /* hysteresis, fraction of the current count, >= 0       */
+    uint64_t max_bins;    /* bitmap bits; 0 = 2^27                                 */
+} eslam_kld_params;
+/* 0.1 m, 36 bins, stratified, epsilon 0.05, z 2.3263478740408408 (delta 0.01),
+ * n_min = cfg->particle_count (1 when that is 0 or cfg is NULL), n_max 0, min_change 0, max_bins 0 */
+void eslam_kld_params_default(const eslam_config* cfg, eslam_kld_params* p);
+typedef struct eslam_kld_info {
+    uint64_t particles_counted, particles_skipped, bins_occupied;
+    int64_t origin[2];    /* ix0, iy0 */
+    uint64_t bins[3];     /* nx, ny, theta_bins */
+    double bound;
+    uint64_t samples;
+    uint32_t clamped, pad;
+} eslam_kld_info;
+int eslam_gpu_kld_count(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info);
+int eslam_gpu_resample_kld(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info /* may be NULL */,
+                           eslam_resample_info* rinfo /* may be NULL */);
+
 /* ---- resume state: RNG + the filter scalars (bit-exact resume with the particles) ------- */
 typedef struct eslam_rng_state {
     uint32_t minstd_x;                     /* ParticleFilter::rand_gen state                */

@@ -489,6 +489,18 @@ struct GmmParams {                        // eslam_gmm_params_default
     double tolerance = 1e-5, minVariance = 1e-6;
 };
 
+// KLD-sampling's parameters (eslam_kld_params_default).  nMin 0: the configured
+// particle count.
+struct KldParams {
+    double binXY = 0.1;                   // metres
+    unsigned thetaBins = 36;              // yaw bins per turn
+    bool multinomial = false;             // resampleKld: resample_multinomial instead of _stratified
+    double epsilon = 0.05, zQuantile = 2.3263478740408408;      // the KL bound; delta = 0.01
+    uint64_t nMin = 0, nMax = 0;          // nMax 0: only the call's own limits
+    double minChange = 0;                 // hysteresis, a fraction of the current count
+    uint64_t maxBins = 0;                 // bitmap bits; 0 = 2^27
+};
+
 struct PoseDistribution {                 // src/PoseParticle.hpp:88-114
     typedef GaussianMixture2D GMM;
     double time = 0;
@@ -1013,6 +1025,29 @@ public:
             check(ctx_, eslam_gpu_resample_multinomial(ctx_, samples, &last_resample_));
     }
     const eslam_resample_info& lastResample() const { return last_resample_; }
+    // KLD-sampling (eslam_gpu_kld_count): the occupied bins of the pose lattice over
+    // the particles as they stand, counted on the device, and the count they ask for
+    // (info.samples).  The filter is unchanged.  A collective on a sharded estimator.
+    eslam_kld_info kldCount(const KldParams& kp = KldParams()) const
+    {
+        flush();
+        const eslam_kld_params p = kldParams(kp);
+        eslam_kld_info info = {};
+        check(ctx_, eslam_gpu_kld_count(ctx_, &p, &info));
+        return info;
+    }
+    // ... then the resample to that count (eslam_gpu_resample_kld): stratified, or multinomial
+    // with kp.multinomial; getParticles() has the new size afterwards and, on a sharded estimator,
+    // shardBounds() the new table.  lastKld() and lastResample() give the two infos; lastKld() is
+    // filled as far as the call got when it throws.
+    void resampleKld(const KldParams& kp = KldParams())
+    {
+        flush();
+        invalidate();
+        const eslam_kld_params p = kldParams(kp);
+        check(ctx_, eslam_gpu_resample_kld(ctx_, &p, &last_kld_, &last_resample_));
+    }
+    const eslam_kld_info& lastKld() const { return last_kld_; }
     size_t getBestParticleIndex() const
     {
         flush();
@@ -1131,6 +1166,22 @@ public:
     }
 
 private:
+    eslam_kld_params kldParams(const KldParams& kp) const
+    {
+        eslam_kld_params p;
+        const eslam_config c = config_.toC();
+        eslam_kld_params_default(&c, &p);             // n_min: the configured particle count
+        p.bin_xy = kp.binXY;
+        p.theta_bins = kp.thetaBins;
+        p.multinomial = kp.multinomial ? 1u : 0u;
+        p.epsilon = kp.epsilon;
+        p.z_quantile = kp.zQuantile;
+        if (kp.nMin) p.n_min = kp.nMin;
+        p.n_max = kp.nMax;
+        p.min_change = kp.minChange;
+        p.max_bins = kp.maxBins;
+        return p;
+    }
     void replaceSet(const std::vector<Particle>& in) const
     {
         const size_t n = in.size();
@@ -1310,6 +1361,7 @@ private:
     eslam_ctx* ctx_ = nullptr;
     eslam_update_info last_ = {};
     eslam_resample_info last_resample_ = {};
+    eslam_kld_info last_kld_ = {};
     mutable std::vector<Particle> view_;           // getParticles()
     mutable std::vector<Hot> shadow_;              // view_ as the device holds it
     mutable bool view_valid_ = false;
@@ -1570,6 +1622,9 @@ public:
         return d;
     }
     GaussianMixture2D fitGmm(const GmmParams& gp = GmmParams()) { return estimator().fitGmm(gp); }
+    // KLD-sampling: the particle count the posterior asks for, and the resample to it
+    eslam_kld_info kldCount(const KldParams& kp = KldParams()) { return estimator().kldCount(kp); }
+    void resampleKld(const KldParams& kp = KldParams()) { estimator().resampleKld(kp); }
 
     PoseEstimator& estimator()
     {

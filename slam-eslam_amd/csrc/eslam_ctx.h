@@ -170,6 +170,8 @@ struct eslam_ctx {
     uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
     Dev<double> cent;                        // getCentroid's chunk records (sharded: sized by set_comm)
     Dev<double> gmm;                         // eslam_gpu_fit_pose_gmm's words, chunk records and exchange, grown on demand
+    Dev<char> kld;                           // eslam_gpu_kld_count's scratch (KldScratch: records, bitmap, the ranks'
+                                             //   bitmaps), kept between calls
     Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)
     bool cow_pending = false;
     // a sharded update's exchange left for the next call: the segments kernel's

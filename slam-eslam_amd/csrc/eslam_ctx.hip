@@ -3356,6 +3356,201 @@ extern "C" int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* pa
     return ESLAM_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// KLD-sampling: the occupied bins of the pose lattice, counted on the device, and the particle
+// count they ask for
+// ---------------------------------------------------------------------------------------
+extern "C" void eslam_kld_params_default(const eslam_config* cfg, eslam_kld_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->bin_xy = 0.1;
+    p->theta_bins = 36;
+    p->epsilon = 0.05;
+    p->z_quantile = 2.3263478740408408;
+    p->n_min = cfg && cfg->particle_count ? cfg->particle_count : 1;
+}
+
+namespace {
+// what is wrong with the parameters, or null
+const char* kld_refusal(const eslam_kld_params* p)
+{
+    if (!dm_isfinite(p->bin_xy) || !(p->bin_xy > 0.0)) return "kld: bin_xy must be finite and positive";
+    if (p->theta_bins < 1 || p->theta_bins > 4096) return "kld: theta_bins must be in [1, 4096]";
+    if (p->multinomial > 1) return "kld: multinomial must be 0 or 1";
+    if (!dm_isfinite(p->epsilon) || !(p->epsilon > 0.0)) return "kld: epsilon must be finite and positive";
+    if (!dm_isfinite(p->z_quantile) || !(p->z_quantile >= 0.0)) return "kld: z_quantile must be finite and not negative";
+    if (p->n_min == 0) return "kld: n_min must be at least 1";
+    if (p->n_max != 0 && p->n_max < p->n_min) return "kld: n_max must be 0 or at least n_min";
+    if (!(p->min_change >= 0.0)) return "kld: min_change must not be negative or NaN";
+    return nullptr;
+}
+
+uint64_t kld_mix(uint64_t a, uint64_t b)
+{
+    uint64_t h = (a ^ (a >> 31)) * 0x9e3779b97f4a7c15ull;
+    h = ((h ^ (h >> 29)) + b) * 0xbf58476d1ce4e5b9ull;
+    return h ^ (h >> 32);
+}
+
+// min / max / sum of record b into a
+void kld_fold(int64_t* a, const int64_t* b)
+{
+    a[kKldIx0] = a[kKldIx0] < b[kKldIx0] ? a[kKldIx0] : b[kKldIx0];
+    a[kKldIx1] = a[kKldIx1] > b[kKldIx1] ? a[kKldIx1] : b[kKldIx1];
+    a[kKldIy0] = a[kKldIy0] < b[kKldIy0] ? a[kKldIy0] : b[kKldIy0];
+    a[kKldIy1] = a[kKldIy1] > b[kKldIy1] ? a[kKldIy1] : b[kKldIy1];
+    a[kKldCounted] += b[kKldCounted];
+    a[kKldSkipped] += b[kKldSkipped];
+}
+
+// ctx->kld of at least the layout's bytes (the new block exists before the old one goes)
+int kld_reserve(eslam_ctx* ctx, uint64_t words, uint64_t gather)
+{
+    KldScratch ks;
+    Carver size(nullptr);
+    carve_kld(size, words, gather, &ks);
+    hipError_t he = hipSuccess;
+    const int rc = ctx->kld.grow_keep(size.bytes(), 1, ctx->stream, &he);
+    if (rc == ESLAM_ERR_HIP) return fail(ctx, rc, hipGetErrorString(he));
+    if (rc) return fail(ctx, rc, "kld_count: no device memory for the bitmap");
+    return ESLAM_OK;
+}
+
+// the count itself; params checked, info zeroed
+int kld_count(eslam_ctx* ctx, const eslam_kld_params* p, eslam_kld_info* info)
+{
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
+    const int G = ctx->sharded ? ctx->comm.nranks : 1;
+    static_assert(kKldWords * 8 <= kHostXBytes, "host_allgather's words");
+    if (ctx->sharded) {
+        // the ranks' parameters, compared before anything depends on them.  Six words: what shapes
+        // the collectives that follow (the lattice, the bitmap's limit) and epsilon as they are,
+        // the other four values as two 64-bit mixes
+        uint64_t mine[kKldWords], all[kKldWords * kMaxRanks];
+        mine[0] = dm_bits(p->bin_xy);
+        mine[1] = (uint64_t)p->theta_bins | (uint64_t)p->multinomial << 32;
+        mine[2] = p->max_bins;
+        mine[3] = dm_bits(p->epsilon);
+        mine[4] = kld_mix(dm_bits(p->z_quantile), p->n_min);
+        mine[5] = kld_mix(p->n_max, dm_bits(p->min_change));
+        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
+        if (rc) return rc;
+        for (int r = 0; r < G; ++r)
+            if (memcmp(&all[kKldWords * r], mine, sizeof(mine)) != 0)
+                return fail(ctx, ESLAM_ERR_INVALID_ARG, "kld_count: the ranks' parameters differ");
+    }
+    const double inv = 1.0 / p->bin_xy;
+    // pass 1 over the particles as they stand.  A rank whose gather or allocation failed says so
+    // in the sign of its count, so no rank is left in a collective
+    int rc = materialize(ctx);
+    if (!rc) rc = kld_reserve(ctx, 0, 0);
+    int64_t rec[kKldWords] = {2147483647ll, -2147483648ll, 2147483647ll, -2147483648ll, 0, 0};
+    KldScratch ks;
+    if (!rc) {
+        Carver place(ctx->kld.get());
+        carve_kld(place, 0, 0, &ks);
+        HIPCHK(ctx, eslam_launch_kld_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, inv, p->theta_bins, ks.part, ks.out, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ks.out, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(rec, ctx->scratch_host.get(), sizeof(rec));
+    }
+    if (ctx->sharded) {
+        const std::string msg = ctx->err;
+        int64_t all[kKldWords * kMaxRanks];
+        if (rc) rec[kKldCounted] = -1;
+        const int crc = host_allgather(ctx, rec, all, sizeof(rec));
+        if (rc) return fail(ctx, rc, msg.c_str());
+        if (crc) return crc;
+        int64_t tot[kKldWords] = {2147483647ll, -2147483648ll, 2147483647ll, -2147483648ll, 0, 0};
+        for (int r = 0; r < G; ++r) {
+            if (all[kKldWords * r + kKldCounted] < 0)
+                return fail(ctx, ESLAM_ERR_COMM, ("kld_count: rank " + std::to_string(r) + " failed").c_str());
+            kld_fold(tot, &all[kKldWords * r]);
+        }
+        memcpy(rec, tot, sizeof(rec));
+    } else if (rc) {
+        return rc;
+    }
+    info->particles_counted = (uint64_t)rec[kKldCounted];
+    info->particles_skipped = (uint64_t)rec[kKldSkipped];
+    info->bins[2] = p->theta_bins;
+    uint64_t k = 0;
+    if (rec[kKldCounted]) {
+        const uint64_t nx = (uint64_t)(rec[kKldIx1] - rec[kKldIx0] + 1), ny = (uint64_t)(rec[kKldIy1] - rec[kKldIy0] + 1);
+        info->origin[0] = rec[kKldIx0];
+        info->origin[1] = rec[kKldIy0];
+        info->bins[0] = nx;
+        info->bins[1] = ny;
+        uint64_t cells = 0, total = 0;
+        const bool wide = __builtin_mul_overflow(nx, ny, &cells) || __builtin_mul_overflow(cells, (uint64_t)p->theta_bins, &total);
+        if (wide || total > (p->max_bins ? p->max_bins : 1ull << 27))
+            return fail(ctx, ESLAM_ERR_UNSUPPORTED, "kld_count: cloud too spread for the bin size (the box's bins exceed max_bins)");
+        const uint64_t words = (total + 63) / 64;
+        rc = agree(ctx, kld_reserve(ctx, words, ctx->sharded ? (uint64_t)G : 0), "kld_count");
+        if (rc) return rc;
+        Carver place(ctx->kld.get());
+        carve_kld(place, words, ctx->sharded ? (uint64_t)G : 0, &ks);
+        KldGrid g;
+        memset(&g, 0, sizeof(g));
+        g.inv = inv;
+        g.theta_bins = p->theta_bins;
+        g.ix0 = rec[kKldIx0];
+        g.iy0 = rec[kKldIy0];
+        g.nx = nx;
+        HIPCHK(ctx, eslam_launch_kld_mark(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, &g, ks.bits, words, ctx->stream));
+        if (ctx->sharded) {
+            rc = comm_allgather(ctx, ks.bits, ks.all, words * sizeof(uint64_t));
+            if (rc) return rc;
+            HIPCHK(ctx, eslam_launch_kld_or(ks.all, (uint32_t)G, words, ks.bits, ctx->stream));
+        }
+        HIPCHK(ctx, eslam_launch_kld_popcount(ks.bits, words, ks.part, ks.out, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ks.out, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        k = (uint64_t)ctx->scratch_host.as<const int64_t>()[kKldCounted];
+    }
+    info->bins_occupied = k;
+    info->bound = dm_kld_bound(k, p->epsilon, p->z_quantile);
+    // the largest count the resample that follows accepts (resample_to, resample_sharded)
+    uint64_t limit = ctx->sharded ? (1ull << 30) - 64 : (1ull << 32) - 2;
+    if (p->n_max && p->n_max < limit) limit = p->n_max;
+    const uint64_t capacity = !particle_maps(ctx) ? 0 : ctx->sharded ? ctx->n_global : ctx->cap;
+    info->samples = dm_kld_samples(info->bound, p->n_min, limit, capacity, ctx->n_global, p->min_change, &info->clamped);
+    return ESLAM_OK;
+}
+}  // namespace
+
+extern "C" int eslam_gpu_kld_count(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (!ctx || !params || !info) return ESLAM_ERR_INVALID_ARG;
+    if (const char* why = kld_refusal(params)) return fail(ctx, ESLAM_ERR_INVALID_ARG, why);
+    return kld_count(ctx, params, info);
+}
+
+extern "C" int eslam_gpu_resample_kld(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info, eslam_resample_info* rinfo)
+{
+    if (info) memset(info, 0, sizeof(*info));
+    if (rinfo) memset(rinfo, 0, sizeof(*rinfo));
+    if (!ctx || !params) return ESLAM_ERR_INVALID_ARG;
+    if (const char* why = kld_refusal(params)) return fail(ctx, ESLAM_ERR_INVALID_ARG, why);
+    // the maps of a sharded filter do not travel, and whether the count changes is known only
+    // after the count's collectives: refused before any, unless the parameters fix the count
+    const bool pinned = ctx->sharded && particle_maps(ctx);
+    if (pinned && !(params->n_min == ctx->n_global && params->n_max == ctx->n_global))
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
+                    "resample_kld: a sharded filter with per-particle maps keeps its count (n_min == n_max == the global count)");
+    eslam_kld_info inf;
+    memset(&inf, 0, sizeof(inf));
+    const int rc = kld_count(ctx, params, &inf);
+    if (info) *info = inf;
+    if (rc) return rc;
+    const bool multi = params->multinomial != 0;
+    return ctx->sharded && !pinned ? resample_sharded(ctx, inf.samples, multi, rinfo) : resample_to(ctx, inf.samples, multi, rinfo);
+}
+
 extern "C" int eslam_gpu_get_rng_state(eslam_ctx* ctx, eslam_rng_state* st)
 {
     if (!ctx || !st) return ESLAM_ERR_INVALID_ARG;

@@ -658,5 +658,24 @@ struct GmmPass {
     dm_gmm_comp c[DM_GMM_MAX];
 };
 
+// KLD-sampling's bin count (eslam_kld.hip).  A record of pass 1: the minima and
+// maxima of the counted particles' cell indices (INT32_MAX / INT32_MIN where nothing was counted)
+// and the counts of counted and skipped particles; the population count's record uses kKldCounted
+constexpr int kKldIx0 = 0, kKldIx1 = 1, kKldIy0 = 2, kKldIy1 = 3, kKldCounted = 4, kKldSkipped = 5;
+constexpr int kKldWords = 6;
+constexpr int kKldBlocks = 1024;             // blocks of a pass at most (each leaves one record)
+// the lattice and the box a marking pass sets bits in
+struct KldGrid {
+    double inv;                          // 1.0 / bin_xy
+    uint32_t theta_bins, pad;
+    int64_t ix0, iy0;                    // the box's origin
+    uint64_t nx;                         // cells of a row of the box
+};
+struct KldScratch {
+    int64_t* out;                        // kKldWords: a pass' folded record
+    int64_t* part;                       // kKldBlocks records
+    uint64_t* bits;                      // the bitmap's words
+    uint64_t* all;                       // sharded: every rank's bitmap
+};
 
 }  // namespace eslam_dev

@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All ten .hip files include it, the defining one too: the
+// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All eleven .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -78,6 +78,14 @@ hipError_t eslam_launch_gmm_bounds(DevState s0, DevState s1, uint64_t n, Ctl* ct
 hipError_t eslam_launch_gmm_pass(int K, int hard, DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, const GmmPass* P,
                                  double* chunk_out, hipStream_t stream);
 hipError_t eslam_launch_gmm_tree(double* a, double* b, uint64_t m, uint32_t R, double* out, hipStream_t stream);
+
+// ---- eslam_kld.hip (KLD-sampling's bin count: the box, the marked bitmap, its population count)
+hipError_t eslam_launch_kld_bounds(DevState s0, DevState s1, uint64_t n, const Ctl* ctl, double inv, uint32_t theta_bins,
+                                   int64_t* part, int64_t* out, hipStream_t stream);
+hipError_t eslam_launch_kld_mark(DevState s0, DevState s1, uint64_t n, const Ctl* ctl, const KldGrid* g, uint64_t* bits,
+                                 uint64_t words, hipStream_t stream);
+hipError_t eslam_launch_kld_or(const uint64_t* all, uint32_t G, uint64_t words, uint64_t* bits, hipStream_t stream);
+hipError_t eslam_launch_kld_popcount(const uint64_t* bits, uint64_t words, int64_t* part, int64_t* out, hipStream_t stream);
 
 // ---- eslam_resample.hip (resample to a count: the cumulative sum, the draws' searches, the gather)
 uint64_t eslam_resample_tiles(uint64_t items);

@@ -93,6 +93,16 @@ inline void carve_scan(Carver& c, uint64_t n, size_t sort_bytes, eslam_dev::Scan
     s->sort_tmp_bytes = sort_bytes;
 }
 
+// a KLD bin count over a bitmap of `words` 64-bit words: a pass' folded record, the blocks'
+// records, the bitmap and, on a filter sharded over `gather` ranks (0: not sharded), theirs
+inline void carve_kld(Carver& c, uint64_t words, uint64_t gather, eslam_dev::KldScratch* s)
+{
+    s->out = c.take<int64_t>(eslam_dev::kKldWords);
+    s->part = c.take<int64_t>((uint64_t)eslam_dev::kKldBlocks * eslam_dev::kKldWords);
+    s->bits = c.take<uint64_t>(words);
+    s->all = c.take<uint64_t>(gather * words);
+}
+
 // a particle-grid composition on tx x ty tiles with `blocks` blocks of cells
 inline void carve_pgrid(Carver& c, uint64_t tx, uint64_t ty, uint64_t blocks, eslam_dev::PgScratch* s)
 {

@@ -326,6 +326,50 @@ class GmmInfo(C.Structure):
         return {f: (list(getattr(self, f)) if f == "centre" else getattr(self, f)) for f, _ in self._fields_}
 
 
+class KldParams(C.Structure):
+    """eslam_kld_params (include/eslam_gpu.h); the defaults are eslam_kld_params_default's but for
+    n_min, which that takes from the configuration."""
+    _fields_ = [
+        ("bin_xy", C.c_double),
+        ("theta_bins", C.c_uint32),
+        ("multinomial", C.c_uint32),
+        ("epsilon", C.c_double),
+        ("z_quantile", C.c_double),
+        ("n_min", C.c_uint64),
+        ("n_max", C.c_uint64),
+        ("min_change", C.c_double),
+        ("max_bins", C.c_uint64),
+    ]
+
+    def __init__(self, bin_xy=0.1, theta_bins=36, multinomial=0, epsilon=0.05, z_quantile=2.3263478740408408, n_min=1,
+                 n_max=0, min_change=0.0, max_bins=0):
+        super().__init__(bin_xy, theta_bins, multinomial, epsilon, z_quantile, n_min, n_max, min_change, max_bins)
+
+
+class KldInfo(C.Structure):
+    """eslam_kld_info (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("particles_counted", C.c_uint64),
+        ("particles_skipped", C.c_uint64),
+        ("bins_occupied", C.c_uint64),
+        ("origin", C.c_int64 * 2),
+        ("bins", C.c_uint64 * 3),
+        ("bound", C.c_double),
+        ("samples", C.c_uint64),
+        ("clamped", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {f: (list(getattr(self, f)) if f in ("origin", "bins") else getattr(self, f)) for f, _ in self._fields_}
+
+    def as_tuple(self):
+        """every field, the bound as its bits (NaN compares equal to itself)"""
+        import struct
+        return (self.particles_counted, self.particles_skipped, self.bins_occupied, tuple(self.origin), tuple(self.bins),
+                struct.unpack("<Q", struct.pack("<d", self.bound))[0], self.samples, self.clamped, self.pad)
+
+
 class RngState(C.Structure):
     _fields_ = [
         ("minstd_x", C.c_uint32),

@@ -119,6 +119,12 @@ def load_library(path=LIB_PATH):
         L.eslam_gmm_params_default.argtypes = [C.POINTER(A.GmmParams)]
         L.eslam_gmm_params_default.restype = None
         L.eslam_gpu_fit_pose_gmm.argtypes = [vp, C.POINTER(A.GmmParams), C.POINTER(A.GmmComponent), C.POINTER(A.GmmInfo)]
+    # a library without them is an error at the call
+    if hasattr(L, "eslam_gpu_kld_count"):
+        L.eslam_kld_params_default.argtypes = [C.POINTER(A.Config), C.POINTER(A.KldParams)]
+        L.eslam_kld_params_default.restype = None
+        L.eslam_gpu_kld_count.argtypes = [vp, C.POINTER(A.KldParams), C.POINTER(A.KldInfo)]
+        L.eslam_gpu_resample_kld.argtypes = [vp, C.POINTER(A.KldParams), C.POINTER(A.KldInfo), C.POINTER(A.ResampleInfo)]
     L.eslam_gpu_get_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_set_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_get_ancestors.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64]
@@ -497,6 +503,44 @@ class GpuFilter:
         means = np.array([list(out[i].mean) for i in range(k)], dtype=np.float64).reshape(k, 2)
         covs = np.array([list(out[i].cov) for i in range(k)], dtype=np.float64).reshape(k, 3)
         return weights, means, covs, info
+
+    def kld_params(self, **params):
+        """eslam_kld_params_default for this filter's configuration (n_min = its particle_count),
+        then the given fields"""
+        p = A.KldParams()
+        self.L.eslam_kld_params_default(C.byref(self.cfg), C.byref(p))
+        for k, v in params.items():
+            if k not in dict(A.KldParams._fields_):
+                raise TypeError(f"eslam_kld_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def kld_count(self, **params):
+        """eslam_gpu_kld_count: the occupied bins of the pose lattice, counted on the device, and
+        the particle count KLD-sampling asks for; the filter is unchanged.  params:
+        fields of eslam_kld_params over kld_params()'s defaults.  Returns the KldInfo; an
+        EslamError carries what the call filled in as .info.  A collective on a sharded filter."""
+        p = self.kld_params(**params)
+        info = A.KldInfo()
+        try:
+            self._check(self.L.eslam_gpu_kld_count(self.h, C.byref(p), C.byref(info)))
+        except EslamError as e:
+            e.info = info
+            raise
+        return info
+
+    def resample_kld(self, **params):
+        """eslam_gpu_resample_kld: kld_count, then the resample to its count (stratified, or
+        multinomial=1).  Returns (KldInfo, ResampleInfo); an EslamError carries the KldInfo as
+        .info.  A collective on a sharded filter."""
+        p = self.kld_params(**params)
+        info, rinfo = A.KldInfo(), A.ResampleInfo()
+        try:
+            self._check(self.L.eslam_gpu_resample_kld(self.h, C.byref(p), C.byref(info), C.byref(rinfo)))
+        except EslamError as e:
+            e.info = info
+            raise
+        return info, rinfo
 
     def ancestors(self):
         n = self.count()

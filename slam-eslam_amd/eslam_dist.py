@@ -159,6 +159,16 @@ class ShardedGpuFilter:
         """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
         return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
 
+    def kld_count(self, **params):
+        """eslam_gpu_kld_count on the sharded filter (a collective): the one-GPU KldInfo on every rank"""
+        return self.f.kld_count(**params)
+
+    def resample_kld(self, **params):
+        """eslam_gpu_resample_kld on the sharded filter (a collective): the count, then the sharded
+        resample to it; bounds, n_global, gbase and n_local follow the new table.  Returns
+        (KldInfo, ResampleInfo)."""
+        return _resample_sharded(self, lambda _: self.f.resample_kld(**params), None)
+
     def close(self):
         """Collective: every rank completes the exchange it may still owe, then frees its context."""
         if getattr(self.f, "h", None):
@@ -206,6 +216,16 @@ class RcclShardedGpuFilter:
     def resample_multinomial_sharded(self, samples):
         """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
         return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
+
+    def kld_count(self, **params):
+        """eslam_gpu_kld_count on the sharded filter (a collective): the one-GPU KldInfo on every rank"""
+        return self.f.kld_count(**params)
+
+    def resample_kld(self, **params):
+        """eslam_gpu_resample_kld on the sharded filter (a collective): the count, then the sharded
+        resample to it; bounds, n_global, gbase and n_local follow the new table.  Returns
+        (KldInfo, ResampleInfo)."""
+        return _resample_sharded(self, lambda _: self.f.resample_kld(**params), None)
 
     def close(self):
         """Collective: every rank completes the exchange it may still owe, then frees its context."""
