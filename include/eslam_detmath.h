@@ -2351,4 +2351,190 @@ DM_FN uint64_t dm_kld_samples(double bound, uint64_t n_min, uint64_t limit, uint
     return s;
 }
 
+/* ------------------------------------------------------------------------------------ */
+/* the pose estimate's moments over (x, y, z, yaw)                         */
+/* ------------------------------------------------------------------------------------ */
+#define DM_2PI_1 6.2831853069365025e+00     /* 0x401921fb54400000: the first 33 bits of 2 pi */
+#define DM_2PI_2 2.430840202602477e-10      /* 0x3df0b4611a626331: RN(2 pi - DM_2PI_1)       */
+
+/* d less the nearest whole number of turns: k = floor(d / (2 pi) + 1/2) and (d - k P1) - k P2.
+ * k DM_2PI_1 is exact for |k| < 2^20 and the first difference cancels.  Where the rounding of
+ * d DM_INV_2PI put k on the wrong side of the cut (d within a few ulps of an odd multiple of pi)
+ * the result would leave [-pi, pi] by as much as d's own ulp; k then moves by one, so the result
+ * is within [-pi - 1e-15, pi + 1e-15] for |d| up to 2^20 turns.  Against d - 2 pi round(d / (2 pi))
+ * in mpmath, |d| <= 50 and the neighbours of odd multiples of pi (tests/test_detmath_atan2.py):
+ * at most 2.0e-16 absolute (on the cut itself, where the two may pick opposite ends, taken on
+ * the circle).                                                                               */
+DM_FN double dm_wrap_pi(double d)
+{
+    double k = dm_floor(d * DM_INV_2PI + 0.5);
+    double r = (d - k * DM_2PI_1) - k * DM_2PI_2;
+    if (r > 3.141592653589793 || r < -3.141592653589793) {
+        k = r > 0.0 ? k + 1.0 : k - 1.0;
+        r = (d - k * DM_2PI_1) - k * DM_2PI_2;
+    }
+    return r;
+}
+
+/* atan(t) = t - t z P(z), z = t^2 <= (7/16)^2: P a degree-12 minimax fit (Remez,
+ * tools/gen_minimax.py; |t z (P - p)| / atan t < 2.5e-18); returns the correction t z p    */
+DM_POLY_TABLE(dm_c_atan, 13, 0.011584797603183015, -0.02803731287113866, 0.0397665350138786, -0.046828771530260216,
+              0.052513272176188244, -0.05881094640609188, 0.06666571785614105, -0.0769230269449829, 0.09090908912410753,
+              -0.1111111110700351, 0.14285714285658418, -0.19999999999999618, 0.3333333333333333)
+/* {hi, lo} of base +- s (tools/gen_minimax.py): the octant's base 0, pi/2, pi/2, pi taken with
+ * + - + -, the segment's s = 0, atan(1/2), pi/4 */
+DM_CONST double dm_atan2_tab[4][3][2] = {
+    {{0.0, 0.0}, {0.4636476090008061, 2.2698777452961687e-17}, {0.7853981633974483, 3.061616997868383e-17}},
+    {{1.5707963267948966, 6.123233995736766e-17}, {1.1071487177940904, 9.40447137356638e-17}, {0.7853981633974483, 3.061616997868383e-17}},
+    {{1.5707963267948966, 6.123233995736766e-17}, {2.0344439357957027, 2.841996617907152e-17}, {2.356194490192345, 9.184850993605148e-17}},
+    {{3.141592653589793, 1.2246467991473532e-16}, {2.677945044588987, 1.5527705369303147e-16}, {2.356194490192345, 9.184850993605148e-17}},
+};
+
+/* atan2(y, x) of finite arguments; signed zeros and the axes as C's atan2 (atan2(+-0, -0) is
+ * +-pi, atan2(+-0, +0) is +-0, atan2(y, +-0) is +-pi/2).  Octant reduction to a = min(|y|, |x|)
+ * over b = max: the angle is base +- atan(a / b).  Then the segment, chosen by comparisons:
+ * a / b below 7/16 directly; below 11/16 atan(1/2) + atan((2a - b) / (2b + a)); else
+ * pi/4 + atan((a - b) / (a + b)) -- both numerators exact -- so one division gives |t| <= 7/16.
+ * The octant's and the segment's constants are one two-part entry of dm_atan2_tab, and the
+ * result is formed as hi +- (t - (t z p -+ lo)): one rounding at the result's size.
+ * Evaluated on the host (on summed sines and cosines); through this header so that no result
+ * depends on a libm.  Worst error against mpmath at 40 digits over the inputs of
+ * tests/test_detmath_atan2.py: 1.00 ulp.                                                      */
+DM_FN double dm_atan2(double y, double x)
+{
+    const int sy = (int)(dm_bits(y) >> 63), sx = (int)(dm_bits(x) >> 63);
+    double a = dm_fabs(y), b = dm_fabs(x);
+    const int swap = a > b;
+    if (swap) { const double s = a; a = b; b = s; }
+    const int oct = swap ? (sx ? 2 : 1) : (sx ? 3 : 0);
+    int seg = 0;
+    double t;
+    if (a == 0.0) t = 0.0;                                 /* an axis, or both zero */
+    else if (a < 0.4375 * b) t = a / b;
+    else {
+        if (b > 0x1p1000) { a = a * 0x1p-4; b = b * 0x1p-4; }   /* 2b + a stays finite; exact, a >= 0.43 b */
+        if (a < 0.6875 * b) { seg = 1; t = (2.0 * a - b) / (2.0 * b + a); }
+        else { seg = 2; t = (a - b) / (a + b); }
+    }
+    const double z = t * t;
+    const double c = (t * z) * DM_POLY(dm_c_atan, 13, z);
+    const double hi = dm_atan2_tab[oct][seg][0], lo = dm_atan2_tab[oct][seg][1];
+    const double r = (oct & 1) ? hi - (t - (c + lo)) : hi + (t - (c - lo));
+    return sy ? -r : r;
+}
+
+/* The moments' sums.  Pass 1, DM_MOM_REC1 doubles: W_all over every valid particle, then over
+ * the counted ones S0, Q, Sx, Sy, Sz, Ss, Sc, Sv.  Pass 2, DM_MOM_REC2 doubles: S0, D_x D_y D_z
+ * D_t, then C_ab for a <= b in the order xx xy xz xt yy yz yt zz zt tt.  Weights are scaled by
+ * 2^-E (E = dm_stat_exp(max w over the valid particles)).                                   */
+#define DM_MOM_REC1 9
+#define DM_MOM_REC2 15
+
+/* the gate: centre, A = (axx, axy, ayy), its determinant and the threshold; on == 0: no gate */
+typedef struct dm_mom_gate {
+    double gx, gy, axx, axy, ayy, det, chi2;
+    int32_t on, pad;
+} dm_mom_gate;
+
+/* fills g from a gate's centre, cov (xx, xy, yy) and chi2; 0 when the gate is refused: det not
+ * finite or <= 0, axx <= 0, chi2 not finite or negative, or a centre that is not finite      */
+DM_FN int dm_mom_gate_set(dm_mom_gate* g, const double centre[2], const double cov[3], double chi2)
+{
+    g->gx = centre[0];
+    g->gy = centre[1];
+    g->axx = cov[0];
+    g->axy = cov[1];
+    g->ayy = cov[2];
+    g->det = g->axx * g->ayy - g->axy * g->axy;
+    g->chi2 = chi2;
+    g->on = 1;
+    g->pad = 0;
+    return dm_isfinite(g->det) && g->det > 0.0 && g->axx > 0.0 && dm_isfinite(chi2) && chi2 >= 0.0 && dm_isfinite(g->gx) &&
+           dm_isfinite(g->gy);
+}
+
+/* a particle takes part when all six of its values are finite and w > 0 */
+DM_FN int dm_mom_valid(double x, double y, double z, double th, double zs, double w)
+{
+    return dm_isfinite(x) && dm_isfinite(y) && dm_isfinite(z) && dm_isfinite(th) && dm_isfinite(zs) && dm_isfinite(w) && w > 0.0;
+}
+
+/* a valid particle is counted when it lies inside the gate (the E-step's quadratic form) */
+DM_FN int dm_mom_inside(const dm_mom_gate* g, double x, double y)
+{
+    if (!g->on) return 1;
+    const double dx = x - g->gx, dy = y - g->gy;
+    const double q = ((g->ayy * (dx * dx) - ((2.0 * g->axy) * dx) * dy) + g->axx * (dy * dy)) / g->det;
+    return q <= g->chi2;
+}
+
+/* pass 1: a valid particle's terms (t its scaled weight) */
+DM_FN void dm_mom_add1(double* s, int inside, double t, double x, double y, double z, double th, double zs)
+{
+    s[0] = s[0] + t;
+    if (!inside) return;
+    double sn, cs;
+    dm_sincos(th, &sn, &cs);
+    s[1] = s[1] + t;
+    s[2] = s[2] + t * t;
+    s[3] = s[3] + t * x;
+    s[4] = s[4] + t * y;
+    s[5] = s[5] + t * z;
+    s[6] = s[6] + t * sn;
+    s[7] = s[7] + t * cs;
+    s[8] = s[8] + t * (zs * zs);
+}
+
+/* after pass 1 (S0 > 0): mean = (mx, my, mz, psi); q = R, effective, weight_share, z_within */
+DM_FN void dm_mom_mean(const double* s, double mean[4], double q[4])
+{
+    const double S0 = s[1];
+    mean[0] = s[3] / S0;
+    mean[1] = s[4] / S0;
+    mean[2] = s[5] / S0;
+    mean[3] = (s[6] == 0.0 && s[7] == 0.0) ? 0.0 : dm_atan2(s[6], s[7]);
+    const double r = dm_sqrt(s[6] * s[6] + s[7] * s[7]) / S0;
+    q[0] = r < 1.0 ? r : 1.0;
+    q[1] = (S0 * S0) / s[2];
+    q[2] = S0 / s[0];
+    q[3] = s[8] / S0;
+}
+
+/* pass 2: a counted particle's terms around the mean */
+DM_FN void dm_mom_add2(double* s, double t, const double mean[4], double x, double y, double z, double th)
+{
+    const double dx = x - mean[0], dy = y - mean[1], dz = z - mean[2], dt = dm_wrap_pi(th - mean[3]);
+    const double tx = t * dx, ty = t * dy, tz = t * dz, tt = t * dt;
+    s[0] = s[0] + t;
+    s[1] = s[1] + tx;
+    s[2] = s[2] + ty;
+    s[3] = s[3] + tz;
+    s[4] = s[4] + tt;
+    s[5] = s[5] + tx * dx;
+    s[6] = s[6] + tx * dy;
+    s[7] = s[7] + tx * dz;
+    s[8] = s[8] + tx * dt;
+    s[9] = s[9] + ty * dy;
+    s[10] = s[10] + ty * dz;
+    s[11] = s[11] + ty * dt;
+    s[12] = s[12] + tz * dz;
+    s[13] = s[13] + tz * dt;
+    s[14] = s[14] + tt * dt;
+}
+
+/* after pass 2 (S0 > 0): the symmetric row-major 4 x 4 covariance over (x, y, z, yaw) */
+DM_FN void dm_mom_cov(const double* s, double cov[16])
+{
+    const double S0 = s[0];
+    double m[4];
+    for (int a = 0; a < 4; ++a) m[a] = s[1 + a] / S0;
+    int q = 5;
+    for (int a = 0; a < 4; ++a)
+        for (int b = a; b < 4; ++b) {
+            const double c = s[q++] / S0 - m[a] * m[b];
+            cov[4 * a + b] = c;
+            cov[4 * b + a] = c;
+        }
+}
+
 #endif /* ESLAM_DETMATH_H */

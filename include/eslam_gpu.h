@@ -655,6 +655,10 @@ int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index);  /* :160
 /* PoseEstimator::getCentroid src/PoseEstimator.cpp:354-383 (normalises in place, Q15):
  * position[3] + quaternion (w,x,y,z)                                                        */
 int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double orientation[4]);
+/* the yaw-free body orientation (w,x,y,z) of the last step -- zCompensatedOrientation of
+ * ContactModel::setContactPoints src/ContactModel.cpp:21-41 --, the factor getCentroid composes its
+ * orientation with after the yaw about Z; the identity before any step.  Reads host state only. */
+int eslam_gpu_get_z_compensated_orientation(eslam_ctx* ctx, double orientation[4]);
 
 /* ---- PoseDistribution::gmm (src/PoseParticle.hpp:88-114): a 2-D Gaussian mixture over (x, y) --
  * Fitted by EM on the device over the particles as they stand (a deferred exchange is settled
@@ -705,6 +709,44 @@ typedef struct eslam_gmm_info {
 } eslam_gmm_info;
 int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* params, eslam_gmm_component* out /* params->components */,
                            eslam_gmm_info* info /* may be NULL */);
+
+/* ---- the pose estimate with its covariance: moments over (x, y, z, yaw), summed on the device --
+ * Over the particles as they stand (a deferred exchange is settled and a pending gather run
+ * first) and their current weights at any scale, normalised or not.  The rule is this build's own
+ * (DESIGN.md 5i), all fp64 through eslam_detmath.h, every sum in getCentroid's order, so one GPU,
+ * a sharded filter and the CPU restatement give the same bits.  In short: a particle is valid when
+ * x, y, zpos, orientation, zsigma and w are finite and w > 0 (the others are skipped and counted).
+ * With a gate a valid particle is counted when it lies inside the ellipse
+ * (p - centre)^T cov^-1 (p - centre) <= chi2 over p = (x, y) -- a GMM component with chi2 = 9 is
+ * its 3-sigma ellipse, the identity with chi2 = r^2 a circle -- else it is gated out and counted as
+ * such; without a gate every valid particle is counted.  Weights are scaled by 2^-weight_exp, the
+ * exponent of the largest VALID weight (the gate never moves the scale).  mean is the weighted
+ * mean of x, y, z and the circular mean of the yaw, atan2 of the weighted sums of sin and cos
+ * (0 when both vanish), in (-pi, pi]: unlike eslam_gpu_get_centroid's linear mean it holds when
+ * the cloud straddles the +-pi cut or its yaws differ by whole turns.  cov is the weighted
+ * covariance of the deviations from the mean, the yaw's wrapped to one turn around the circular
+ * mean.  The call changes nothing in the filter: particles, weights (no in-place normalise), RNG,
+ * maps and pose hash are as before.  Synchronous; needs particles, no map.
+ * ESLAM_ERR_INVALID_ARG (checked before any launch or collective): a null ctx or out; a gate
+ * whose cov has a determinant xx yy - xy^2 that is not finite or not > 0, or xx <= 0, whose chi2
+ * is not finite or negative, or whose centre is not finite.  ESLAM_ERR_NOT_INITIALISED: no
+ * particles.  A poisoned filter returns its fault.
+ * No counted particle: ESLAM_OK, the counts filled, every double zero.
+ * Sharded filters: a collective in SPMD order.  The ranks first compare their gates (one
+ * all_gather of host words; a mismatch is ESLAM_ERR_INVALID_ARG on every rank); every rank
+ * returns the one-GPU result bit for bit.                                                    */
+typedef struct eslam_pose_gate { double centre[2]; double cov[3] /* xx, xy, yy */; double chi2; } eslam_pose_gate;
+typedef struct eslam_pose_moments {
+    uint64_t particles_counted, particles_gated_out, particles_skipped;
+    double mean[4];          /* x, y, z, yaw: yaw the circular mean in (-pi, pi]           */
+    double cov[16];          /* row-major, symmetric, over (x, y, z, yaw deviation)         */
+    double z_within;         /* weighted mean of zSigma^2: add to cov[10] for the total z variance */
+    double yaw_resultant;    /* mean resultant length R in [0, 1]                           */
+    double effective;        /* (sum w)^2 / sum w^2 of the counted particles                */
+    double weight_share;     /* counted weight / valid weight (1 without a gate)            */
+    int32_t weight_exp, pad;
+} eslam_pose_moments;
+int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gate /* may be NULL */, eslam_pose_moments* out);
 
 /* ---- KLD-sampling (Fox 2003): the particle count the posterior needs --------------------------
  * The reference takes `samples` from its caller (src/ParticleFilter.hpp); the rule is this

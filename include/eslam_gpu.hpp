@@ -489,6 +489,55 @@ struct GmmParams {                        // eslam_gmm_params_default
     double tolerance = 1e-5, minVariance = 1e-6;
 };
 
+// The gate of poseMoments(): the ellipse (p - centre)^T cov^-1 (p - centre) <= chi2 over p = (x, y)
+// (eslam_pose_gate).  From a mixture's component and a sigma count: its mean, its covariance and
+// chi2 = sigmas^2, so 3 is the component's 3-sigma ellipse.
+struct PoseGate {
+    Vector2d centre;
+    Matrix2d cov;                         // symmetric: (0, 1) is read
+    double chi2 = 9.0;
+    PoseGate() { cov(0, 0) = cov(1, 1) = 1.0; }
+    PoseGate(const Vector2d& c, const Matrix2d& a, double chi2_) : centre(c), cov(a), chi2(chi2_) {}
+    PoseGate(const GaussianMixture2D::Parameter& component, double sigmas)
+        : centre(component.dist.mean), cov(component.dist.cov), chi2(sigmas * sigmas) {}
+    eslam_pose_gate c() const
+    {
+        eslam_pose_gate g;
+        g.centre[0] = centre[0];
+        g.centre[1] = centre[1];
+        g.cov[0] = cov(0, 0);
+        g.cov[1] = cov(0, 1);
+        g.cov[2] = cov(1, 1);
+        g.chi2 = chi2;
+        return g;
+    }
+};
+
+// The pose estimate with its covariance (eslam_gpu_pose_moments; the rule is this build's own,
+// DESIGN.md 5i): the fields of eslam_pose_moments, and the yaw-free body orientation of the last
+// step that pose() composes the orientation with.
+struct PoseMoments {
+    eslam_pose_moments m = {};
+    Quaterniond zCompensatedOrientation;
+    uint64_t particlesCounted() const { return m.particles_counted; }
+    uint64_t particlesGatedOut() const { return m.particles_gated_out; }
+    uint64_t particlesSkipped() const { return m.particles_skipped; }
+    Vector3d position() const { return Vector3d(m.mean[0], m.mean[1], m.mean[2]); }
+    double yaw() const { return m.mean[3]; }                  // the circular mean, in (-pi, pi]
+    double cov(int r, int c) const { return m.cov[4 * r + c]; }   // over (x, y, z, yaw deviation)
+    double zWithin() const { return m.z_within; }             // add to cov(2, 2) for the total z variance
+    double yawResultant() const { return m.yaw_resultant; }
+    double effective() const { return m.effective; }
+    double weightShare() const { return m.weight_share; }
+    // the mean as getCentroid composes its pose (src/PoseEstimator.cpp:378-382): the yaw about Z,
+    // then zCompensatedOrientation
+    Pose pose() const
+    {
+        const double ha = 0.5 * m.mean[3];
+        return Pose(position(), Quaterniond(std::cos(ha), 0.0, 0.0, std::sin(ha)) * zCompensatedOrientation);
+    }
+};
+
 // KLD-sampling's parameters (eslam_kld_params_default).  nMin 0: the configured
 // particle count.
 struct KldParams {
@@ -1091,6 +1140,22 @@ public:
         }
         return g;
     }
+    // the pose estimate with its 4 x 4 covariance over (x, y, z, yaw), summed on the device over
+    // the particles as they stand, or over those inside `gate` (eslam_gpu_pose_moments); the filter
+    // is unchanged.  The dominant cluster's estimate: fitGmm(), its heaviest component c, then
+    // PoseGate g(c, 3) and poseMoments(&g).
+    PoseMoments poseMoments(const PoseGate* gate = nullptr) const
+    {
+        flush();
+        PoseMoments r;
+        eslam_pose_gate g;
+        if (gate) g = gate->c();
+        check(ctx_, eslam_gpu_pose_moments(ctx_, gate ? &g : nullptr, &r.m));
+        double q[4];
+        check(ctx_, eslam_gpu_get_z_compensated_orientation(ctx_, q));
+        r.zCompensatedOrientation = Quaterniond(q[0], q[1], q[2], q[3]);
+        return r;
+    }
 
     // getParticles(): the particles as a vector the caller may edit, like the reference's
     // std::vector<Particle>& (src/ParticleFilter.hpp:150-153; processMap edits weights through
@@ -1622,6 +1687,7 @@ public:
         return d;
     }
     GaussianMixture2D fitGmm(const GmmParams& gp = GmmParams()) { return estimator().fitGmm(gp); }
+    PoseMoments poseMoments(const PoseGate* gate = nullptr) const { return estimator().poseMoments(gate); }
     // KLD-sampling: the particle count the posterior asks for, and the resample to it
     eslam_kld_info kldCount(const KldParams& kp = KldParams()) { return estimator().kldCount(kp); }
     void resampleKld(const KldParams& kp = KldParams()) { estimator().resampleKld(kp); }

@@ -170,6 +170,7 @@ struct eslam_ctx {
     uint64_t nrecv_maps = 0;                 // records whose maps wait in recvhdr / recvpay
     Dev<double> cent;                        // getCentroid's chunk records (sharded: sized by set_comm)
     Dev<double> gmm;                         // eslam_gpu_fit_pose_gmm's words, chunk records and exchange, grown on demand
+    Dev<double> moments;                     // eslam_gpu_pose_moments' words, chunk records and exchange (gmm's layout), grown on demand
     Dev<char> kld;                           // eslam_gpu_kld_count's scratch (KldScratch: records, bitmap, the ranks'
                                              //   bitmaps), kept between calls
     Dev<double> bspill;                      // K1's parked per-bucket sums (k1_bspill_bytes)

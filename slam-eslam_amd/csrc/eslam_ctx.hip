@@ -3159,6 +3159,13 @@ extern "C" int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double
     return ESLAM_OK;
 }
 
+extern "C" int eslam_gpu_get_z_compensated_orientation(eslam_ctx* ctx, double orientation[4])
+{
+    if (!ctx || !orientation) return ESLAM_ERR_INVALID_ARG;
+    memcpy(orientation, ctx->zcomp, sizeof(ctx->zcomp));
+    return ESLAM_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // PoseDistribution::gmm: the 2-D Gaussian mixture over (x, y), fitted on the device
 // ---------------------------------------------------------------------------------------
@@ -3211,17 +3218,18 @@ uint64_t gmm_carve(const eslam_ctx* ctx, uint32_t R, uint32_t J, void* base, Gmm
     return c.bytes();
 }
 
-// one pass: the chunk records of this context (sharded: of every rank, all-gathered into global
-// chunk order), then the one-GPU tree; rec = the pass' DM_GMM_REC(K) sums
-int gmm_pass(eslam_ctx* ctx, int K, bool hard, const GmmPass& P, uint32_t J, const GmmBufs& g, double* rec)
+// one pass of R sums per chunk: `launch(dst)` leaves the chunk records of this context at dst
+// (sharded: those of every rank are then all-gathered into global chunk order), then the one-GPU
+// tree; rec = the pass' R sums
+template <typename Launch>
+int chunk_pass(eslam_ctx* ctx, uint32_t R, const GmmBufs& g, double* rec, Launch launch)
 {
-    const uint32_t R = DM_GMM_REC(K);
     hipError_t e = hipSuccess;
     if (!ctx->sharded) {
-        e = eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, g.a, ctx->stream);
+        e = launch(g.a);
     } else {
         e = hipMemsetAsync(g.mine, 0, g.maxch * R * sizeof(double), ctx->stream);
-        if (e == hipSuccess) e = eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, g.mine, ctx->stream);
+        if (e == hipSuccess) e = launch(g.mine);
         if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
         const int rc = comm_allgather(ctx, g.mine, g.all, g.maxch * R * sizeof(double));
         if (rc) return rc;
@@ -3237,6 +3245,14 @@ int gmm_pass(eslam_ctx* ctx, int K, bool hard, const GmmPass& P, uint32_t J, con
     if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
     memcpy(rec, ctx->scratch_host.get(), R * sizeof(double));
     return ESLAM_OK;
+}
+
+// a pass of the mixture's fit; rec = its DM_GMM_REC(K) sums
+int gmm_pass(eslam_ctx* ctx, int K, bool hard, const GmmPass& P, uint32_t J, const GmmBufs& g, double* rec)
+{
+    return chunk_pass(ctx, DM_GMM_REC(K), g, rec, [&](double* dst) {
+        return eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
+    });
 }
 }  // namespace
 
@@ -3353,6 +3369,90 @@ extern "C" int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* pa
     inf.centre[1] = P.cy;
     inf.weight_exp = P.E;
     if (info) *info = inf;
+    return ESLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the pose estimate with its 4 x 4 covariance over (x, y, z, yaw), summed on the device
+// ---------------------------------------------------------------------------------------
+extern "C" int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gate, eslam_pose_moments* out)
+{
+    if (!ctx || !out) return ESLAM_ERR_INVALID_ARG;
+    MomPass P;
+    memset(&P, 0, sizeof(P));
+    if (gate && !dm_mom_gate_set(&P.g, gate->centre, gate->cov, gate->chi2))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG,
+                    "pose_moments: the gate needs a finite centre, xx > 0, a finite determinant > 0 and a finite chi2 >= 0");
+    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
+    if (const int rc_ = check_poisoned(ctx)) return rc_;
+    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
+    static_assert((kMaxRanks + 1) * kMomWords * 8 <= 4096 && DM_MOM_REC2 * 8 <= 4096, "scratch_host holds a readback");
+    static_assert(kMomWords <= kGmmWords && kMomBoundsBlocks <= kGmmBoundsBlocks, "gmm_carve's pass B arrays hold the moments'");
+    if (ctx->sharded) {
+        // the ranks' gates, compared before anything depends on them: the six doubles' bits, all
+        // ones without a gate (no accepted gate has them: its values are finite)
+        uint64_t mine[6], all[6 * kMaxRanks];
+        memset(mine, 0xff, sizeof(mine));
+        if (gate) memcpy(mine, gate, sizeof(mine));
+        static_assert(sizeof(eslam_pose_gate) == sizeof(mine) && sizeof(mine) <= kHostXBytes, "host_allgather's words");
+        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
+        if (rc) return rc;
+        for (int r = 0; r < ctx->comm.nranks; ++r)
+            if (memcmp(&all[6 * r], mine, sizeof(mine)) != 0)
+                return fail(ctx, ESLAM_ERR_INVALID_ARG, "pose_moments: the ranks' gates differ");
+    }
+    int rc = materialize(ctx);                       // the particles as they stand
+    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
+    GmmBufs g;                                       // the fit's layout at the wider record
+    if (!rc) rc = grow(ctx, ctx->moments, gmm_carve(ctx, DM_MOM_REC2, J, nullptr, &g));
+    rc = agree(ctx, rc, "pose_moments");             // no rank is left alone in the collectives below
+    if (rc) return rc;
+    gmm_carve(ctx, DM_MOM_REC2, J, ctx->moments.get(), &g);
+
+    // pass B: order-free words, reduced over the ranks identically everywhere
+    const int G = ctx->sharded ? ctx->comm.nranks : 1;
+    HIPCHK(ctx, eslam_launch_moments_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, &P, g.part, g.words, ctx->stream));
+    if (ctx->sharded) {
+        rc = comm_allgather(ctx, g.words, g.words_all, kMomWords * sizeof(uint64_t));
+        if (rc) return rc;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->sharded ? g.words_all : g.words, (uint64_t)G * kMomWords * sizeof(uint64_t),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t B[kMomWords] = {};
+    for (int r = 0; r < G; ++r) {
+        const uint64_t* w = ctx->scratch_host.as<const uint64_t>() + (uint64_t)r * kMomWords;
+        B[kMomMaxW] = B[kMomMaxW] > w[kMomMaxW] ? B[kMomMaxW] : w[kMomMaxW];
+        for (int q = kMomCounted; q <= kMomSkipped; ++q) B[q] += w[q];
+    }
+    eslam_pose_moments m;
+    memset(&m, 0, sizeof(m));
+    m.particles_counted = B[kMomCounted];
+    m.particles_gated_out = B[kMomGatedOut];
+    m.particles_skipped = B[kMomSkipped];
+    if (B[kMomCounted] + B[kMomGatedOut]) m.weight_exp = P.E = dm_stat_exp(gmm_unkey(B[kMomMaxW]));
+    if (!B[kMomCounted]) {                           // no counted particle: the counts, every double zero
+        *out = m;
+        return ESLAM_OK;
+    }
+    auto pass = [&](int which, uint32_t R, double* rec) {
+        return chunk_pass(ctx, R, g, rec, [&](double* dst) {
+            return eslam_launch_moments_pass(which, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
+        });
+    };
+    double rec[DM_MOM_REC2], q[4];
+    rc = pass(1, DM_MOM_REC1, rec);
+    if (rc) return rc;
+    dm_mom_mean(rec, P.mean, q);
+    rc = pass(2, DM_MOM_REC2, rec);
+    if (rc) return rc;
+    memcpy(m.mean, P.mean, sizeof(m.mean));
+    dm_mom_cov(rec, m.cov);
+    m.yaw_resultant = q[0];
+    m.effective = q[1];
+    m.weight_share = q[2];
+    m.z_within = q[3];
+    *out = m;
     return ESLAM_OK;
 }
 

@@ -658,6 +658,18 @@ struct GmmPass {
     dm_gmm_comp c[DM_GMM_MAX];
 };
 
+// The pose estimate's moments (eslam_moments.hip).  Pass B's words: the maximum of
+// the valid particles' weight keys (gmm_key) and the three counts, all zero before the kernel.
+constexpr int kMomMaxW = 0, kMomCounted = 1, kMomGatedOut = 2, kMomSkipped = 3;
+constexpr int kMomWords = 4;
+constexpr int kMomBoundsBlocks = 1024;       // blocks of pass B at most (each wave leaves kMomWords words)
+// a pass' arguments: the gate, the weight scale 2^-E and (pass 2) the mean the deviations are taken around
+struct MomPass {
+    dm_mom_gate g;
+    double mean[4];
+    int32_t E, pad;
+};
+
 // KLD-sampling's bin count (eslam_kld.hip).  A record of pass 1: the minima and
 // maxima of the counted particles' cell indices (INT32_MAX / INT32_MIN where nothing was counted)
 // and the counts of counted and skipped particles; the population count's record uses kKldCounted

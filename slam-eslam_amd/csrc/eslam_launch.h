@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All eleven .hip files include it, the defining one too: the
+// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All twelve .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -78,6 +78,12 @@ hipError_t eslam_launch_gmm_bounds(DevState s0, DevState s1, uint64_t n, Ctl* ct
 hipError_t eslam_launch_gmm_pass(int K, int hard, DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, const GmmPass* P,
                                  double* chunk_out, hipStream_t stream);
 hipError_t eslam_launch_gmm_tree(double* a, double* b, uint64_t m, uint32_t R, double* out, hipStream_t stream);
+
+// ---- eslam_moments.hip (the pose estimate's moments: pass B, a pass' chunk records; the tree is eslam_launch_gmm_tree)
+hipError_t eslam_launch_moments_bounds(DevState s0, DevState s1, uint64_t n, Ctl* ctl, const MomPass* P, uint64_t* part,
+                                       uint64_t* out, hipStream_t stream);
+hipError_t eslam_launch_moments_pass(int pass, DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, const MomPass* P,
+                                     double* chunk_out, hipStream_t stream);
 
 // ---- eslam_kld.hip (KLD-sampling's bin count: the box, the marked bitmap, its population count)
 hipError_t eslam_launch_kld_bounds(DevState s0, DevState s1, uint64_t n, const Ctl* ctl, double inv, uint32_t theta_bins,

@@ -326,6 +326,49 @@ class GmmInfo(C.Structure):
         return {f: (list(getattr(self, f)) if f == "centre" else getattr(self, f)) for f, _ in self._fields_}
 
 
+class PoseGate(C.Structure):
+    """eslam_pose_gate: the ellipse (p - centre)^T cov^-1 (p - centre) <= chi2 over p = (x, y); cov as xx, xy, yy."""
+    _fields_ = [
+        ("centre", C.c_double * 2),
+        ("cov", C.c_double * 3),
+        ("chi2", C.c_double),
+    ]
+
+    def __init__(self, centre=(0.0, 0.0), cov=(1.0, 0.0, 1.0), chi2=9.0):
+        super().__init__((C.c_double * 2)(*centre), (C.c_double * 3)(*cov), chi2)
+
+
+class PoseMoments(C.Structure):
+    """eslam_pose_moments (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("particles_counted", C.c_uint64),
+        ("particles_gated_out", C.c_uint64),
+        ("particles_skipped", C.c_uint64),
+        ("mean", C.c_double * 4),
+        ("cov", C.c_double * 16),
+        ("z_within", C.c_double),
+        ("yaw_resultant", C.c_double),
+        ("effective", C.c_double),
+        ("weight_share", C.c_double),
+        ("weight_exp", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {f: (list(getattr(self, f)) if f in ("mean", "cov") else getattr(self, f)) for f, _ in self._fields_}
+
+    def doubles(self):
+        """the 24 doubles in the struct's order"""
+        return list(self.mean) + list(self.cov) + [self.z_within, self.yaw_resultant, self.effective, self.weight_share]
+
+    def as_tuple(self):
+        """every field, the doubles as their bits (NaN compares equal to itself)"""
+        import struct
+        d = self.doubles()
+        return (self.particles_counted, self.particles_gated_out, self.particles_skipped) + \
+            struct.unpack(f"<{len(d)}Q", struct.pack(f"<{len(d)}d", *d)) + (self.weight_exp, self.pad)
+
+
 class KldParams(C.Structure):
     """eslam_kld_params (include/eslam_gpu.h); the defaults are eslam_kld_params_default's but for
     n_min, which that takes from the configuration."""

@@ -119,6 +119,8 @@ def load_library(path=LIB_PATH):
         L.eslam_gmm_params_default.argtypes = [C.POINTER(A.GmmParams)]
         L.eslam_gmm_params_default.restype = None
         L.eslam_gpu_fit_pose_gmm.argtypes = [vp, C.POINTER(A.GmmParams), C.POINTER(A.GmmComponent), C.POINTER(A.GmmInfo)]
+    if hasattr(L, "eslam_gpu_pose_moments"):
+        L.eslam_gpu_pose_moments.argtypes = [vp, C.POINTER(A.PoseGate), C.POINTER(A.PoseMoments)]
     # a library without them is an error at the call
     if hasattr(L, "eslam_gpu_kld_count"):
         L.eslam_kld_params_default.argtypes = [C.POINTER(A.Config), C.POINTER(A.KldParams)]
@@ -503,6 +505,15 @@ class GpuFilter:
         means = np.array([list(out[i].mean) for i in range(k)], dtype=np.float64).reshape(k, 2)
         covs = np.array([list(out[i].cov) for i in range(k)], dtype=np.float64).reshape(k, 3)
         return weights, means, covs, info
+
+    def pose_moments(self, gate=None):
+        """eslam_gpu_pose_moments: the pose estimate -- the weighted mean of (x, y, z), the circular
+        mean of the yaw -- with its 4 x 4 covariance, summed on the device; the
+        filter is unchanged.  gate: None, or a PoseGate whose ellipse selects the particles
+        counted.  Returns the PoseMoments.  A collective on a sharded filter."""
+        out = A.PoseMoments()
+        self._check(self.L.eslam_gpu_pose_moments(self.h, None if gate is None else C.byref(gate), C.byref(out)))
+        return out
 
     def kld_params(self, **params):
         """eslam_kld_params_default for this filter's configuration (n_min = its particle_count),

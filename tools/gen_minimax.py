@@ -1,4 +1,4 @@
-"""Minimax kernel polynomials of include/eslam_detmath.h (sin, cos, exp, log kernels).
+"""Minimax kernel polynomials of include/eslam_detmath.h (sin, cos, exp, log, atan kernels).
 
 Provenance: a Remez exchange in mpmath at 60 digits on the reduced ranges the header uses,
 coefficients then rounded to double; the printed error is that of the rounded polynomial
@@ -10,6 +10,8 @@ coefficients then rounded to double; the printed error is that of the rounded po
   exp  e^r = 1 + r (1 + r (1/2 + r P(r))), P(r) = (e^r - 1 - r - r^2/2) / r^3, |r| <= ln2/2
   log  log(1+f) = f - s (f - z P(z)),    P(z) = 2 (atanh(sqrt z)/sqrt z - 1) / z,
        s = f / (2 + f), z = s^2 <= ((sqrt2 - 1)/(sqrt2 + 1))^2
+  atan atan(t) = t - t z P(z),           P(z) = (1 - atan(sqrt z)/sqrt z) / z,  z = t^2 <= (7/16)^2
+       (dm_atan2: t the reduced ratio of its segment; and the table of its two-part constants)
 """
 import mpmath as mp
 
@@ -41,6 +43,13 @@ def p_log(z):
         return mp.mpf(2) / 3
     s = mp.sqrt(z)
     return 2 * (mp.atanh(s) / s - 1) / z
+
+
+def p_atan(z):
+    if z == 0:
+        return mp.mpf(1) / 3
+    t = mp.sqrt(z)
+    return (1 - mp.atan(t) / t) / z
 
 
 def peval(c, x):                       # c: lowest degree first
@@ -111,3 +120,15 @@ if __name__ == "__main__":
     report("exp P(r)", p_exp, -h, h, 9, scale=lambda r: abs(r) ** 3 / mp.exp(r))
     sm = (mp.sqrt(2) - 1) / (mp.sqrt(2) + 1)
     report("log P(z)", p_log, 0, sm * sm, 6, scale=lambda z: z * mp.sqrt(z) / (2 * mp.atanh(mp.sqrt(z)) + mp.mpf("1e-300")))
+    # dm_atan2: |t| <= 7/16 after the segment reduction; the error relative to atan(t)
+    za = (mp.mpf(7) / 16) ** 2 * (1 + mp.mpf("1e-9"))
+    report("atan P(z)", p_atan, 0, za, 12, scale=lambda z: z * mp.sqrt(z) / (mp.atan(mp.sqrt(z)) + mp.mpf("1e-300")))
+    # dm_atan2_tab[octant][segment] = {hi, lo} of base +- s: base 0, pi/2, pi/2, pi with sign + - + -,
+    # s = 0, atan(1/2), pi/4
+    for base, sign in ((0, 1), (mp.pi / 2, -1), (mp.pi / 2, 1), (mp.pi, -1)):
+        row = []
+        for s in (mp.mpf(0), mp.atan(mp.mpf(1) / 2), mp.pi / 4):
+            c = base + sign * s
+            hi = float(c)
+            row.append("{%r, %r}" % (hi, float(c - mp.mpf(hi))))
+        print("    {" + ", ".join(row) + "},")
