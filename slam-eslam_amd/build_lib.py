@@ -31,7 +31,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ESLAM_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["eslam_kernels.hip", "eslam_resample.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_snapshot.hip",
-           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_gmm.hip", "eslam_moments.hip", "eslam_kld.hip", "eslam_ctx.hip", "eslam_host_comm.hip"]
+           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_gmm.hip", "eslam_moments.hip", "eslam_kld.hip", "eslam_ctx.hip", "eslam_host_comm.hip",
+           "eslam_host_map.hip", "eslam_host_stats.hip", "eslam_host_snapshot.hip"]
 HEADERS = [os.path.join(CSRC, "eslam_internal.h"), os.path.join(CSRC, "eslam_launch.h"), os.path.join(CSRC, "eslam_buf.h"),
            os.path.join(CSRC, "eslam_scratch.h"), os.path.join(CSRC, "eslam_ctx.h"),
            os.path.join(ROOT, "include", "eslam_gpu.h"), os.path.join(ROOT, "include", "eslam_detmath.h")]

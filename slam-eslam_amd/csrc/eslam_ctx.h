@@ -1,6 +1,8 @@
 // eslam_ctx.h -- host-only: the context behind the C ABI of include/eslam_gpu.h, and the helpers
 // that more than one host file uses (namespace eslam_host).  Included by the host files:
-// eslam_ctx.hip and eslam_host_comm.hip (the multi-GPU plumbing).
+// eslam_ctx.hip (lifecycle, particles, the step, the resamplers), eslam_host_map.hip (the maps and
+// the scan build), eslam_host_stats.hip (centroid, mixture, moments, KLD), eslam_host_snapshot.hip
+// (save and load) and eslam_host_comm.hip (the multi-GPU plumbing).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -263,10 +265,30 @@ int grow(eslam_ctx* ctx, B& buf, uint64_t bytes)
     return ESLAM_OK;
 }
 
+inline bool particle_maps(const eslam_ctx* ctx) { return (ctx->cfg.flags & ESLAM_FLAG_PARTICLE_MAPS) != 0; }
+
+inline const LocalMaps* store_of(const eslam_ctx* ctx) { return particle_maps(ctx) ? &ctx->lm : nullptr; }
+
 // ---- eslam_ctx.hip
 extern std::atomic<int> g_statics_sharded;
 int settle(eslam_ctx* ctx);              // completes a deferred sharded exchange (run_update_tail_multi)
 void free_particles(eslam_ctx* ctx);
+void q_to_mat(const double q[4], double R[9]);
+void q_mul(const double a[4], const double b[4], double r[4]);
+void q_from_yaw(double angle, double q[4]);
+void remove_yaw(const double q[4], double out[4]);
+int check_poisoned(eslam_ctx* ctx);
+int read_ctl(eslam_ctx* ctx);
+int write_ctl(eslam_ctx* ctx);
+int alloc_particles(eslam_ctx* ctx, uint64_t n);
+int local_maps_reset(eslam_ctx* ctx);
+int reset_ctl_for_new_particles(eslam_ctx* ctx, int wexp);
+const double* hash_field(eslam_ctx* ctx, int f);
+MergeParams merge_params(eslam_ctx* ctx, const CowScratch& cs);
+GatherView gather_view(eslam_ctx* ctx);
+int materialize(eslam_ctx* ctx);
+int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info);
+int resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info);
 
 // ---- eslam_host_comm.hip
 int comm_allgather(eslam_ctx* ctx, const void* dsend, void* drecv, uint64_t bytes);
@@ -278,10 +300,19 @@ int comm_alltoallv(eslam_ctx* ctx, const void* dsend, const uint64_t* sb, void* 
 // pass through the buffer, so only that assert catches a caller that outgrows it.
 constexpr uint64_t kHostXBytes = 6 * 8;   // the largest user: the snapshot plan's six words (snap_plan)
 int host_allgather(eslam_ctx* ctx, const void* send, void* recv, uint64_t bytes);
+// the check that the ranks of a collective call were given the same parameters: gathers `nwords`
+// words of every rank and fails with ESLAM_ERR_INVALID_ARG and `msg` where a rank's differ from `mine`
+int same_on_every_rank(eslam_ctx* ctx, const uint64_t* mine, uint32_t nwords, const char* msg);
 // `rc` itself on an unsharded filter.  On a sharded one a collective: ESLAM_OK on a rank means
 // every rank passed ESLAM_OK.  A failing rank keeps its own code (and message); the others return
 // ESLAM_ERR_COMM with "<what>: rank R failed (C)".
 int agree(eslam_ctx* ctx, int rc, const char* what);
+// the chunk records of a sum over the particles, one per 64 J particles of every shard in the table
+// gall[0..G]: each rank's count (nch, may be null), the largest (at least 1) and their sum
+void chunk_shape(const uint64_t* gall, int G, uint32_t J, uint64_t* nch, uint64_t* maxch, uint64_t* total);
+// every rank's `mine` (maxch records of R doubles, zero-padded) all-gathered into `all`, then each
+// rank's nch[r] records copied to `a` in global chunk order
+int gather_chunks(eslam_ctx* ctx, const uint64_t* nch, uint64_t maxch, uint32_t R, const double* mine, double* all, double* a);
 uint64_t centroid_bytes(const uint64_t* gall, int G, uint32_t J);
 // a shard table's buffers (may fail; nothing else changes), and the table itself (eslam_host_comm.hip)
 int reserve_shard_table(eslam_ctx* ctx, int nranks, uint64_t n_global, const uint64_t* shard_gbase);

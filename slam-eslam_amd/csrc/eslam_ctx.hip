@@ -1,5 +1,9 @@
-// eslam_ctx.hip -- host side of libeslam_gpu: the C ABI of include/eslam_gpu.h (the context itself
-// and what crosses the host files: eslam_ctx.h; the multi-GPU plumbing: eslam_host_comm.hip).
+// eslam_ctx.hip -- host side of libeslam_gpu: the context's lifecycle, the particles (allocation,
+// initialisation, the surface hash, upload, download, records), the whole step and the resamplers
+// of the C ABI of include/eslam_gpu.h.  The context itself and what crosses the host files:
+// eslam_ctx.h.  The maps and the scan build: eslam_host_map.hip; the estimates (centroid, mixture,
+// moments, KLD): eslam_host_stats.hip; snapshots: eslam_host_snapshot.hip; the multi-GPU plumbing:
+// eslam_host_comm.hip.
 //
 // Per-step host work is O(1): the reference's per-step scalar preparation
 // (src/PoseEstimator.cpp:186-194: yaw, removeYaw, the odometry z delta and variance,
@@ -27,7 +31,7 @@
 // ---------------------------------------------------------------------------------------
 // small Eigen / base-types restatements (host, per step)
 // ---------------------------------------------------------------------------------------
-namespace {
+namespace eslam_host {
 
 void q_to_mat(const double q[4], double R[9])          // QuaternionBase::toRotationMatrix
 {
@@ -58,6 +62,10 @@ void q_from_yaw(double angle, double q[4])              // Quaternion(AngleAxis(
     q[1] = s * 0.0; q[2] = s * 0.0; q[3] = s * 1.0;
 }
 
+}  // namespace eslam_host
+
+namespace {
+
 void q_rotate(const double q[4], const double v[3], double out[3])   // _transformVector
 {
     const double qx = q[1], qy = q[2], qz = q[3], w = q[0];
@@ -77,12 +85,16 @@ double get_yaw(const double q[4])                        // base::getYaw (getEul
     return x > 1e-12 ? atan2(R[3], R[0]) : 0.0;
 }
 
-void remove_yaw(const double q[4], double out[4])       // base::removeYaw
+}  // namespace
+
+void eslam_host::remove_yaw(const double q[4], double out[4])       // base::removeYaw
 {
     double a[4];
     q_from_yaw(-get_yaw(q), a);
     q_mul(a, q, out);
 }
+
+namespace {
 
 void q_from_mat(const double m[9], double q[4])          // Eigen quaternion from 3x3
 {
@@ -166,12 +178,8 @@ static ProcessStatics& process_statics()
 // their respawns and hash indices would disagree (eslam_gpu_set_comm refuses a second one)
 std::atomic<int> eslam_host::g_statics_sharded{0};
 
-// timing mode (EventRing): event k (0..4) of the current step; event k (0..4) of the current map
-// update (start, gather, copy on write, plan, merge); event k (0: start, 1: end) of the current
-// map match
+// timing mode (EventRing): event k (0..4) of the current step
 static void rec(eslam_ctx* ctx, int k) { ctx->ring.record(ctx->timing, k, ctx->stream); }
-static void mrec(eslam_ctx* ctx, int k) { ctx->mring.record(ctx->timing, k, ctx->stream); }
-static void xrec(eslam_ctx* ctx, int k) { ctx->xring.record(ctx->timing, k, ctx->stream); }
 
 extern "C" int eslam_gpu_abi_version(void) { return ESLAM_ABI_VERSION; }
 
@@ -220,10 +228,7 @@ extern "C" void eslam_config_default(eslam_config* c)
 
 extern "C" const char* eslam_gpu_last_error(const eslam_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-static int materialize(eslam_ctx* ctx);
 static int store_receive(eslam_ctx* ctx);
-static int local_maps_reset(eslam_ctx* ctx);
-static GatherView gather_view(eslam_ctx* ctx);
 
 static const char* kPoisonMsg =
     "resample scan: a cross-block wait gave up (a preceding tile's total or the finalize never arrived); "
@@ -241,7 +246,7 @@ static int poison_fail(eslam_ctx* ctx)
     return ctx->poison_pages ? fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, kPagesMsg) : fail(ctx, ESLAM_ERR_HIP, kPoisonMsg);
 }
 
-static int check_poisoned(eslam_ctx* ctx)
+int eslam_host::check_poisoned(eslam_ctx* ctx)
 {
     if (!ctx->poisoned) {
         const uint32_t f = __atomic_load_n(ctx->fault_host.get(), __ATOMIC_ACQUIRE);
@@ -253,14 +258,14 @@ static int check_poisoned(eslam_ctx* ctx)
     return ctx->poisoned ? poison_fail(ctx) : ESLAM_OK;
 }
 
-static int read_ctl(eslam_ctx* ctx)
+int eslam_host::read_ctl(eslam_ctx* ctx)
 {
     HIPCHK(ctx, hipMemcpyAsync(ctx->ctl_host, ctx->ctl, sizeof(Ctl), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ESLAM_OK;
 }
 
-static int write_ctl(eslam_ctx* ctx)
+int eslam_host::write_ctl(eslam_ctx* ctx)
 {
     HIPCHK(ctx, hipMemcpyAsync(ctx->ctl, ctx->ctl_host, sizeof(Ctl), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -359,10 +364,6 @@ static void free_debug(eslam_ctx* ctx)
     ctx->dbg_cap = 0;
     ctx->dbg_valid = false;
 }
-
-static bool particle_maps(const eslam_ctx* ctx) { return (ctx->cfg.flags & ESLAM_FLAG_PARTICLE_MAPS) != 0; }
-
-static const LocalMaps* store_of(const eslam_ctx* ctx) { return particle_maps(ctx) ? &ctx->lm : nullptr; }
 
 static void free_local_maps(eslam_ctx* ctx)
 {
@@ -499,7 +500,7 @@ static void adopt_particle_set(eslam_ctx* ctx, ParticleSet& ps, uint64_t cap)
     ctx->cap = cap;
 }
 
-static int alloc_particles(eslam_ctx* ctx, uint64_t n)
+int eslam_host::alloc_particles(eslam_ctx* ctx, uint64_t n)
 {
     if (n >= (1ull << 32) - 1) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle count must be < 2^32 - 1");
     if (ctx->sharded && n != ctx->gall[ctx->comm.rank + 1] - ctx->gall[ctx->comm.rank])
@@ -523,7 +524,7 @@ static int alloc_particles(eslam_ctx* ctx, uint64_t n)
 // maxSensorRange (dm_lm_half of the cell size); a pool of 2 x cap tables and local_map_pages
 // pages per particle.  Runs at particle allocation and at set_map (the tables name cells of
 // the map, so a new map starts them over).
-static int local_maps_reset(eslam_ctx* ctx)
+int eslam_host::local_maps_reset(eslam_ctx* ctx)
 {
     free_local_maps(ctx);
     if (!particle_maps(ctx) || !ctx->has_map || !ctx->n) return ESLAM_OK;
@@ -670,7 +671,7 @@ extern "C" int eslam_gpu_set_map(eslam_ctx* ctx, const eslam_mls_grid* g)
     return local_maps_reset(ctx);
 }
 
-static int reset_ctl_for_new_particles(eslam_ctx* ctx, int wexp)
+int eslam_host::reset_ctl_for_new_particles(eslam_ctx* ctx, int wexp)
 {
     int rc = read_ctl(ctx);
     if (rc) return rc;
@@ -812,7 +813,7 @@ extern "C" int eslam_gpu_hash_create(eslam_ctx* ctx)
     return ESLAM_OK;
 }
 
-static const double* hash_field(eslam_ctx* ctx, int f)
+const double* eslam_host::hash_field(eslam_ctx* ctx, int f)
 {
     return ctx->d_hash + (uint64_t)f * (ctx->hash_n ? ctx->hash_n : 1);
 }
@@ -1168,11 +1169,8 @@ extern "C" int eslam_gpu_download_records(eslam_ctx* ctx, uint64_t first, uint64
     return ESLAM_OK;
 }
 
-// ---------------------------------------------------------------------------------------
-// per-particle local maps
-// ---------------------------------------------------------------------------------------
 // the map-update parameters every copy-on-write pass shares (the merge, a sharded receive)
-static MergeParams merge_params(eslam_ctx* ctx, const CowScratch& cs)
+MergeParams eslam_host::merge_params(eslam_ctx* ctx, const CowScratch& cs)
 {
     MergeParams mp;
     memset(&mp, 0, sizeof(mp));
@@ -1188,736 +1186,11 @@ static MergeParams merge_params(eslam_ctx* ctx, const CowScratch& cs)
     return mp;
 }
 
-extern "C" int eslam_gpu_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count)
-{
-    if (!ctx || (!patches && count)) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!particle_maps(ctx)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "map_update needs per-particle maps (ESLAM_FLAG_PARTICLE_MAPS)");
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (!ctx->lm_ready) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "per-particle maps not allocated");
-    for (uint32_t k = 0; k < count; ++k)
-        if (!dm_isfinite(patches[k].position[0]) || !dm_isfinite(patches[k].position[1]) ||
-            !dm_isfinite(patches[k].position[2]) || !dm_isfinite(patches[k].stdev))
-            return fail(ctx, ESLAM_ERR_INVALID_ARG, "map_update: scan patches must be finite");
-    mrec(ctx, 0);
-    // one GPU: a pending resample gather runs inside the merge (MergeParams::fuse: the store
-    // classes and the merge read the particles through the marks), so the update reads and
-    // writes the particle state once.  Sharded: the gather may hand this rank particles whose
-    // stores are still in received payloads, which get local stores first (materialize).
-    const bool fuse = !ctx->sharded;
-    const GatherView gv = gather_view(ctx);
-    if (!fuse) {
-        const int rc = materialize(ctx);
-        if (rc) return rc;
-    }
-    mrec(ctx, 1);
-    // the scan on the device: this update's slot is free once the update before last is done
-    const uint32_t slot = ctx->scan_slot ^= 1u;
-    if (!ctx->scan_ev[slot]) HIPCHK(ctx, ctx->scan_ev[slot].create(false));
-    else HIPCHK(ctx, hipEventSynchronize(ctx->scan_ev[slot]));
-    const uint64_t sbytes = (uint64_t)(count ? count : 1) * sizeof(ScanPatch);
-    int rc = grow(ctx, ctx->scan_host[slot], sbytes);
-    if (!rc) rc = grow(ctx, ctx->scan_dev[slot], sbytes);
-    // a scan of more than kScanPartSmall patches merges in parts of kScanPartLarge
-    const uint32_t part = count <= kScanPartSmall ? kScanPartSmall : kScanPartLarge;
-    if (!rc && part == kScanPartLarge) rc = grow(ctx, ctx->lmb.codes, ctx->cap * 2 * kScanPartLarge);
-    if (rc) return rc;
-    ScanPatch* sh = ctx->scan_host[slot];
-    for (uint32_t k = 0; k < count; ++k)
-        sh[k] = ScanPatch{patches[k].position[0], patches[k].position[1], patches[k].position[2], patches[k].stdev};
-    if (count) HIPCHK(ctx, hipMemcpyAsync(ctx->scan_dev[slot], sh, sbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the parts in order: every cell sees its patches in the scan's order; the parts' counters
-    // add up (map_stores_changed counts a map once per part that changed it)
-    for (uint32_t c0 = 0; c0 == 0 || c0 < count; c0 += part) {
-        const uint32_t cm = count - c0 < part ? count - c0 : part;
-        const SidRef sr{ctx->st[0].sid, ctx->st[1].sid, ctx->ctl};
-        const CowScratch cs = cow_layout(ctx->pt.cow, ctx->cap);
-        HIPCHK(ctx, eslam_launch_store_refs(sr, ctx->n, store_pool(ctx->cap), &cs, fuse ? &gv : nullptr, ctx->lm.tgen,
-                                            ctx->stream));
-        if (!c0) mrec(ctx, 2);
-        MergeParams mp = merge_params(ctx, cs);
-        mp.is_id = ctx->map.g2l_identity;
-        mp.gv = gv;                           // (the first part runs a pending gather; the device knows)
-        mp.gbase = ctx->gbase;
-        mp.fuse = fuse ? 1u : 0u;
-        mp.aux = (ctx->cfg.flags & ESLAM_FLAG_NO_AUX_GATHER) ? 0u : 1u;
-        mp.acc = c0 ? 1u : 0u;
-        mp.m = cm;
-        mp.sp = ctx->scan_dev[slot] + c0;
-        mp.codes = ctx->lmb.codes;
-        HIPCHK(ctx, eslam_launch_map_plan(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &ctx->lm, &mp, ctx->lmb.pgc, ctx->stream));
-        if (!c0) mrec(ctx, 3);
-        HIPCHK(ctx, eslam_launch_map_merge(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, &ctx->lm, &mp, ctx->stream));
-        if (fuse) {
-            HIPCHK(ctx, eslam_launch_commit(ctx->ctl, ctx->stream));     // the gather's buffer flip, if one ran
-        }
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->scan_ev[slot], ctx->stream));
-    mrec(ctx, 4);
-    return ESLAM_OK;
-}
-
-// processMap(scanMap, match = true, ...)  src/EmbodiedSlamFilter.cpp:214-221 (k_map_match)
-extern "C" int eslam_gpu_map_match(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count)
-{
-    if (!ctx || (!patches && count)) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (particle_maps(ctx) && !ctx->lm_ready) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "per-particle maps not allocated");
-    for (uint32_t k = 0; k < count; ++k)
-        if (!dm_isfinite(patches[k].position[0]) || !dm_isfinite(patches[k].position[1]) ||
-            !dm_isfinite(patches[k].position[2]) || !dm_isfinite(patches[k].stdev))
-            return fail(ctx, ESLAM_ERR_INVALID_ARG, "map_match: scan patches must be finite");
-    xrec(ctx, 0);
-    int rc = materialize(ctx);                // the weights of the particles as they stand
-    if (rc) return rc;
-    std::vector<ScanPatch> s;
-    for (uint32_t k = 0; k < count; k += kMatchSampling)
-        s.push_back(ScanPatch{patches[k].position[0], patches[k].position[1], patches[k].position[2], patches[k].stdev});
-    MatchParams mp;
-    mp.n = ctx->n;
-    mp.m = (uint32_t)s.size();
-    mp.is_id = ctx->map.g2l_identity;
-    mp.sp = nullptr;
-    const bool inline_sp = s.size() <= (size_t)kMaxScanPatches;   // the kernel arguments carry them
-    if (inline_sp) {
-        for (size_t k = 0; k < s.size(); ++k) mp.spi[k] = s[k];
-    } else {
-        rc = grow(ctx, ctx->lmb.match_sp, s.size() * sizeof(ScanPatch));
-        if (rc) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(ctx->lmb.match_sp, s.data(), s.size() * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
-        mp.sp = ctx->lmb.match_sp;
-    }
-    HIPCHK(ctx, eslam_launch_map_match(ctx->st[0], ctx->st[1], ctx->ctl, &ctx->map, store_of(ctx), &mp, ctx->stream));
-    xrec(ctx, 1);
-    // a scan of more than 640 patches: the host's copy of the sampled ones goes away on return
-    if (!inline_sp) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_set_particle_maps(eslam_ctx* ctx, int on)
-{
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    const bool cur = particle_maps(ctx);
-    if ((on != 0) == cur) return ESLAM_OK;
-    if (ctx->n) return fail(ctx, ESLAM_ERR_INVALID_ARG, "the map mode is chosen before the particles are initialised");
-    if (on) ctx->cfg.flags |= ESLAM_FLAG_PARTICLE_MAPS;
-    else ctx->cfg.flags &= ~ESLAM_FLAG_PARTICLE_MAPS;
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_get_particle_map(eslam_ctx* ctx, uint64_t index, uint32_t* cells, float* mean, float* stdev,
-                                          uint32_t capacity, uint32_t* count)
-{
-    if (!ctx || !count) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!particle_maps(ctx)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "no per-particle maps (ESLAM_FLAG_PARTICLE_MAPS)");
-    if (index >= ctx->n) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle index out of range");
-    int rc = materialize(ctx);
-    if (!rc) rc = read_ctl(ctx);
-    if (rc) return rc;
-    *count = 0;
-    if (!ctx->lm_ready) return ESLAM_OK;
-    const LocalMaps& lm = ctx->lm;
-    const uint32_t* sid = ctx->st[ctx->ctl_host->base ^ ctx->ctl_host->flip].sid;
-    uint32_t X = 0;
-    HIPCHK(ctx, hipMemcpy(&X, sid + index, 4, hipMemcpyDeviceToHost));
-    int2 c;
-    std::vector<uint32_t> sl(lm.S);
-    HIPCHK(ctx, hipMemcpy(&c, lm.ctr + X, sizeof(int2), hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(sl.data(), lm.slot + (uint64_t)X * lm.S, lm.S * 4, hipMemcpyDeviceToHost));
-    // the window's tiles in slot order, then the trail's in entry order, each tile's cells row
-    // by row (the oracle's or_get_particle_map)
-    uint32_t k = 0;
-    float2 cell[DM_LM_PAGE_CELLS];
-    const uint32_t W = lm.wx * lm.wy, toff = lm.S - 4u * lm.V;
-    const uint32_t hw = sl[toff - 1u] == DM_LM_NONE ? 0u : sl[toff - 1u];   // the trail's used entries
-    for (uint32_t s = 0; s < W + hw; ++s) {
-            const bool tr = s >= W;
-            const uint32_t pg = tr ? sl[toff + 4u * (s - W) + 2u] : sl[s];
-            if (pg == DM_LM_NONE) continue;
-            const int64_t a = tr ? (int64_t)(int32_t)sl[toff + 4u * (s - W)] : dm_lm_tile_of(s % lm.wx, c.x, lm.hx, lm.wx);
-            const int64_t b = tr ? (int64_t)(int32_t)sl[toff + 4u * (s - W) + 1u] : dm_lm_tile_of(s / lm.wx, c.y, lm.hy, lm.wy);
-            HIPCHK(ctx, hipMemcpy(cell, lm.page + (uint64_t)pg * DM_LM_PAGE_CELLS, sizeof(cell), hipMemcpyDeviceToHost));
-            for (uint32_t j = 0; j < DM_LM_PAGE_CELLS; ++j) {
-                if (!dm_lm_holds(cell[j].y)) continue;
-                if (k < capacity) {
-                    const uint64_t m = (uint64_t)(8 * a) + (j & 7u), n = (uint64_t)(8 * b) + (j >> 3);
-                    if (cells) cells[k] = (uint32_t)(n * ctx->map.width + m);
-                    if (mean) mean[k] = cell[j].x;
-                    if (stdev) stdev[k] = cell[j].y;
-                }
-                ++k;
-            }
-    }
-    *count = k;
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// the shared map: processMap's merge into the one grid (eslam_shared_map.hip)
-// ---------------------------------------------------------------------------------------
-// a second set of the grid's arrays with room for `cap` patches; false (nothing held) when
-// the device has no room
-static bool sm_alloc_grid(GridBufs* g, uint64_t ncell, uint64_t cap, bool heights)
-{
-    *g = GridBufs{};
-    const uint64_t c = cap ? cap : 1;
-    bool ok = g->cells.alloc((ncell + 1) * 4) == hipSuccess && g->patch.alloc(c * sizeof(float2)) == hipSuccess &&
-              g->occ.alloc(((ncell + 31) / 32) * 4) == hipSuccess && g->cell_tab.alloc(ncell * sizeof(uint4)) == hipSuccess;
-    if (ok && heights) ok = g->height.alloc(c * 4) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        *g = GridBufs{};
-    }
-    return ok;
-}
-
-// the run scratch for `rec` records and `ncell` cells, carved from one allocation the context keeps
-static int sm_scratch(eslam_ctx* ctx, uint64_t rec, uint64_t ncell, uint64_t scan_patches, SmScratch* s, ScanPatch** sp)
-{
-    const size_t sort_bytes = eslam_sm_sort_bytes(rec);
-    Carver size(nullptr);
-    carve_sm(size, rec, ncell, scan_patches, sort_bytes, s, sp);
-    const uint64_t total = size.bytes();
-    if (total > ctx->sm_mem.cap()) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->sm_mem.alloc(total) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the run scratch (lower max_records)");
-        }
-    }
-    Carver place(ctx->sm_mem.get());
-    carve_sm(place, rec, ncell, scan_patches, sort_bytes, s, sp);
-    return ESLAM_OK;
-}
-
-// ---- the merge on a sharded filter (eslam_gpu_shared_map_update_sharded): every rank merges
-// every run into its own copy of the grid, from the run's poses gathered in global order
-constexpr uint64_t kSmPoseBytes = kSmPoseWords * 8;
-
-// the pose records of the run's particles [i0, i0 + np) (global), in global order, into `recv`:
-// every rank stages its part of the run once per rank and the all_to_all_v hands every rank
-// every part, in rank order -- the shards are consecutive, so that is the run's order
-static int sm_exchange(eslam_ctx* ctx, uint64_t i0, uint64_t np, double* send, double* recv)
-{
-    const int G = ctx->comm.nranks, me = ctx->comm.rank;
-    uint64_t sb[kMaxRanks], rb[kMaxRanks], first = 0, mine = 0;
-    for (int r = 0; r < G; ++r) {
-        const uint64_t a = i0 > ctx->gall[r] ? i0 : ctx->gall[r];
-        const uint64_t b = i0 + np < ctx->gall[r + 1] ? i0 + np : ctx->gall[r + 1];
-        const uint64_t c = b > a ? b - a : 0;
-        rb[r] = c * kSmPoseBytes;
-        if (r == me) {
-            first = c ? a - ctx->gbase : 0;
-            mine = c;
-        }
-    }
-    for (int r = 0; r < G; ++r) sb[r] = mine * kSmPoseBytes;
-    if (mine) HIPCHK(ctx, eslam_launch_sm_stage(ctx->st[0], ctx->st[1], ctx->ctl, first, mine, (uint32_t)G, send, ctx->stream));
-    return comm_alltoallv(ctx, send, sb, recv, rb);
-}
-
-static uint64_t sm_patch_hash(const eslam_scan_patch* patches, uint32_t count)
-{
-    uint64_t h = 0xcbf29ce484222325ull;                        // FNV-1a over the patches' bytes
-    const unsigned char* p = reinterpret_cast<const unsigned char*>(patches);
-    for (uint64_t k = 0; k < (uint64_t)count * sizeof(eslam_scan_patch); ++k) h = (h ^ p[k]) * 0x100000001b3ull;
-    return h;
-}
-
-// both entry points.  collective: eslam_gpu_shared_map_update_sharded; on a sharded filter
-// (sh) the runs cover the global index range and read gathered poses.
-static int sm_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
-                     eslam_shared_merge_info* info, bool collective)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx || (!patches && count)) return ESLAM_ERR_INVALID_ARG;
-    if (particle_maps(ctx))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "shared_map_update: the filter has per-particle maps (eslam_gpu_map_update merges into those)");
-    for (uint32_t k = 0; k < count; ++k)
-        if (!dm_isfinite(patches[k].position[0]) || !dm_isfinite(patches[k].position[1]) ||
-            !dm_isfinite(patches[k].position[2]) || !dm_isfinite(patches[k].stdev))
-            return fail(ctx, ESLAM_ERR_INVALID_ARG, "shared_map_update: scan patches must be finite");
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (ctx->sharded && !collective)
-        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
-                    "shared_map_update: a sharded filter keeps a copy of the grid per rank; the merge in global particle "
-                    "order is the collective eslam_gpu_shared_map_update_sharded");
-    const bool sh = ctx->sharded;
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
-    if (sh) {
-        // every check above ran before the first collective; then the ranks must have been given
-        // the same call, or their grids would differ from here on
-        if (count && ncell >= 0xffffffffull)
-            return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
-        if (const int rc_ = settle(ctx)) return rc_;           // a deferred sharded exchange first
-        const uint64_t mine[3] = {count, max_records, sm_patch_hash(patches, count)};
-        uint64_t all[3 * kMaxRanks] = {};
-        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's buffer");
-        if (const int rc_ = host_allgather(ctx, mine, all, sizeof(mine))) return rc_;
-        for (int r = 0; r < ctx->comm.nranks; ++r)
-            if (memcmp(all + 3 * r, mine, sizeof(mine)) != 0)
-                return fail(ctx, ESLAM_ERR_INVALID_ARG,
-                            "shared_map_update_sharded: the ranks passed different scans or max_records; every rank must make "
-                            "the same call");
-    }
-    if (info) info->n_patches = ctx->map_np;
-    if (!count) return ESLAM_OK;
-    if (ncell >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "shared_map_update: the grid has 2^32 - 1 cells or more");
-    // a run: whole particles, at most max_records records, at least one particle
-    const uint64_t P = count, n = sh ? ctx->n_global : ctx->n;
-    uint64_t lim = max_records ? max_records : kSmDefaultRecords;
-    if (lim > (1ull << 31)) lim = 1ull << 31;                  // record indices are 32-bit
-    uint64_t per = lim / P;
-    per = per < 1 ? 1 : (per > n ? n : per);
-    SmScratch sc;
-    ScanPatch* d_sp = nullptr;
-    double *x_send = nullptr, *x_recv = nullptr;               // a sharded run's pose records, out and in
-    auto setup = [&]() -> int {
-        int rc = sm_scratch(ctx, per * P, ncell, P, &sc, &d_sp);
-        if (!rc && sh) {
-            // the staged copies (one per rank) and the gathered run
-            const uint64_t G = ctx->comm.nranks, out = (G * per * kSmPoseBytes + 255) & ~255ull;
-            hipError_t he_ = hipSuccess;
-            rc = ctx->sm_x.grow_keep(out + per * kSmPoseBytes, 1, ctx->stream, &he_);
-            if (rc == ESLAM_ERR_OUT_OF_MEMORY)
-                return fail(ctx, rc, "shared_map_update_sharded: no device memory for the exchange (lower max_records)");
-            if (rc) HIPCHK(ctx, he_);
-            x_send = reinterpret_cast<double*>(ctx->sm_x.as<char>());
-            x_recv = reinterpret_cast<double*>(ctx->sm_x.as<char>() + out);
-        }
-        if (!rc) rc = materialize(ctx);                       // the particles as they stand
-        if (rc) return rc;
-        static_assert(sizeof(ScanPatch) == sizeof(eslam_scan_patch), "scan patch layout");
-        HIPCHK(ctx, hipMemcpyAsync(d_sp, patches, P * sizeof(ScanPatch), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(sc.cnt, 0, kSmCounters * 8, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(sc.touched, 0, ncell * 4, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));       // `patches` is the caller's
-        return ESLAM_OK;
-    };
-    int rc = setup();
-    if (sh) rc = agree(ctx, rc, "shared_map_update_sharded");   // an allocation can fail on one rank only
-    if (rc) return rc;
-    GridBufs spare;
-    uint64_t spare_cap = 0;
-    uint64_t cnt[kSmCounters] = {};
-    uint64_t done = 0, runs = 0, placed_all = 0;
-    hipError_t he = hipSuccess;
-    // what k_sm_place / k_sm_apply read the poses from: the particles, or (SmRun::gath) the gathered run
-    DevState gathered = {};
-    gathered.x = x_recv;
-    const DevState a0 = sh ? gathered : ctx->st[0], a1 = sh ? gathered : ctx->st[1];
-    for (uint64_t i0 = 0; i0 < n && !rc; i0 += per) {
-        const uint64_t np = n - i0 < per ? n - i0 : per;
-        SmRun run = {};
-        run.i0 = sh ? 0 : i0;
-        run.P = count;
-        run.R = np * P;
-        run.ncell = (uint32_t)ncell;
-        run.is_id = ctx->map.g2l_identity;
-        run.sp = d_sp;
-        run.gath = sh ? 1u : 0u;
-        if (sh && (rc = sm_exchange(ctx, i0, np, x_send, x_recv)) != ESLAM_OK) break;
-        uint64_t placed = 0;
-        // the new arrays exist before anything of the grid changes: a run that finds no room
-        // leaves the grid as the runs before it made it
-        do {
-            if ((he = eslam_launch_sm_place(a0, a1, ctx->ctl, &ctx->map, &run, &sc, ctx->stream)) != hipSuccess) break;
-            if ((he = hipMemcpyAsync(&placed, sc.cnt + kSmRunPlaced, 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-            if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
-            if (!placed) break;
-            const uint64_t need = ctx->map_np + placed;
-            if (need > 0xffffffffull) {
-                rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: the grid would pass 2^32 - 1 patches");
-                break;
-            }
-            if (!spare.cells || spare_cap < need) {
-                uint64_t want = need + need / 4;
-                want = want > 0xffffffffull ? 0xffffffffull : want;
-                const bool h = ctx->grid.height != nullptr;
-                spare_cap = sm_alloc_grid(&spare, ncell, want, h) ? want : sm_alloc_grid(&spare, ncell, need, h) ? need : 0;
-                if (!spare_cap) rc = fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "shared_map_update: no device memory for the merged grid");
-            }
-        } while (0);
-        if (sh) {
-            // the ranks agree before any of them changes its grid (the apply fuses in place): after
-            // a failure every rank holds the grid of the same completed runs
-            if (he != hipSuccess) {
-                ctx->err = std::string("shared_map_update: ") + hipGetErrorString(he);
-                he = hipSuccess;
-                rc = ESLAM_ERR_HIP;
-            }
-            rc = agree(ctx, rc, "shared_map_update_sharded");
-        }
-        if (he != hipSuccess || rc) break;
-        if (placed) {
-            const SmGrid cur = ctx->grid.view(), next = spare.view();
-            if ((he = eslam_launch_sm_merge(a0, a1, ctx->ctl, &run, &cur, &next, &sc, ctx->stream)) != hipSuccess) break;
-            uint32_t total = 0;
-            if ((he = hipMemcpyAsync(&total, next.cell_start + ncell, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) break;
-            if ((he = hipStreamSynchronize(ctx->stream)) != hipSuccess) break;
-            // the swap: every later launch takes the grid from ctx->map (K1's window staging, the
-            // match, the hash build and get_map read these pointers at their call)
-            std::swap(ctx->grid, spare);                          // the next run rebuilds into the old arrays
-            std::swap(ctx->map_np_cap, spare_cap);
-            ctx->map_np = total;
-            ctx->map.cell_start = ctx->grid.cells; ctx->map.patch = ctx->grid.patch; ctx->map.height = ctx->grid.height;
-            ctx->map.occ = ctx->grid.occ; ctx->map.cell_tab = ctx->grid.cell_tab;
-        }
-        placed_all += placed;
-        done = i0 + np;
-        ++runs;
-    }
-    if (he == hipSuccess) he = hipMemcpy(cnt, sc.cnt, sizeof(cnt), hipMemcpyDeviceToHost);
-    spare = GridBufs{};                                          // (hipFree waits for the device)
-    if (info) {
-        info->particles_done = done;
-        info->patches_placed = placed_all;
-        info->patches_off_grid = done * P - placed_all;
-        info->cells_touched = cnt[kSmTouched];
-        info->fused = cnt[kSmFused];
-        info->absorbed = cnt[kSmAbsorbed];
-        info->inserted = cnt[kSmInserted];
-        info->n_patches = ctx->map_np;
-        info->runs = runs;
-    }
-    if (he != hipSuccess) {
-        ctx->err = std::string("shared_map_update: ") + hipGetErrorString(he);
-        return ESLAM_ERR_HIP;
-    }
-    return rc;
-}
-
-extern "C" int eslam_gpu_shared_map_update(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count, uint64_t max_records,
-                                           eslam_shared_merge_info* info)
-{
-    return sm_update(ctx, patches, count, max_records, info, false);
-}
-
-extern "C" int eslam_gpu_shared_map_update_sharded(eslam_ctx* ctx, const eslam_scan_patch* patches, uint32_t count,
-                                                   uint64_t max_records, eslam_shared_merge_info* info)
-{
-    return sm_update(ctx, patches, count, max_records, info, true);
-}
-
-extern "C" int eslam_gpu_map_size(eslam_ctx* ctx, uint32_t* width, uint32_t* height, uint64_t* n_patches, int* has_height)
-{
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    if (width) *width = ctx->map.width;
-    if (height) *height = ctx->map.height_cells;
-    if (n_patches) *n_patches = ctx->map_np;
-    if (has_height) *has_height = ctx->grid.height ? 1 : 0;
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_get_map(eslam_ctx* ctx, uint32_t* cell_start, float* mean, float* stdev, float* patch_height,
-                                 uint64_t patch_capacity)
-{
-    if (!ctx || !cell_start || ((!mean || !stdev) && patch_capacity)) return ESLAM_ERR_INVALID_ARG;
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    const uint64_t np = ctx->map_np, ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
-    if (patch_capacity < np) return fail(ctx, ESLAM_ERR_INVALID_ARG, "get_map: patch_capacity is below the grid's patch count (eslam_gpu_map_size)");
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(cell_start, ctx->grid.cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
-    if (!np) return ESLAM_OK;
-    std::vector<float2> patch(np);
-    HIPCHK(ctx, hipMemcpy(patch.data(), ctx->grid.patch, np * sizeof(float2), hipMemcpyDeviceToHost));
-    for (uint64_t k = 0; k < np; ++k) {
-        mean[k] = patch[k].x;
-        stdev[k] = patch[k].y;
-    }
-    if (patch_height) {
-        if (ctx->grid.height) HIPCHK(ctx, hipMemcpy(patch_height, ctx->grid.height, np * 4, hipMemcpyDeviceToHost));
-        else memset(patch_height, 0, np * 4);
-    }
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// a particle's whole map as one grid (kernels in eslam_particle_grid.hip)
-// ---------------------------------------------------------------------------------------
-// The checks of the three entry points, then the directory of particle index's table and the
-// composed counts (in *s): *total = the composed grid's patches.
-static int pgrid_count(eslam_ctx* ctx, uint64_t index, PgScratch* s, uint64_t* total)
-{
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!particle_maps(ctx)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "no per-particle maps (ESLAM_FLAG_PARTICLE_MAPS)");
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (index >= ctx->n) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle index out of range");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
-    if (ncell >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "particle_grid: the grid has 2^32 - 1 cells or more");
-    int rc = materialize(ctx);
-    if (!rc) rc = read_ctl(ctx);
-    if (rc) return rc;
-    if (!ctx->lm_ready) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "per-particle maps are not set up");
-    const size_t bytes = eslam_pgrid_work_bytes(ctx->map.width, ctx->map.height_cells, nullptr, nullptr);
-    if (bytes > ctx->pg_mem.cap() && ctx->pg_mem.alloc(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "particle_grid: no device memory for the scratch");
-    }
-    (void)eslam_pgrid_work_bytes(ctx->map.width, ctx->map.height_cells, ctx->pg_mem.get(), s);
-    const uint32_t* sid = ctx->st[ctx->ctl_host->base ^ ctx->ctl_host->flip].sid;
-    HIPCHK(ctx, eslam_launch_pgrid_count(&ctx->lm, sid + index, &ctx->map, s, ctx->stream));
-    uint64_t own = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&own, s->own, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *total = ctx->map_np + own;
-    if (*total > 0xffffffffull) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle_grid: the composed grid would pass 2^32 - 1 patches");
-    return ESLAM_OK;
-}
-
-// ... and the composed grid itself in ctx->pg_out, a second set of the grid's arrays that stays
-// with the context for the next export (allocating them cost more than composing into them);
-// a count above `capacity` (the caller's arrays) is refused first
-static int pgrid_compose(eslam_ctx* ctx, uint64_t index, uint64_t* total, uint64_t capacity)
-{
-    PgScratch s;
-    if (const int rc_ = pgrid_count(ctx, index, &s, total)) return rc_;
-    if (capacity < *total)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "get_particle_grid: patch_capacity is below the composed patch count (eslam_gpu_particle_grid_size)");
-    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
-    const bool h = ctx->grid.height != nullptr;
-    if (!ctx->pg_out.cells || ctx->pg_out_cells != ncell || ctx->pg_out_cap < *total || (ctx->pg_out.height != nullptr) != h) {
-        // room for the window and the trail full of patches, so other particles' exports fit too
-        uint64_t want = ctx->map_np + ((uint64_t)ctx->lm.wx * ctx->lm.wy + ctx->lm.V) * DM_LM_PAGE_CELLS;
-        want = want < *total ? *total : (want > 0xffffffffull ? 0xffffffffull : want);
-        ctx->pg_out_cells = ncell;
-        ctx->pg_out_cap = sm_alloc_grid(&ctx->pg_out, ncell, want, h) ? want : sm_alloc_grid(&ctx->pg_out, ncell, *total, h) ? *total : 0;
-        if (!ctx->pg_out.cells) {
-            ctx->pg_out_cap = ctx->pg_out_cells = 0;
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "particle_grid: no device memory for the composed grid");
-        }
-    }
-    const SmGrid cur = ctx->grid.view(), nw = ctx->pg_out.view();
-    HIPCHK(ctx, eslam_launch_pgrid_fill(&ctx->lm, &ctx->map, &s, &cur, &nw, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_particle_grid_size(eslam_ctx* ctx, uint64_t index, uint64_t* n_patches)
-{
-    if (!ctx || !n_patches) return ESLAM_ERR_INVALID_ARG;
-    PgScratch s;
-    return pgrid_count(ctx, index, &s, n_patches);
-}
-
-extern "C" int eslam_gpu_get_particle_grid(eslam_ctx* ctx, uint64_t index, uint32_t* cell_start, float* mean, float* stdev,
-                                           float* patch_height, uint64_t patch_capacity)
-{
-    if (!ctx || !cell_start || !mean || !stdev) return ESLAM_ERR_INVALID_ARG;
-    uint64_t np = 0;
-    if (const int rc_ = pgrid_compose(ctx, index, &np, patch_capacity)) return rc_;
-    const GridBufs& out = ctx->pg_out;
-    const uint64_t ncell = (uint64_t)ctx->map.width * ctx->map.height_cells;
-    HIPCHK(ctx, hipMemcpy(cell_start, out.cells, (ncell + 1) * 4, hipMemcpyDeviceToHost));
-    if (!np) return ESLAM_OK;
-    std::vector<float2> patch(np);
-    HIPCHK(ctx, hipMemcpy(patch.data(), out.patch, np * sizeof(float2), hipMemcpyDeviceToHost));
-    for (uint64_t k = 0; k < np; ++k) {
-        mean[k] = patch[k].x;
-        stdev[k] = patch[k].y;
-    }
-    if (patch_height) {
-        if (out.height) HIPCHK(ctx, hipMemcpy(patch_height, out.height, np * 4, hipMemcpyDeviceToHost));
-        else memset(patch_height, 0, np * 4);
-    }
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_adopt_particle_map(eslam_ctx* ctx, uint64_t index)
-{
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    // refused before any collective (settle is one)
-    if (ctx->sharded)
-        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
-                    "adopt_particle_map: a sharded filter keeps a copy of the grid per rank; export the map on the owning "
-                    "rank (eslam_gpu_get_particle_grid) and give it to every rank by eslam_gpu_set_map");
-    // the new arrays exist before anything changes
-    uint64_t np = 0;
-    if (const int rc_ = pgrid_compose(ctx, index, &np, ~0ull)) return rc_;
-    // as eslam_gpu_set_map: the grid's arrays, the view every later launch reads, no pose hash,
-    // and every particle's map starts over, empty (they name cells of the previous grid)
-    ctx->grid = std::move(ctx->pg_out);                          // (hipFree waits for the device)
-    ctx->pg_out = GridBufs{};
-    const uint64_t cap = ctx->pg_out_cap;
-    ctx->pg_out_cap = ctx->pg_out_cells = 0;
-    ctx->map.cell_start = ctx->grid.cells; ctx->map.patch = ctx->grid.patch; ctx->map.height = ctx->grid.height;
-    ctx->map.occ = ctx->grid.occ; ctx->map.cell_tab = ctx->grid.cell_tab;
-    ctx->map.has_height = ctx->grid.height ? 1u : 0u;
-    ctx->map_np = np;
-    ctx->map_np_cap = cap ? cap : 1;
-    ctx->has_hash = false;
-    return local_maps_reset(ctx);
-}
-
-// ---------------------------------------------------------------------------------------
-// the scan MLS from a sensor reading (kernels in eslam_scan.hip)
-// ---------------------------------------------------------------------------------------
-extern "C" int eslam_scan_params_default(const eslam_config* cfg, eslam_scan_params* p)
-{
-    if (!p) return ESLAM_ERR_INVALID_ARG;
-    memset(p, 0, sizeof(*p));
-    p->sensor2body[0] = p->sensor2body[5] = p->sensor2body[10] = 1.0;
-    p->orientation[0] = 1.0;
-    p->sensor_rot_sigma[0] = 5.0 / 180.0 * M_PI;       // scanAngleSigma  src/EmbodiedSlamFilter.cpp:281, 323
-    p->body_rot_sigma[0] = p->body_rot_sigma[1] = 3.0 / 180.0 * M_PI;   // pitchRollSigma  :290, 332
-    p->min_sigma = 1e-3;                               // :124
-    p->resolution = 0.05;                              // Configuration::gridResolution
-    p->patch_thickness = 0.1;                          // Configuration::gridPatchThickness
-    p->max_sensor_range = cfg ? cfg->max_sensor_range : 3.0;
-    return ESLAM_OK;
-}
-
-// the frame of a build from the caller's parameters (reach: see dm_scan_frame_init)
-static int scan_frame(eslam_ctx* ctx, const eslam_scan_params* p, double ray, dm_scan_frame* f)
-{
-    bool fin = true;
-    for (int i = 0; i < 12; ++i) fin = fin && dm_isfinite(p->sensor2body[i]);
-    for (int i = 0; i < 4; ++i) fin = fin && dm_isfinite(p->orientation[i]);
-    for (int i = 0; i < 3; ++i) fin = fin && dm_isfinite(p->sensor_rot_sigma[i]) && dm_isfinite(p->body_rot_sigma[i]);
-    fin = fin && dm_isfinite(p->min_sigma) && dm_isfinite(p->resolution) && dm_isfinite(p->patch_thickness) &&
-          dm_isfinite(p->max_sensor_range) && dm_isfinite(ray);
-    if (!fin) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: transforms, sigmas and sizes must be finite");
-    if (!(p->min_sigma > 0.0)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: min_sigma must be positive");
-    if (!(p->resolution > 0.0) || !(p->patch_thickness > 0.0) || !(p->max_sensor_range > 0.0))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: resolution, patch_thickness and max_sensor_range must be positive");
-    // R_w = removeYaw(orientation), as fill_step_params compensates the feet
-    double yc[4], Rw[9];
-    remove_yaw(p->orientation, yc);
-    q_to_mat(yc, Rw);
-    if (!dm_scan_frame_init(f, p->sensor2body, Rw, p->sensor_rot_sigma, p->body_rot_sigma, p->min_sigma, p->resolution,
-                            p->patch_thickness, p->max_sensor_range, p->max_sensor_range * ray))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan: the scan grid would pass 2^32 - 1 cells (resolution too fine for the range)");
-    return ESLAM_OK;
-}
-
-// a buffer of at least `bytes`: the new one exists before the old one goes, so a failed
-// allocation leaves the context with what it had
-template <typename B>
-static int scan_grow(eslam_ctx* ctx, B& buf, uint64_t bytes, uint64_t unit, const char* what)
-{
-    hipError_t he = hipSuccess;
-    const int rc = buf.grow_keep(bytes, unit, ctx->stream, &he);
-    if (rc == ESLAM_ERR_OUT_OF_MEMORY) return fail(ctx, rc, what);
-    HIPCHK(ctx, he);
-    return ESLAM_OK;
-}
-
-static int scan_build(eslam_ctx* ctx, const dm_scan_frame* f, ScanReading* rd, const void* host_raw, eslam_scan_info* info)
-{
-    const uint64_t n = rd->n;
-    ctx->scan_count = 0;
-    if (info) info->points = n;
-    if (!n) return ESLAM_OK;
-    const uint64_t need = eslam_scan_work_bytes(n, nullptr, nullptr);
-    if (const int rc_ = scan_grow(ctx, ctx->scan_mem, need, 1, "scan: no device memory for the build's scratch"))
-        return rc_;
-    ScanWork w;
-    (void)eslam_scan_work_bytes(n, ctx->scan_mem, &w);
-    HIPCHK(ctx, hipMemcpyAsync(w.raw, host_raw, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    rd->raw = w.raw;
-    HIPCHK(ctx, eslam_launch_scan_order(f, rd, &w, ctx->stream));
-    uint64_t cnt[kScanCounters] = {};
-    uint32_t nheads = 0, total = 0;
-    HIPCHK(ctx, hipMemcpyAsync(cnt, w.cnt, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&nheads, w.b + n, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `host_raw` is the caller's
-    const uint64_t binned = n - cnt[kScanInvalid] - cnt[kScanOutOfRange];
-    if (info) {
-        info->points_valid = binned;
-        info->points_invalid = cnt[kScanInvalid];
-        info->points_out_of_range = cnt[kScanOutOfRange];
-        info->cells = nheads;
-    }
-    if (!nheads) return ESLAM_OK;
-    HIPCHK(ctx, eslam_launch_scan_count(f, &w, nheads, (uint32_t)binned, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&total, w.a + nheads, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (const int rc_ = scan_grow(ctx, ctx->scan_out, (uint64_t)total * sizeof(eslam_scan_patch),
-                                  sizeof(eslam_scan_patch), "scan: no device memory for the patches"))
-        return rc_;
-    HIPCHK(ctx, eslam_launch_scan_emit(f, &w, nheads, (uint32_t)binned, ctx->scan_out, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scan_count = total;
-    if (info) info->patches = total;
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_scan_from_laser(eslam_ctx* ctx, const eslam_laser_scan* scan, const eslam_scan_params* params,
-                                         eslam_scan_info* info)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (!scan || !params || (scan->n && !scan->ranges)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: null argument");
-    if (!dm_isfinite(scan->start_angle) || !dm_isfinite(scan->angular_resolution))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: the angles must be finite");
-    if (scan->n > kScanMaxPoints) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_laser: more than 2^30 beams");
-    dm_scan_frame f;
-    if (const int rc_ = scan_frame(ctx, params, 1.0, &f)) return rc_;
-    ScanReading rd = {};
-    rd.depth = 0;
-    rd.n = scan->n;
-    rd.start_angle = scan->start_angle;
-    rd.angular_resolution = scan->angular_resolution;
-    rd.min_range = scan->min_range;
-    rd.max_range = scan->max_range;
-    rd.width = 1;
-    return scan_build(ctx, &f, &rd, scan->ranges, info);
-}
-
-extern "C" int eslam_gpu_scan_from_depth(eslam_ctx* ctx, const eslam_depth_image* image, const eslam_scan_params* params,
-                                         eslam_scan_info* info)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (!image || !params || !image->data) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: null argument");
-    if (!image->width || !image->height) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: a zero-size image");
-    if ((uint64_t)image->width * image->height > kScanMaxPoints)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: more than 2^30 pixels");
-    if (!dm_isfinite(image->scale_x) || !dm_isfinite(image->scale_y) || !dm_isfinite(image->center_x) ||
-        !dm_isfinite(image->center_y))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_from_depth: the image's scales and centres must be finite");
-    dm_scan_frame f;
-    const double ray = dm_scan_depth_ray(image->width, image->height, image->scale_x, image->scale_y, image->center_x,
-                                         image->center_y);
-    if (const int rc_ = scan_frame(ctx, params, ray, &f)) return rc_;
-    ScanReading rd = {};
-    rd.depth = 1;
-    rd.n = image->width * image->height;
-    rd.width = image->width;
-    rd.sx = image->scale_x; rd.sy = image->scale_y; rd.cx = image->center_x; rd.cy = image->center_y;
-    return scan_build(ctx, &f, &rd, image->data, info);
-}
-
-extern "C" int eslam_gpu_scan_patches(eslam_ctx* ctx, eslam_scan_patch* out, uint64_t capacity, uint64_t* count)
-{
-    if (!ctx) return ESLAM_ERR_INVALID_ARG;
-    if (!count || (!out && capacity)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "scan_patches: null argument");
-    *count = ctx->scan_count;
-    const uint64_t m = capacity < ctx->scan_count ? capacity : ctx->scan_count;
-    if (m) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMemcpy(out, ctx->scan_out, m * sizeof(eslam_scan_patch), hipMemcpyDeviceToHost));
-    }
-    return ESLAM_OK;
-}
-
 // ---------------------------------------------------------------------------------------
 // the hot path
 // ---------------------------------------------------------------------------------------
 // the pending resample gather (consumed by the next k_project_weight or materialised)
-static GatherView gather_view(eslam_ctx* ctx)
+GatherView eslam_host::gather_view(eslam_ctx* ctx)
 {
     GatherView gv;
     memset(&gv, 0, sizeof(gv));
@@ -1951,7 +1224,7 @@ static int store_receive(eslam_ctx* ctx)
     return ESLAM_OK;
 }
 
-static int materialize(eslam_ctx* ctx)
+int eslam_host::materialize(eslam_ctx* ctx)
 {
     if (!ctx->n) return ESLAM_OK;
     const GatherView gv = gather_view(ctx);
@@ -2763,7 +2036,7 @@ extern "C" int eslam_gpu_resample(eslam_ctx* ctx)
 // cumulative sum is written out, every draw searches its ancestor, and the gather runs at once
 // into the other state buffer, or, beyond the capacity, into a new particle set allocated before
 // anything changes.
-static int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
+int eslam_host::resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
 {
     if (info) memset(info, 0, sizeof(*info));
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
@@ -2878,7 +2151,7 @@ extern "C" int eslam_gpu_resample_multinomial(eslam_ctx* ctx, uint64_t samples, 
 // all_gathers carry the ranks' status too (~0 for a rank that could not allocate), so a
 // rank-local failure ends the call on every rank before anything has changed.  Nothing of the
 // filter changes before the commit at the end: the minstd state included.
-static int resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
+int eslam_host::resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info)
 {
     if (!ctx) {
         if (info) memset(info, 0, sizeof(*info));
@@ -3062,595 +2335,6 @@ extern "C" int eslam_gpu_resample_multinomial_sharded(eslam_ctx* ctx, uint64_t s
     return resample_sharded(ctx, samples, true, info);
 }
 
-extern "C" int eslam_gpu_get_best_particle_index(eslam_ctx* ctx, uint64_t* index)
-{
-    if (!ctx || !index) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    if (!ctx->n) { *index = 0; return ESLAM_OK; }
-    if (const int rc0 = materialize(ctx)) return rc0;
-    uint64_t* out = ctx->scratch.as<uint64_t>();
-    HIPCHK(ctx, eslam_launch_best_index(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, out, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->scratch, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t* h = ctx->scratch_host.as<const uint64_t>();
-    if (!ctx->sharded) {
-        *index = h[1] == ~0ull ? 0 : h[1];
-        return ESLAM_OK;
-    }
-    // sharded: the first global maximum = the lowest rank holding the largest key
-    uint64_t* m = ctx->mg_host;
-    m[mg::kBest] = h[0];
-    m[mg::kBest + 1] = h[1] == ~0ull ? ~0ull : ctx->gbase + h[1];
-    HIPCHK(ctx, hipMemcpy(ctx->mg + mg::kBest, &m[mg::kBest], 16, hipMemcpyHostToDevice));
-    const int rc = comm_allgather(ctx, ctx->mg + mg::kBest, ctx->mg + mg::kBestAll, 16);
-    if (rc) return rc;
-    HIPCHK(ctx, hipMemcpy(&m[mg::kBestAll], ctx->mg + mg::kBestAll, 16ull * ctx->comm.nranks, hipMemcpyDeviceToHost));
-    uint64_t best = 0, idx = ~0ull;
-    for (int r = 0; r < ctx->comm.nranks; ++r) {
-        const uint64_t k = m[mg::kBestAll + 2 * r], i = m[mg::kBestAll + 2 * r + 1];
-        if (i == ~0ull) continue;
-        if (idx == ~0ull || k > best) { best = k; idx = i; }
-    }
-    *index = idx == ~0ull ? 0 : idx;
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_get_centroid(eslam_ctx* ctx, double position[3], double orientation[4])
-{
-    if (!ctx || !position || !orientation) return ESLAM_ERR_INVALID_ARG;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    int rc = eslam_gpu_normalize_weights(ctx, nullptr);     // side effect, Q15
-    if (rc) return rc;
-    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
-    if (!ctx->sharded) {
-        // the chunk records and the tree's second level, in the context's own buffer
-        const uint64_t csz = 64ull * J, chunks = (ctx->n + csz - 1) / csz;
-        rc = grow(ctx, ctx->cent, 2 * (chunks ? chunks : 1) * 5 * sizeof(double));
-        if (rc) return rc;
-        HIPCHK(ctx, eslam_launch_centroid(ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, ctx->cent, ctx->scratch, ctx->stream));
-    } else {
-        // the shards are chunk-aligned: every rank's chunk records, all-gathered (padded to
-        // the largest shard) and laid out in global chunk order, feed the same fixed tree
-        // as on one GPU, so every rank computes the one-GPU centroid bit for bit
-        rc = materialize(ctx);
-        if (rc) return rc;
-        const int G = ctx->comm.nranks;
-        const uint64_t csz = 64ull * J;
-        std::vector<uint64_t> nch(G);
-        uint64_t maxch = 1, total = 0;
-        for (int r = 0; r < G; ++r) {
-            nch[r] = (ctx->gall[r + 1] - ctx->gall[r] + csz - 1) / csz;
-            maxch = nch[r] > maxch ? nch[r] : maxch;
-            total += nch[r];
-        }
-        const uint64_t rec = 5 * sizeof(double);
-        if (centroid_bytes(ctx->gall.data(), G, J) > ctx->cent.cap())
-            return fail(ctx, ESLAM_ERR_HIP, "getCentroid: buffer not sized by set_comm");
-        double* mine = ctx->cent;
-        double* all = mine + maxch * 5;
-        double* a = all + G * maxch * 5;
-        double* b = a + (total ? total : 1) * 5;
-        hipError_t e = hipMemsetAsync(mine, 0, maxch * rec, ctx->stream);
-        if (e == hipSuccess) e = eslam_launch_centroid_chunks(ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, mine, ctx->stream);
-        if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
-        rc = comm_allgather(ctx, mine, all, maxch * rec);
-        if (rc) return rc;
-        uint64_t off = 0;
-        for (int r = 0; r < G && e == hipSuccess; ++r) {
-            if (nch[r]) e = hipMemcpyAsync(a + off * 5, all + (uint64_t)r * maxch * 5, nch[r] * rec, hipMemcpyDeviceToDevice,
-                                           ctx->stream);
-            off += nch[r];
-        }
-        if (e == hipSuccess) e = eslam_launch_centroid_tree(a, b, total, ctx->scratch, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->scratch, 5 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const double* h = ctx->scratch_host;       // sum x w, y w, theta w, z w, w
-    const double sw = h[4];
-    position[0] = h[0] / sw;
-    position[1] = h[1] / sw;
-    position[2] = h[3] / sw;
-    const double mo = h[2] / sw;
-    double a[4];
-    q_from_yaw(mo, a);
-    q_mul(a, ctx->zcomp, orientation);
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_get_z_compensated_orientation(eslam_ctx* ctx, double orientation[4])
-{
-    if (!ctx || !orientation) return ESLAM_ERR_INVALID_ARG;
-    memcpy(orientation, ctx->zcomp, sizeof(ctx->zcomp));
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// PoseDistribution::gmm: the 2-D Gaussian mixture over (x, y), fitted on the device
-// ---------------------------------------------------------------------------------------
-extern "C" void eslam_gmm_params_default(eslam_gmm_params* p)
-{
-    if (!p) return;
-    p->components = 3;
-    p->max_iterations = 10;
-    p->tolerance = 1e-5;
-    p->min_variance = 1e-6;
-}
-
-namespace {
-// the fit's arrays within ctx->gmm: pass B's words (sharded: then every rank's), this rank's chunk
-// records padded to the largest shard and all ranks' (sharded only), and the tree's two levels
-// over the global chunks
-struct GmmBufs {
-    uint64_t* words;
-    uint64_t* words_all;
-    uint64_t* part;                      // pass B: every wave's words
-    double* mine;
-    double* all;
-    double* a;
-    double* b;
-    uint64_t maxch = 1, total = 0;
-    std::vector<uint64_t> nch;
-};
-
-uint64_t gmm_carve(const eslam_ctx* ctx, uint32_t R, uint32_t J, void* base, GmmBufs* g)
-{
-    const int G = ctx->sharded ? ctx->comm.nranks : 1;
-    const uint64_t csz = 64ull * J;
-    g->nch.assign(G, 0);
-    g->maxch = 1;
-    g->total = 0;
-    for (int r = 0; r < G; ++r) {
-        const uint64_t n = ctx->sharded ? ctx->gall[r + 1] - ctx->gall[r] : ctx->n;
-        g->nch[r] = (n + csz - 1) / csz;
-        g->maxch = g->nch[r] > g->maxch ? g->nch[r] : g->maxch;
-        g->total += g->nch[r];
-    }
-    Carver c(base);
-    g->words = c.take<uint64_t>(kGmmWords);
-    g->words_all = c.take<uint64_t>((uint64_t)kGmmWords * G);
-    g->part = c.take<uint64_t>((uint64_t)kGmmBoundsBlocks * kWaves * kGmmWords);
-    g->mine = c.take<double>(ctx->sharded ? g->maxch * R : 0);
-    g->all = c.take<double>(ctx->sharded ? (uint64_t)G * g->maxch * R : 0);
-    g->a = c.take<double>((g->total ? g->total : 1) * R);
-    g->b = c.take<double>((g->total ? g->total : 1) * R);
-    return c.bytes();
-}
-
-// one pass of R sums per chunk: `launch(dst)` leaves the chunk records of this context at dst
-// (sharded: those of every rank are then all-gathered into global chunk order), then the one-GPU
-// tree; rec = the pass' R sums
-template <typename Launch>
-int chunk_pass(eslam_ctx* ctx, uint32_t R, const GmmBufs& g, double* rec, Launch launch)
-{
-    hipError_t e = hipSuccess;
-    if (!ctx->sharded) {
-        e = launch(g.a);
-    } else {
-        e = hipMemsetAsync(g.mine, 0, g.maxch * R * sizeof(double), ctx->stream);
-        if (e == hipSuccess) e = launch(g.mine);
-        if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
-        const int rc = comm_allgather(ctx, g.mine, g.all, g.maxch * R * sizeof(double));
-        if (rc) return rc;
-        uint64_t off = 0;
-        for (int r = 0; r < ctx->comm.nranks && e == hipSuccess; ++r) {
-            if (g.nch[r]) e = hipMemcpyAsync(g.a + off * R, g.all + (uint64_t)r * g.maxch * R, g.nch[r] * R * sizeof(double),
-                                             hipMemcpyDeviceToDevice, ctx->stream);
-            off += g.nch[r];
-        }
-    }
-    if (e == hipSuccess) e = eslam_launch_gmm_tree(g.a, g.b, g.total, R, ctx->scratch_host, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
-    memcpy(rec, ctx->scratch_host.get(), R * sizeof(double));
-    return ESLAM_OK;
-}
-
-// a pass of the mixture's fit; rec = its DM_GMM_REC(K) sums
-int gmm_pass(eslam_ctx* ctx, int K, bool hard, const GmmPass& P, uint32_t J, const GmmBufs& g, double* rec)
-{
-    return chunk_pass(ctx, DM_GMM_REC(K), g, rec, [&](double* dst) {
-        return eslam_launch_gmm_pass(K, hard, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
-    });
-}
-}  // namespace
-
-extern "C" int eslam_gpu_fit_pose_gmm(eslam_ctx* ctx, const eslam_gmm_params* params, eslam_gmm_component* out,
-                                      eslam_gmm_info* info)
-{
-    if (!ctx || !params || !out) return ESLAM_ERR_INVALID_ARG;
-    if (params->components < 1 || params->components > ESLAM_GMM_MAX_COMPONENTS)
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: components must be in [1, 8]");
-    if (!(params->tolerance >= 0.0)) return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: tolerance must not be negative or NaN");
-    if (!dm_isfinite(params->min_variance) || !(params->min_variance > 0.0))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: min_variance must be finite and positive");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    const int K = (int)params->components;
-    const uint32_t R = DM_GMM_REC(K);
-    static_assert(DM_GMM_MAX == ESLAM_GMM_MAX_COMPONENTS, "component limit");
-    static_assert((kMaxRanks + 1) * kGmmWords * 8 <= 4096 && DM_GMM_REC(DM_GMM_MAX) * 8 <= 4096, "scratch_host holds a readback");
-    if (ctx->sharded) {
-        // the ranks' parameters, compared before anything depends on them
-        uint64_t mine[3], all[3 * kMaxRanks];
-        mine[0] = (uint64_t)params->components | (uint64_t)params->max_iterations << 32;
-        mine[1] = dm_bits(params->tolerance);
-        mine[2] = dm_bits(params->min_variance);
-        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's words");
-        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
-        if (rc) return rc;
-        for (int r = 0; r < ctx->comm.nranks; ++r)
-            if (memcmp(&all[3 * r], mine, sizeof(mine)) != 0)
-                return fail(ctx, ESLAM_ERR_INVALID_ARG, "fit_pose_gmm: the ranks' parameters differ");
-    }
-    int rc = materialize(ctx);                       // the particles as they stand
-    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
-    GmmBufs g;
-    if (!rc) rc = grow(ctx, ctx->gmm, gmm_carve(ctx, R, J, nullptr, &g));
-    // sharded: a rank whose gather or allocation failed must not leave the others in the passes'
-    // collectives (a failure inside a pass is a HIP or transport error no rank recovers from)
-    rc = agree(ctx, rc, "fit_pose_gmm");
-    if (rc) return rc;
-    gmm_carve(ctx, R, J, ctx->gmm.get(), &g);
-
-    // pass B: order-free words, reduced over the ranks identically everywhere
-    const int G = ctx->sharded ? ctx->comm.nranks : 1;
-    HIPCHK(ctx, eslam_launch_gmm_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, g.part, g.words, ctx->stream));
-    if (ctx->sharded) {
-        rc = comm_allgather(ctx, g.words, g.words_all, kGmmWords * sizeof(uint64_t));
-        if (rc) return rc;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->sharded ? g.words_all : g.words, (uint64_t)G * kGmmWords * sizeof(uint64_t),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t B[kGmmWords] = {};
-    for (int r = 0; r < G; ++r) {
-        const uint64_t* w = ctx->scratch_host.as<const uint64_t>() + (uint64_t)r * kGmmWords;
-        for (int q = kGmmMaxW; q <= kGmmMaxY; ++q) B[q] = B[q] > w[q] ? B[q] : w[q];
-        B[kGmmUsed] += w[kGmmUsed];
-        B[kGmmSkipped] += w[kGmmSkipped];
-    }
-
-    const double nan_ = dm_from_bits(0x7ff8000000000000ull);
-    dm_gmm_comp comp[DM_GMM_MAX];
-    memset(comp, 0, sizeof(comp));
-    memset(out, 0, sizeof(eslam_gmm_component) * K);
-    eslam_gmm_info inf;
-    memset(&inf, 0, sizeof(inf));
-    inf.particles_used = B[kGmmUsed];
-    inf.particles_skipped = B[kGmmSkipped];
-    if (!B[kGmmUsed]) {                              // no fitted particle: everything zero
-        if (info) *info = inf;
-        return ESLAM_OK;
-    }
-    GmmPass P;
-    memset(&P, 0, sizeof(P));
-    const double xmin = gmm_unkey(~B[kGmmMinX]), xmax = gmm_unkey(B[kGmmMaxX]);
-    const double ymin = gmm_unkey(~B[kGmmMinY]), ymax = gmm_unkey(B[kGmmMaxY]);
-    P.E = dm_stat_exp(gmm_unkey(B[kGmmMaxW]));
-    P.cx = 0.5 * xmin + 0.5 * xmax;
-    P.cy = 0.5 * ymin + 0.5 * ymax;
-    P.axis = (xmax - xmin) >= (ymax - ymin) ? 0 : 1;
-    P.amin = P.axis ? ymin : xmin;
-    P.h = ((P.axis ? ymax : xmax) - P.amin) / (double)K;
-
-    // pass 0: the hard assignment; then the fused E+M passes
-    double rec[DM_GMM_REC(DM_GMM_MAX)];
-    rc = gmm_pass(ctx, K, true, P, J, g, rec);
-    if (rc) return rc;
-    for (int k = 0; k < K; ++k) comp[k].live = 1;
-    int nlive = dm_gmm_mstep(rec, K, params->min_variance, comp);
-    double L = nan_, Lprev = nan_;
-    for (uint32_t t = 1; t <= params->max_iterations && nlive > 0; ++t) {
-        memcpy(P.c, comp, sizeof(comp));
-        rc = gmm_pass(ctx, K, false, P, J, g, rec);
-        if (rc) return rc;
-        L = rec[6 * K + 1] / rec[6 * K];
-        nlive = dm_gmm_mstep(rec, K, params->min_variance, comp);
-        inf.iterations = t;
-        if (t >= 2 && dm_fabs(L - Lprev) <= params->tolerance) { inf.converged = 1; break; }
-        Lprev = L;
-    }
-    for (int k = 0; k < K; ++k) {
-        if (!comp[k].set) continue;
-        out[k].weight = comp[k].weight;
-        out[k].mean[0] = comp[k].mx + P.cx;
-        out[k].mean[1] = comp[k].my + P.cy;
-        out[k].cov[0] = comp[k].cxx;
-        out[k].cov[1] = comp[k].cxy;
-        out[k].cov[2] = comp[k].cyy;
-    }
-    inf.components_live = (uint32_t)nlive;
-    for (int k = 0; k < K; ++k) inf.live_mask |= comp[k].live ? 1u << k : 0u;
-    inf.log_likelihood = L;
-    inf.centre[0] = P.cx;
-    inf.centre[1] = P.cy;
-    inf.weight_exp = P.E;
-    if (info) *info = inf;
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// the pose estimate with its 4 x 4 covariance over (x, y, z, yaw), summed on the device
-// ---------------------------------------------------------------------------------------
-extern "C" int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gate, eslam_pose_moments* out)
-{
-    if (!ctx || !out) return ESLAM_ERR_INVALID_ARG;
-    MomPass P;
-    memset(&P, 0, sizeof(P));
-    if (gate && !dm_mom_gate_set(&P.g, gate->centre, gate->cov, gate->chi2))
-        return fail(ctx, ESLAM_ERR_INVALID_ARG,
-                    "pose_moments: the gate needs a finite centre, xx > 0, a finite determinant > 0 and a finite chi2 >= 0");
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    static_assert((kMaxRanks + 1) * kMomWords * 8 <= 4096 && DM_MOM_REC2 * 8 <= 4096, "scratch_host holds a readback");
-    static_assert(kMomWords <= kGmmWords && kMomBoundsBlocks <= kGmmBoundsBlocks, "gmm_carve's pass B arrays hold the moments'");
-    if (ctx->sharded) {
-        // the ranks' gates, compared before anything depends on them: the six doubles' bits, all
-        // ones without a gate (no accepted gate has them: its values are finite)
-        uint64_t mine[6], all[6 * kMaxRanks];
-        memset(mine, 0xff, sizeof(mine));
-        if (gate) memcpy(mine, gate, sizeof(mine));
-        static_assert(sizeof(eslam_pose_gate) == sizeof(mine) && sizeof(mine) <= kHostXBytes, "host_allgather's words");
-        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
-        if (rc) return rc;
-        for (int r = 0; r < ctx->comm.nranks; ++r)
-            if (memcmp(&all[6 * r], mine, sizeof(mine)) != 0)
-                return fail(ctx, ESLAM_ERR_INVALID_ARG, "pose_moments: the ranks' gates differ");
-    }
-    int rc = materialize(ctx);                       // the particles as they stand
-    const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
-    GmmBufs g;                                       // the fit's layout at the wider record
-    if (!rc) rc = grow(ctx, ctx->moments, gmm_carve(ctx, DM_MOM_REC2, J, nullptr, &g));
-    rc = agree(ctx, rc, "pose_moments");             // no rank is left alone in the collectives below
-    if (rc) return rc;
-    gmm_carve(ctx, DM_MOM_REC2, J, ctx->moments.get(), &g);
-
-    // pass B: order-free words, reduced over the ranks identically everywhere
-    const int G = ctx->sharded ? ctx->comm.nranks : 1;
-    HIPCHK(ctx, eslam_launch_moments_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, &P, g.part, g.words, ctx->stream));
-    if (ctx->sharded) {
-        rc = comm_allgather(ctx, g.words, g.words_all, kMomWords * sizeof(uint64_t));
-        if (rc) return rc;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ctx->sharded ? g.words_all : g.words, (uint64_t)G * kMomWords * sizeof(uint64_t),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t B[kMomWords] = {};
-    for (int r = 0; r < G; ++r) {
-        const uint64_t* w = ctx->scratch_host.as<const uint64_t>() + (uint64_t)r * kMomWords;
-        B[kMomMaxW] = B[kMomMaxW] > w[kMomMaxW] ? B[kMomMaxW] : w[kMomMaxW];
-        for (int q = kMomCounted; q <= kMomSkipped; ++q) B[q] += w[q];
-    }
-    eslam_pose_moments m;
-    memset(&m, 0, sizeof(m));
-    m.particles_counted = B[kMomCounted];
-    m.particles_gated_out = B[kMomGatedOut];
-    m.particles_skipped = B[kMomSkipped];
-    if (B[kMomCounted] + B[kMomGatedOut]) m.weight_exp = P.E = dm_stat_exp(gmm_unkey(B[kMomMaxW]));
-    if (!B[kMomCounted]) {                           // no counted particle: the counts, every double zero
-        *out = m;
-        return ESLAM_OK;
-    }
-    auto pass = [&](int which, uint32_t R, double* rec) {
-        return chunk_pass(ctx, R, g, rec, [&](double* dst) {
-            return eslam_launch_moments_pass(which, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
-        });
-    };
-    double rec[DM_MOM_REC2], q[4];
-    rc = pass(1, DM_MOM_REC1, rec);
-    if (rc) return rc;
-    dm_mom_mean(rec, P.mean, q);
-    rc = pass(2, DM_MOM_REC2, rec);
-    if (rc) return rc;
-    memcpy(m.mean, P.mean, sizeof(m.mean));
-    dm_mom_cov(rec, m.cov);
-    m.yaw_resultant = q[0];
-    m.effective = q[1];
-    m.weight_share = q[2];
-    m.z_within = q[3];
-    *out = m;
-    return ESLAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// KLD-sampling: the occupied bins of the pose lattice, counted on the device, and the particle
-// count they ask for
-// ---------------------------------------------------------------------------------------
-extern "C" void eslam_kld_params_default(const eslam_config* cfg, eslam_kld_params* p)
-{
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->bin_xy = 0.1;
-    p->theta_bins = 36;
-    p->epsilon = 0.05;
-    p->z_quantile = 2.3263478740408408;
-    p->n_min = cfg && cfg->particle_count ? cfg->particle_count : 1;
-}
-
-namespace {
-// what is wrong with the parameters, or null
-const char* kld_refusal(const eslam_kld_params* p)
-{
-    if (!dm_isfinite(p->bin_xy) || !(p->bin_xy > 0.0)) return "kld: bin_xy must be finite and positive";
-    if (p->theta_bins < 1 || p->theta_bins > 4096) return "kld: theta_bins must be in [1, 4096]";
-    if (p->multinomial > 1) return "kld: multinomial must be 0 or 1";
-    if (!dm_isfinite(p->epsilon) || !(p->epsilon > 0.0)) return "kld: epsilon must be finite and positive";
-    if (!dm_isfinite(p->z_quantile) || !(p->z_quantile >= 0.0)) return "kld: z_quantile must be finite and not negative";
-    if (p->n_min == 0) return "kld: n_min must be at least 1";
-    if (p->n_max != 0 && p->n_max < p->n_min) return "kld: n_max must be 0 or at least n_min";
-    if (!(p->min_change >= 0.0)) return "kld: min_change must not be negative or NaN";
-    return nullptr;
-}
-
-uint64_t kld_mix(uint64_t a, uint64_t b)
-{
-    uint64_t h = (a ^ (a >> 31)) * 0x9e3779b97f4a7c15ull;
-    h = ((h ^ (h >> 29)) + b) * 0xbf58476d1ce4e5b9ull;
-    return h ^ (h >> 32);
-}
-
-// min / max / sum of record b into a
-void kld_fold(int64_t* a, const int64_t* b)
-{
-    a[kKldIx0] = a[kKldIx0] < b[kKldIx0] ? a[kKldIx0] : b[kKldIx0];
-    a[kKldIx1] = a[kKldIx1] > b[kKldIx1] ? a[kKldIx1] : b[kKldIx1];
-    a[kKldIy0] = a[kKldIy0] < b[kKldIy0] ? a[kKldIy0] : b[kKldIy0];
-    a[kKldIy1] = a[kKldIy1] > b[kKldIy1] ? a[kKldIy1] : b[kKldIy1];
-    a[kKldCounted] += b[kKldCounted];
-    a[kKldSkipped] += b[kKldSkipped];
-}
-
-// ctx->kld of at least the layout's bytes (the new block exists before the old one goes)
-int kld_reserve(eslam_ctx* ctx, uint64_t words, uint64_t gather)
-{
-    KldScratch ks;
-    Carver size(nullptr);
-    carve_kld(size, words, gather, &ks);
-    hipError_t he = hipSuccess;
-    const int rc = ctx->kld.grow_keep(size.bytes(), 1, ctx->stream, &he);
-    if (rc == ESLAM_ERR_HIP) return fail(ctx, rc, hipGetErrorString(he));
-    if (rc) return fail(ctx, rc, "kld_count: no device memory for the bitmap");
-    return ESLAM_OK;
-}
-
-// the count itself; params checked, info zeroed
-int kld_count(eslam_ctx* ctx, const eslam_kld_params* p, eslam_kld_info* info)
-{
-    if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    const int G = ctx->sharded ? ctx->comm.nranks : 1;
-    static_assert(kKldWords * 8 <= kHostXBytes, "host_allgather's words");
-    if (ctx->sharded) {
-        // the ranks' parameters, compared before anything depends on them.  Six words: what shapes
-        // the collectives that follow (the lattice, the bitmap's limit) and epsilon as they are,
-        // the other four values as two 64-bit mixes
-        uint64_t mine[kKldWords], all[kKldWords * kMaxRanks];
-        mine[0] = dm_bits(p->bin_xy);
-        mine[1] = (uint64_t)p->theta_bins | (uint64_t)p->multinomial << 32;
-        mine[2] = p->max_bins;
-        mine[3] = dm_bits(p->epsilon);
-        mine[4] = kld_mix(dm_bits(p->z_quantile), p->n_min);
-        mine[5] = kld_mix(p->n_max, dm_bits(p->min_change));
-        const int rc = host_allgather(ctx, mine, all, sizeof(mine));
-        if (rc) return rc;
-        for (int r = 0; r < G; ++r)
-            if (memcmp(&all[kKldWords * r], mine, sizeof(mine)) != 0)
-                return fail(ctx, ESLAM_ERR_INVALID_ARG, "kld_count: the ranks' parameters differ");
-    }
-    const double inv = 1.0 / p->bin_xy;
-    // pass 1 over the particles as they stand.  A rank whose gather or allocation failed says so
-    // in the sign of its count, so no rank is left in a collective
-    int rc = materialize(ctx);
-    if (!rc) rc = kld_reserve(ctx, 0, 0);
-    int64_t rec[kKldWords] = {2147483647ll, -2147483648ll, 2147483647ll, -2147483648ll, 0, 0};
-    KldScratch ks;
-    if (!rc) {
-        Carver place(ctx->kld.get());
-        carve_kld(place, 0, 0, &ks);
-        HIPCHK(ctx, eslam_launch_kld_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, inv, p->theta_bins, ks.part, ks.out, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ks.out, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(rec, ctx->scratch_host.get(), sizeof(rec));
-    }
-    if (ctx->sharded) {
-        const std::string msg = ctx->err;
-        int64_t all[kKldWords * kMaxRanks];
-        if (rc) rec[kKldCounted] = -1;
-        const int crc = host_allgather(ctx, rec, all, sizeof(rec));
-        if (rc) return fail(ctx, rc, msg.c_str());
-        if (crc) return crc;
-        int64_t tot[kKldWords] = {2147483647ll, -2147483648ll, 2147483647ll, -2147483648ll, 0, 0};
-        for (int r = 0; r < G; ++r) {
-            if (all[kKldWords * r + kKldCounted] < 0)
-                return fail(ctx, ESLAM_ERR_COMM, ("kld_count: rank " + std::to_string(r) + " failed").c_str());
-            kld_fold(tot, &all[kKldWords * r]);
-        }
-        memcpy(rec, tot, sizeof(rec));
-    } else if (rc) {
-        return rc;
-    }
-    info->particles_counted = (uint64_t)rec[kKldCounted];
-    info->particles_skipped = (uint64_t)rec[kKldSkipped];
-    info->bins[2] = p->theta_bins;
-    uint64_t k = 0;
-    if (rec[kKldCounted]) {
-        const uint64_t nx = (uint64_t)(rec[kKldIx1] - rec[kKldIx0] + 1), ny = (uint64_t)(rec[kKldIy1] - rec[kKldIy0] + 1);
-        info->origin[0] = rec[kKldIx0];
-        info->origin[1] = rec[kKldIy0];
-        info->bins[0] = nx;
-        info->bins[1] = ny;
-        uint64_t cells = 0, total = 0;
-        const bool wide = __builtin_mul_overflow(nx, ny, &cells) || __builtin_mul_overflow(cells, (uint64_t)p->theta_bins, &total);
-        if (wide || total > (p->max_bins ? p->max_bins : 1ull << 27))
-            return fail(ctx, ESLAM_ERR_UNSUPPORTED, "kld_count: cloud too spread for the bin size (the box's bins exceed max_bins)");
-        const uint64_t words = (total + 63) / 64;
-        rc = agree(ctx, kld_reserve(ctx, words, ctx->sharded ? (uint64_t)G : 0), "kld_count");
-        if (rc) return rc;
-        Carver place(ctx->kld.get());
-        carve_kld(place, words, ctx->sharded ? (uint64_t)G : 0, &ks);
-        KldGrid g;
-        memset(&g, 0, sizeof(g));
-        g.inv = inv;
-        g.theta_bins = p->theta_bins;
-        g.ix0 = rec[kKldIx0];
-        g.iy0 = rec[kKldIy0];
-        g.nx = nx;
-        HIPCHK(ctx, eslam_launch_kld_mark(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, &g, ks.bits, words, ctx->stream));
-        if (ctx->sharded) {
-            rc = comm_allgather(ctx, ks.bits, ks.all, words * sizeof(uint64_t));
-            if (rc) return rc;
-            HIPCHK(ctx, eslam_launch_kld_or(ks.all, (uint32_t)G, words, ks.bits, ctx->stream));
-        }
-        HIPCHK(ctx, eslam_launch_kld_popcount(ks.bits, words, ks.part, ks.out, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_host, ks.out, sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        k = (uint64_t)ctx->scratch_host.as<const int64_t>()[kKldCounted];
-    }
-    info->bins_occupied = k;
-    info->bound = dm_kld_bound(k, p->epsilon, p->z_quantile);
-    // the largest count the resample that follows accepts (resample_to, resample_sharded)
-    uint64_t limit = ctx->sharded ? (1ull << 30) - 64 : (1ull << 32) - 2;
-    if (p->n_max && p->n_max < limit) limit = p->n_max;
-    const uint64_t capacity = !particle_maps(ctx) ? 0 : ctx->sharded ? ctx->n_global : ctx->cap;
-    info->samples = dm_kld_samples(info->bound, p->n_min, limit, capacity, ctx->n_global, p->min_change, &info->clamped);
-    return ESLAM_OK;
-}
-}  // namespace
-
-extern "C" int eslam_gpu_kld_count(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx || !params || !info) return ESLAM_ERR_INVALID_ARG;
-    if (const char* why = kld_refusal(params)) return fail(ctx, ESLAM_ERR_INVALID_ARG, why);
-    return kld_count(ctx, params, info);
-}
-
-extern "C" int eslam_gpu_resample_kld(eslam_ctx* ctx, const eslam_kld_params* params, eslam_kld_info* info, eslam_resample_info* rinfo)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (rinfo) memset(rinfo, 0, sizeof(*rinfo));
-    if (!ctx || !params) return ESLAM_ERR_INVALID_ARG;
-    if (const char* why = kld_refusal(params)) return fail(ctx, ESLAM_ERR_INVALID_ARG, why);
-    // the maps of a sharded filter do not travel, and whether the count changes is known only
-    // after the count's collectives: refused before any, unless the parameters fix the count
-    const bool pinned = ctx->sharded && particle_maps(ctx);
-    if (pinned && !(params->n_min == ctx->n_global && params->n_max == ctx->n_global))
-        return fail(ctx, ESLAM_ERR_UNSUPPORTED,
-                    "resample_kld: a sharded filter with per-particle maps keeps its count (n_min == n_max == the global count)");
-    eslam_kld_info inf;
-    memset(&inf, 0, sizeof(inf));
-    const int rc = kld_count(ctx, params, &inf);
-    if (info) *info = inf;
-    if (rc) return rc;
-    const bool multi = params->multinomial != 0;
-    return ctx->sharded && !pinned ? resample_sharded(ctx, inf.samples, multi, rinfo) : resample_to(ctx, inf.samples, multi, rinfo);
-}
-
 extern "C" int eslam_gpu_get_rng_state(eslam_ctx* ctx, eslam_rng_state* st)
 {
     if (!ctx || !st) return ESLAM_ERR_INVALID_ARG;
@@ -3764,1069 +2448,3 @@ extern "C" int eslam_gpu_selftest_math(int device, int fn, const double* x, cons
     if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
     return e == hipSuccess ? ESLAM_OK : ESLAM_ERR_HIP;
 }
-
-// ---------------------------------------------------------------------------------------
-// snapshots: eslam_gpu_save / eslam_gpu_load (kernels in eslam_snapshot.hip)
-// ---------------------------------------------------------------------------------------
-namespace {
-
-const char kSnapMagic[8] = {'E', 'S', 'L', 'A', 'M', 'S', 'N', 'P'};
-enum { kSecGrid = 0, kSecHash, kSecParticles, kSecScalars, kSecMaps, kSecCount };   // bit k of SnapHeader::sections
-struct SnapSection {
-    uint64_t off, size;
-};
-struct SnapHeader {
-    char magic[8];
-    uint32_t version, sections;
-    uint64_t bytes;
-    uint64_t n;
-    uint32_t particle_maps, local_map_trail;
-    uint32_t hx, hy;                         // the window's half-widths (0 without per-particle maps)
-    double max_sensor_range;
-    uint32_t width, height;
-    double scale_x, scale_y, offset_x, offset_y;
-    double g2l[12];
-    uint64_t n_patches;
-    uint32_t has_height, hash_bins;
-    uint64_t hash_n;
-    uint64_t tables, pages;
-    uint32_t wx, wy;
-    uint32_t row_words, pad;
-    SnapSection sec[kSecCount];
-    uint64_t reserved;
-};
-static_assert(sizeof(SnapHeader) == 336, "snapshot header");
-struct SnapScalars {
-    eslam_rng_state rng;
-    uint64_t pad;
-    int32_t wexp;
-    uint32_t minstd;
-    double max_weight;
-    uint64_t update_count;
-    double inv_n;
-};
-static_assert(sizeof(eslam_rng_state) == 280 && sizeof(SnapScalars) == 320, "snapshot scalars");
-
-inline uint64_t pad16(uint64_t b) { return (b + 15) & ~(uint64_t)15; }
-inline uint32_t snap_row_words(uint32_t W, uint32_t V) { return (4u + W + 3u * V + 3u) & ~3u; }
-constexpr uint64_t kPageBytes = DM_LM_PAGE_CELLS * sizeof(float2);
-
-// the sections' offsets and sizes that the header's counts imply (the one layout a blob may have)
-void snap_layout(const SnapHeader& h, SnapSection sec[kSecCount], uint64_t* bytes)
-{
-    uint64_t at = sizeof(SnapHeader);
-    const uint64_t ncell = (uint64_t)h.width * h.height, np = h.n_patches, n = h.n;
-    uint64_t size[kSecCount];
-    size[kSecGrid] = pad16((ncell + 1) * 4) + pad16(np * 8) + (h.has_height ? pad16(np * 4) : 0);
-    size[kSecHash] = 4 * pad16(h.hash_n * 8) + pad16(h.hash_n * 4) + pad16((uint64_t)h.hash_bins * h.hash_bins * 4);
-    size[kSecParticles] = 7 * pad16(n * 8) + pad16(n);
-    size[kSecScalars] = sizeof(SnapScalars);
-    size[kSecMaps] = pad16(n * 4) + pad16(h.tables * h.row_words * 4) + pad16(h.pages * 4) + h.pages * kPageBytes;
-    for (int k = 0; k < kSecCount; ++k) {
-        sec[k] = SnapSection{0, 0};
-        if (!(h.sections & (1u << k))) continue;
-        sec[k] = SnapSection{at, size[k]};
-        at += size[k];
-    }
-    *bytes = at;
-}
-
-enum PieceKind { PK_HOST = 0, PK_DEV, PK_SID, PK_TABLES, PK_OWNER, PK_PAGES };
-// one array of the blob, or the part of it this rank writes: count units of unit bytes at blob
-// offset off (then tail zeros, up to 16 bytes, where the part ends the array)
-struct Piece {
-    int kind;
-    const void* src;                         // PK_HOST: host memory; PK_DEV: device memory
-    uint64_t count, unit;
-    uint64_t off = 0, tail = 0;
-};
-// the blob as positional writes and reads (the stream forms ignore the offset: their order is the blob's)
-typedef std::function<int(uint64_t off, const void* data, uint64_t bytes)> SnapSink;
-typedef std::function<int(uint64_t off, void* data, uint64_t bytes)> SnapSource;
-
-struct SnapPlan {
-    SnapHeader h;
-    SnapScalars sc;
-    std::vector<Piece> pieces;
-    SnapCensus cen;
-    const uint32_t* sid;
-    std::vector<uint32_t> bsizes;            // the pose hash's bucket sizes
-    uint64_t T = 0, P = 0;                   // this rank's live tables and pages (h.tables, h.pages: the filter's)
-    uint32_t tbase = 0, pbase = 0;           // those of the ranks below (a sharded filter)
-};
-
-const char* const kSnapStreamSharded =
-    "snapshot: a sharded filter is one file written and read by offset (eslam_gpu_save_at / eslam_gpu_load_at); "
-    "a sequential stream cannot carry a part of it";
-
-int snap_staging(eslam_ctx* ctx, uint64_t bytes)
-{
-    for (int k = 0; k < 2; ++k)
-        HIPCHK(ctx, ctx->snap_ev[k].create(false));
-    if (bytes <= ctx->snap_cap) return ESLAM_OK;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; ++k) {
-        ctx->snap_host[k].reset();
-        ctx->snap_dev[k].reset();
-    }
-    ctx->snap_cap = 0;
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->snap_host[k].alloc(bytes) != hipSuccess || ctx->snap_dev[k].alloc(bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no memory for the staging buffers (lower chunk_bytes)");
-        }
-    }
-    ctx->snap_cap = bytes;
-    return ESLAM_OK;
-}
-
-// the staging size for pieces of at most `largest` bytes with units of at most `unit` bytes
-uint64_t snap_stage_bytes(uint64_t chunk, uint64_t largest, uint64_t unit)
-{
-    uint64_t b = chunk < largest ? chunk : largest;
-    b = b < unit ? unit : b;
-    return pad16(b < 4096 ? 4096 : b) + 16;  // a part's last chunk carries the whole array's padding
-}
-
-uint64_t snap_tiles(uint64_t items) { return (items + kCompactTileItems - 1) / kCompactTileItems; }
-
-int snap_read_count(eslam_ctx* ctx, const uint32_t* dev, uint64_t* out)
-{
-    uint32_t* h = ctx->scratch_host.as<uint32_t>();
-    HIPCHK(ctx, hipMemcpyAsync(h, dev, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *out = *h;
-    return ESLAM_OK;
-}
-
-// the census of the per-particle maps: the live tables and pages, ranked (pl.cen), and their counts
-int snap_census(eslam_ctx* ctx, SnapPlan& pl)
-{
-    const LocalMaps& lm = ctx->lm;
-    SnapCensus& c = pl.cen;
-    Carver size(nullptr);
-    carve_census(size, lm.ntables, ctx->cap, lm.npages, &c);
-    // kept until the maps are dropped (free_local_maps)
-    if (!ctx->lmb.census && ctx->lmb.census.alloc(size.bytes()) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the census");
-    }
-    Carver place(ctx->lmb.census.get());
-    carve_census(place, lm.ntables, ctx->cap, lm.npages, &c);
-    const uint64_t n = ctx->n, ttiles = snap_tiles(n);
-    int rc = grow(ctx, ctx->lmb.counts, (ttiles + 1) * 4);
-    if (rc) return rc;
-    c.counts = ctx->lmb.counts;
-    HIPCHK(ctx, eslam_launch_snap_census_tables(&lm, &c, pl.sid, n, ctx->stream));
-    uint64_t T = 0, P = 0;
-    rc = snap_read_count(ctx, c.counts + ttiles, &T);
-    if (rc) return rc;
-    const uint64_t ptiles = snap_tiles(T * (lm.wx * lm.wy + lm.V));
-    if (ptiles >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: the page census has 2^32 tiles or more");
-    rc = grow(ctx, ctx->lmb.counts, (ptiles + 1) * 4);
-    if (rc) return rc;
-    c.counts = ctx->lmb.counts;
-    HIPCHK(ctx, eslam_launch_snap_census_pages(&lm, &c, T, ctx->stream));
-    rc = snap_read_count(ctx, c.counts + ptiles, &P);
-    if (rc) return rc;
-    pl.T = pl.h.tables = T;
-    pl.P = pl.h.pages = P;
-    return ESLAM_OK;
-}
-
-// settle, run a pending gather, take the census: the header, the scalars and the pieces of a save
-// this rank's part of the plan: everything but the counts of the other ranks
-int snap_plan_local(eslam_ctx* ctx, SnapPlan& pl);
-// the pieces this rank writes, in the blob's order
-int snap_plan_pieces(eslam_ctx* ctx, SnapPlan& pl);
-
-// On a sharded filter a collective: one all_gather of every rank's {code, tables, pages,
-// n_patches, update_count, minstd}.  A rank whose own part failed takes part in it, so either
-// every rank has a plan or every rank returns an error (its own, or ESLAM_ERR_COMM).
-int snap_plan(eslam_ctx* ctx, SnapPlan& pl)
-{
-    if (const int rc_ = settle(ctx)) return rc_;
-    int rc = snap_plan_local(ctx, pl);
-    if (ctx->sharded) {
-        const std::string msg = ctx->err;
-        const int G = ctx->comm.nranks, me = ctx->comm.rank;
-        const uint64_t mine[6] = {(uint64_t)(int64_t)rc, pl.T, pl.P, pl.h.n_patches, pl.sc.update_count, pl.sc.minstd};
-        std::vector<uint64_t> all(6 * (size_t)G, 0);
-        static_assert(sizeof(mine) <= kHostXBytes, "host_allgather's buffer");
-        const int crc = host_allgather(ctx, mine, all.data(), sizeof(mine));
-        if (rc) {
-            ctx->err = msg;
-            return rc;
-        }
-        if (crc) return crc;
-        uint64_t T = 0, P = 0;
-        for (int r = 0; r < G; ++r) {
-            const uint64_t* q = &all[6 * (size_t)r];
-            if (q[0]) return fail(ctx, ESLAM_ERR_COMM, ("snapshot: rank " + std::to_string(r) + " failed").c_str());
-            if (q[3] != mine[3] || q[4] != mine[4] || q[5] != mine[5])
-                return fail(ctx, ESLAM_ERR_COMM, "snapshot: the ranks' grids, update counts or generators differ (not one filter)");
-            if (r == me) {
-                pl.tbase = (uint32_t)T;
-                pl.pbase = (uint32_t)P;
-            }
-            T += q[1];
-            P += q[2];
-        }
-        if (T > ctx->n_global) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the ranks hold more tables than the filter has particles");
-        if (P >= 0xffffffffull) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "snapshot: 2^32 - 1 live pages or more");
-        pl.h.n = ctx->n_global;
-        pl.h.tables = T;
-        pl.h.pages = P;
-        snap_layout(pl.h, pl.h.sec, &pl.h.bytes);
-    }
-    return snap_plan_pieces(ctx, pl);
-}
-
-int snap_plan_local(eslam_ctx* ctx, SnapPlan& pl)
-{
-    memset(&pl.h, 0, sizeof(pl.h));
-    memset(&pl.sc, 0, sizeof(pl.sc));
-    if (const int rc_ = check_poisoned(ctx)) return rc_;
-    if (!ctx->has_map) return fail(ctx, ESLAM_ERR_NO_ENVIRONMENT, "No environment attached.");
-    int rc = materialize(ctx);
-    if (!rc) rc = read_ctl(ctx);
-    if (rc) return rc;
-    const Ctl& ctl = *ctx->ctl_host;
-    const DevState& s = ctx->st[ctl.base ^ ctl.flip];
-    SnapHeader& h = pl.h;
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, kSnapMagic, 8);
-    h.version = ESLAM_SNAPSHOT_VERSION;
-    h.n = ctx->n;
-    h.particle_maps = particle_maps(ctx) ? 1u : 0u;
-    h.local_map_trail = ctx->cfg.local_map_trail;
-    h.max_sensor_range = ctx->cfg.max_sensor_range;
-    h.width = ctx->map.width;
-    h.height = ctx->map.height_cells;
-    h.scale_x = ctx->map_scale[0];
-    h.scale_y = ctx->map_scale[1];
-    h.offset_x = ctx->map.offset_x;
-    h.offset_y = ctx->map.offset_y;
-    memcpy(h.g2l, ctx->map.g2l, sizeof(h.g2l));
-    h.n_patches = ctx->map_np;
-    h.has_height = ctx->grid.height ? 1u : 0u;
-    h.sections = (1u << kSecGrid) | (1u << kSecParticles) | (1u << kSecScalars);
-    if (h.particle_maps) {
-        h.hx = dm_lm_half(ctx->cfg.max_sensor_range, ctx->map_scale[0]);
-        h.hy = dm_lm_half(ctx->cfg.max_sensor_range, ctx->map_scale[1]);
-    }
-    if (ctx->has_hash) {
-        h.sections |= 1u << kSecHash;
-        h.hash_n = ctx->hash_n;
-        h.hash_bins = (uint32_t)ctx->cfg.hash_slope_bins;
-        pl.bsizes.resize(ctx->hash_bstart.size() - 1);
-        for (size_t b = 0; b + 1 < ctx->hash_bstart.size(); ++b) pl.bsizes[b] = ctx->hash_bstart[b + 1] - ctx->hash_bstart[b];
-    }
-    pl.sid = s.sid;
-    if (ctx->lm_ready && ctx->n) {
-        h.sections |= 1u << kSecMaps;
-        h.wx = ctx->lm.wx;
-        h.wy = ctx->lm.wy;
-        h.row_words = snap_row_words(ctx->lm.wx * ctx->lm.wy, ctx->lm.V);
-        rc = snap_census(ctx, pl);
-        if (rc) return rc;
-    }
-    snap_layout(h, h.sec, &h.bytes);
-    // the scalars: eslam_gpu_get_rng_state's, and what the next update reads of the control block
-    SnapScalars& sc = pl.sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.rng.minstd_x = ctl.minstd;
-    sc.rng.project_count = ctx->proj_event;
-    sc.rng.init_count = ctx->init_event;
-    sc.rng.hash_count = *ctx->hash_ev;
-    sc.rng.max_weight = ctl.max_weight;
-    memcpy(sc.rng.ud_pose, ctx->ud_pose, sizeof(ctx->ud_pose));
-    memcpy(sc.rng.libc_rand, ctx->libcp->r, sizeof(sc.rng.libc_rand));
-    sc.rng.libc_rand_pos = ctx->libcp->i;
-    sc.wexp = ctl.wexp;
-    sc.minstd = ctl.minstd;
-    sc.max_weight = ctl.max_weight;
-    sc.update_count = ctl.update_count;
-    sc.inv_n = ctl.inv_n;
-    return ESLAM_OK;
-}
-
-// Every array of the blob is split by owner ("Sharded filters"): rank 0 writes
-// what every rank holds alike (header, grid, hash, scalars); the particle arrays go by shard;
-// tables and pages by the ranks' counts (rank-major order is the canonical order).  The zeros
-// behind an array go with the rank that holds its last element.  Unsharded: everything.
-int snap_plan_pieces(eslam_ctx* ctx, SnapPlan& pl)
-{
-    const SnapHeader& h = pl.h;
-    const Ctl& ctl = *ctx->ctl_host;
-    const DevState& s = ctx->st[ctl.base ^ ctl.flip];
-    std::vector<Piece>& p = pl.pieces;
-    const bool lead = !ctx->sharded || ctx->comm.rank == 0;
-    uint64_t at = 0, mine = 0;
-    // the array of `total` units at the blob's cursor: this rank writes [first, first + count)
-    auto add = [&](int kind, const void* src, uint64_t total, uint64_t unit, uint64_t first, uint64_t count) {
-        Piece q{kind, src, count, unit};
-        q.off = at + first * unit;
-        q.tail = (count && first + count == total) ? pad16(total * unit) - total * unit : 0;
-        at += pad16(total * unit);
-        mine += count * unit + q.tail;
-        if (count) p.push_back(q);
-    };
-    auto whole = [&](int kind, const void* src, uint64_t total, uint64_t unit) { add(kind, src, total, unit, 0, lead ? total : 0); };
-    const uint64_t ncell = (uint64_t)h.width * h.height, n = h.n, gb = ctx->sharded ? ctx->gbase : 0, nl = ctx->n;
-    whole(PK_HOST, &pl.h, sizeof(SnapHeader), 1);
-    whole(PK_DEV, ctx->grid.cells, ncell + 1, 4);
-    whole(PK_DEV, ctx->grid.patch, h.n_patches, 8);
-    if (h.has_height) whole(PK_DEV, ctx->grid.height, h.n_patches, 4);
-    if (ctx->has_hash) {
-        for (int f = 0; f < 4; ++f) whole(PK_DEV, hash_field(ctx, f), h.hash_n, 8);
-        whole(PK_HOST, ctx->hash_bucket.data(), h.hash_n * 4, 1);
-        whole(PK_HOST, pl.bsizes.data(), pl.bsizes.size() * 4, 1);
-    }
-    const double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
-    for (int f = 0; f < 7; ++f) add(PK_DEV, f7[f], n, 8, gb, nl);
-    add(PK_DEV, s.flags, n, 1, gb, nl);
-    whole(PK_HOST, &pl.sc, sizeof(SnapScalars), 1);
-    if (h.sections & (1u << kSecMaps)) {
-        add(PK_SID, nullptr, n, 4, gb, nl);
-        add(PK_TABLES, nullptr, h.tables, (uint64_t)h.row_words * 4, pl.tbase, pl.T);
-        add(PK_OWNER, nullptr, h.pages, 4, pl.pbase, pl.P);
-        add(PK_PAGES, nullptr, h.pages, kPageBytes, pl.pbase, pl.P);
-    }
-    if (at != h.bytes || (!ctx->sharded && mine != h.bytes)) return fail(ctx, ESLAM_ERR_HIP, "snapshot: the pieces do not add up to the layout");
-    return ESLAM_OK;
-}
-
-// chunks a piece splits into: whole units, at most chunk bytes (one unit when a unit is longer);
-// the piece's padding rides on its last chunk
-uint64_t snap_units_per_chunk(const Piece& q, uint64_t chunk)
-{
-    const uint64_t u = chunk / q.unit;       // chunk is a multiple of 16: the padded last chunk fits too
-    return u ? u : 1;
-}
-
-uint64_t snap_chunk_count(const std::vector<Piece>& p, uint64_t chunk)
-{
-    uint64_t c = 0;
-    for (const Piece& q : p) {
-        if (!q.count) continue;
-        const uint64_t per = snap_units_per_chunk(q, chunk);
-        c += (q.count + per - 1) / per;
-    }
-    return c;
-}
-
-void snap_fill_info(const SnapHeader& h, uint64_t chunks, eslam_snapshot_info* info)
-{
-    if (!info) return;
-    memset(info, 0, sizeof(*info));
-    info->bytes = h.bytes;
-    info->particles = h.n;
-    info->tables = h.tables;
-    info->pages = h.pages;
-    info->grid_patches = h.n_patches;
-    info->hash_poses = h.hash_n;
-    info->chunks = chunks;
-    info->version = h.version;
-    info->sections = h.sections;
-}
-
-struct SnapChunk {
-    size_t piece;
-    uint64_t k0, cnt;
-    bool last;                               // the piece's last chunk: its padding follows
-};
-
-int snap_write_pieces(eslam_ctx* ctx, SnapPlan& pl, const SnapSink& w, uint64_t chunk, uint64_t* chunks_out);
-
-// positional: the sink takes every chunk with its offset (a sharded filter: this rank's chunks,
-// and the call is a collective); else the chunks come in the blob's order
-int snap_save(eslam_ctx* ctx, const SnapSink& w, bool positional, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t capacity)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx || !w) return ESLAM_ERR_INVALID_ARG;
-    if (ctx->sharded && !positional) return fail(ctx, ESLAM_ERR_UNSUPPORTED, kSnapStreamSharded);
-    if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
-    const uint64_t chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
-    SnapPlan pl;
-    int rc = snap_plan(ctx, pl);             // sharded: every rank has a plan, or every rank returns here
-    if (rc) return rc;
-    uint64_t chunks = 0;
-    if (capacity < pl.h.bytes)
-        rc = fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: the buffer is smaller than the snapshot (eslam_gpu_snapshot_size)");
-    else
-        rc = snap_write_pieces(ctx, pl, w, chunk, &chunks);
-    rc = agree(ctx, rc, "snapshot");
-    if (rc) return rc;
-    snap_fill_info(pl.h, chunks, info);
-    return ESLAM_OK;
-}
-
-int snap_write_pieces(eslam_ctx* ctx, SnapPlan& pl, const SnapSink& w, uint64_t chunk, uint64_t* chunks_out)
-{
-    int rc = ESLAM_OK;
-    uint64_t largest = 0, unit = 16;
-    for (const Piece& q : pl.pieces) {
-        largest = std::max(largest, pad16(q.count * q.unit + q.tail));
-        unit = std::max(unit, pad16(q.unit));
-    }
-    rc = snap_staging(ctx, snap_stage_bytes(chunk, largest, unit));
-    if (rc) return rc;
-    const std::vector<Piece>& P = pl.pieces;
-    // the next chunk after (piece, k0 + cnt); piece == P.size(): none
-    auto next = [&](const SnapChunk& c) {
-        SnapChunk d = c;
-        d.k0 = c.k0 + c.cnt;
-        while (d.piece < P.size() && d.k0 >= P[d.piece].count) {
-            ++d.piece;
-            d.k0 = 0;
-        }
-        if (d.piece < P.size()) {
-            const uint64_t per = snap_units_per_chunk(P[d.piece], chunk), left = P[d.piece].count - d.k0;
-            d.cnt = left < per ? left : per;
-            d.last = d.cnt == left;
-        }
-        return d;
-    };
-    // chunk c into its slot: packed or copied on the stream into the pinned buffer, the slot's event after it
-    auto issue = [&](const SnapChunk& c, uint32_t slot) -> int {
-        const Piece& q = P[c.piece];
-        const uint64_t bytes = c.cnt * q.unit, off = c.k0 * q.unit;
-        char* host = ctx->snap_host[slot].as<char>();
-        if (q.kind == PK_HOST) {
-            memcpy(host, (const char*)q.src + off, bytes);
-        } else if (q.kind == PK_DEV) {
-            HIPCHK(ctx, hipMemcpyAsync(host, (const char*)q.src + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        } else {
-            HIPCHK(ctx, eslam_launch_snap_pack(q.kind - PK_SID, &ctx->lm, &pl.cen, pl.sid, pl.T, pl.tbase, pl.pbase, c.k0, c.cnt,
-                                               pl.h.row_words, ctx->snap_dev[slot], ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(host, ctx->snap_dev[slot], bytes, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
-        return ESLAM_OK;
-    };
-    SnapChunk cur = next(SnapChunk{0, 0, 0, false});
-    uint32_t slot = 0;
-    uint64_t chunks = 0;
-    if (cur.piece < P.size()) rc = issue(cur, slot);
-    while (!rc && cur.piece < P.size()) {
-        // the device packs chunk c + 1 while the host writes chunk c
-        const SnapChunk nxt = next(cur);
-        if (nxt.piece < P.size()) rc = issue(nxt, slot ^ 1u);
-        if (rc) break;
-        HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));
-        const Piece& q = P[cur.piece];
-        uint64_t bytes = cur.cnt * q.unit;
-        if (cur.last && q.tail) {            // zeros up to the array's next 16-byte boundary
-            memset(ctx->snap_host[slot].as<char>() + bytes, 0, q.tail);
-            bytes += q.tail;
-        }
-        if (w(q.off + cur.k0 * q.unit, ctx->snap_host[slot], bytes) != 0) {
-            rc = fail(ctx, ESLAM_ERR_COMM, "snapshot: the write callback failed");
-            break;
-        }
-        ++chunks;
-        cur = nxt;
-        slot ^= 1u;
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);    // a copy into the pinned buffers may be in flight
-        return rc;
-    }
-    *chunks_out = chunks;
-    return ESLAM_OK;
-}
-
-// ---- load -------------------------------------------------------------------------------
-struct SnapReader {
-    eslam_ctx* ctx;
-    SnapSource r;
-    uint64_t chunk;
-    uint32_t slot = 0;
-    uint64_t chunks = 0;
-    uint64_t at = 0;                         // the blob offset of the next array
-    uint64_t dst0 = 0;                       // PK_TABLES / PK_OWNER: the pool entry of unit `first`
-    const SnapSubset* sub = nullptr;         // PK_OWNER: owners renamed through the subset
-};
-typedef std::function<int(const void* data, uint64_t k0, uint64_t cnt)> SnapCheck;
-
-int snap_bad(eslam_ctx* ctx, const char* msg) { return fail(ctx, ESLAM_ERR_INVALID_ARG, msg); }
-
-// one array of the blob through the staging buffers: every chunk is read into a pinned slot,
-// checked on the host (check; may be empty), and then copied to dst (PK_HOST: host memory,
-// may be null; PK_DEV: device memory) or unpacked into pool entries [k0, k0 + cnt)
-int snap_read_part(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check,
-                   uint64_t off, uint64_t tail);
-
-// the whole array at the cursor
-int snap_read(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check)
-{
-    const uint64_t all = count * unit, off = rd.at;
-    rd.at += pad16(all);
-    rd.dst0 = 0;
-    return snap_read_part(rd, kind, dst, count, unit, rw, check, off, pad16(all) - all);
-}
-
-// units [first, first + count) of the array of `total` units at the cursor, which then moves past the array
-int snap_read_slice(SnapReader& rd, int kind, void* dst, uint64_t total, uint64_t first, uint64_t count, uint64_t unit,
-                    const SnapCheck& check)
-{
-    const uint64_t off = rd.at + first * unit;
-    rd.at += pad16(total * unit);
-    rd.dst0 = 0;
-    return snap_read_part(rd, kind, dst, count, unit, 0, check, off, 0);
-}
-
-int snap_read_part(SnapReader& rd, int kind, void* dst, uint64_t count, uint64_t unit, uint32_t rw, const SnapCheck& check,
-                   uint64_t off, uint64_t tail)
-{
-    eslam_ctx* ctx = rd.ctx;
-    uint64_t per = rd.chunk / unit;
-    per = per ? per : 1;
-    for (uint64_t k0 = 0; k0 < count; k0 += per) {
-        const uint64_t cnt = count - k0 < per ? count - k0 : per, bytes = cnt * unit;
-        const bool last = k0 + cnt == count;
-        const uint32_t slot = rd.slot;
-        rd.slot ^= 1u;
-        HIPCHK(ctx, hipEventSynchronize(ctx->snap_ev[slot]));     // the slot's previous chunk has left it
-        char* host = ctx->snap_host[slot].as<char>();
-        if (rd.r(off + k0 * unit, host, bytes + (last ? tail : 0)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
-        ++rd.chunks;
-        if (check) {
-            const int rc = check(host, k0, cnt);
-            if (rc) return rc;
-        }
-        if (kind == PK_HOST) {
-            if (dst) memcpy((char*)dst + k0 * unit, host, bytes);
-            continue;
-        }
-        if (kind == PK_DEV) {
-            HIPCHK(ctx, hipMemcpyAsync((char*)dst + k0 * unit, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            HIPCHK(ctx, hipMemcpyAsync(ctx->snap_dev[slot], host, bytes, hipMemcpyHostToDevice, ctx->stream));
-            if (kind == PK_OWNER && rd.sub)
-                HIPCHK(ctx, eslam_launch_snap_unpack_owner_subset(&ctx->lm, rd.dst0 + k0, cnt, rd.sub, ctx->snap_dev[slot], ctx->stream));
-            else
-                HIPCHK(ctx, eslam_launch_snap_unpack(kind - PK_SID, &ctx->lm, rd.dst0 + k0, cnt, rw, ctx->snap_dev[slot], ctx->stream));
-        }
-        HIPCHK(ctx, hipEventRecord(ctx->snap_ev[slot], ctx->stream));
-    }
-    return ESLAM_OK;
-}
-
-int snap_check_header(eslam_ctx* ctx, const SnapHeader& h, uint64_t known_bytes)
-{
-    if (memcmp(h.magic, kSnapMagic, 8) != 0) return snap_bad(ctx, "snapshot: bad magic");
-    if (h.version != ESLAM_SNAPSHOT_VERSION) return snap_bad(ctx, "snapshot: unknown version");
-    const uint32_t need = (1u << kSecGrid) | (1u << kSecParticles) | (1u << kSecScalars);
-    if ((h.sections & need) != need || (h.sections >> kSecCount)) return snap_bad(ctx, "snapshot: section mask");
-    if (h.particle_maps > 1u || (h.particle_maps != 0u) != particle_maps(ctx))
-        return snap_bad(ctx, "snapshot: ESLAM_FLAG_PARTICLE_MAPS differs from the context's");
-    if (h.local_map_trail != ctx->cfg.local_map_trail) return snap_bad(ctx, "snapshot: local_map_trail differs from the context's");
-    if (h.n >= (1ull << 32) - 1 || h.tables > h.n || h.pages >= 0xffffffffull) return snap_bad(ctx, "snapshot: counts out of range");
-    if (!h.width || !h.height || (uint64_t)h.width * h.height >= 0xffffffffull || h.n_patches > 0xffffffffull || h.has_height > 1u)
-        return snap_bad(ctx, "snapshot: grid size");
-    if (!(h.scale_x > 0.0) || !(h.scale_y > 0.0) || !dm_isfinite(h.scale_x) || !dm_isfinite(h.scale_y))
-        return snap_bad(ctx, "snapshot: grid scale");
-    const bool hash = (h.sections >> kSecHash) & 1u, maps = (h.sections >> kSecMaps) & 1u;
-    if (hash ? (h.hash_bins == 0 || h.hash_bins > 4096 || h.hash_bins != (uint32_t)ctx->cfg.hash_slope_bins || h.hash_n >= (1ull << 32))
-             : (h.hash_bins != 0 || h.hash_n != 0))
-        return snap_bad(ctx, "snapshot: pose hash size (hash_slope_bins differs from the context's?)");
-    if (h.particle_maps) {
-        const double r = ctx->cfg.max_sensor_range;
-        if (!(r == r) || r < 0.0 || r > 1e6) return snap_bad(ctx, "max_sensor_range must be finite and >= 0");
-        if (h.hx != dm_lm_half(r, h.scale_x) || h.hy != dm_lm_half(r, h.scale_y))
-            return snap_bad(ctx, "snapshot: max_sensor_range (the window's half-widths) differs from the context's");
-        if (h.local_map_trail > 4096) return snap_bad(ctx, "local_map_trail: at most 4096 tiles");
-    } else if (h.hx || h.hy) {
-        return snap_bad(ctx, "snapshot: window without per-particle maps");
-    }
-    if (maps != (h.particle_maps && h.n > 0)) return snap_bad(ctx, "snapshot: per-particle map section");
-    if (maps) {
-        if (h.wx != 2 * h.hx + 1 || h.wy != 2 * h.hy + 1 || h.row_words != snap_row_words(h.wx * h.wy, h.local_map_trail))
-            return snap_bad(ctx, "snapshot: table row size");
-    } else if (h.tables || h.pages || h.wx || h.wy || h.row_words) {
-        return snap_bad(ctx, "snapshot: tables without a map section");
-    }
-    SnapSection sec[kSecCount];
-    uint64_t bytes = 0;
-    snap_layout(h, sec, &bytes);
-    for (int k = 0; k < kSecCount; ++k)
-        if (sec[k].off != h.sec[k].off || sec[k].size != h.sec[k].size)
-            return snap_bad(ctx, "snapshot: a section's offset or size does not match the header's counts");
-    if (bytes != h.bytes || (known_bytes && known_bytes != h.bytes)) return snap_bad(ctx, "snapshot: size does not match the header (truncated?)");
-    if (ctx->sharded && h.n != ctx->n_global)
-        return snap_bad(ctx, "snapshot: its particle count is not the sharded context's n_global");
-    if (maps && !ctx->sharded) {             // a sharded load checks its own part's pages, once it has counted them
-        const uint64_t per = ctx->cfg.local_map_pages ? ctx->cfg.local_map_pages : kDefaultMapPages;
-        if (h.pages > (h.n ? h.n : 1) * per)
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: more live pages than the context's pool holds (raise eslam_config.local_map_pages)");
-    }
-    return ESLAM_OK;
-}
-
-// the host's check of a chunk of table rows: every id before a kernel reads it
-SnapCheck snap_rows_check(eslam_ctx* ctx, uint32_t rw, uint32_t W, uint32_t V, uint64_t P)
-{
-    return [=](const void* d, uint64_t, uint64_t cnt) {
-        const uint32_t* v = (const uint32_t*)d;
-        for (uint64_t k = 0; k < cnt; ++k) {
-            const uint32_t* r = v + k * rw;
-            if (r[2] > 1u || r[3] > V) return snap_bad(ctx, "snapshot: a table's shadow flag or trail mark is out of range");
-            for (uint32_t s = 0; s < W; ++s)
-                if (r[4 + s] != DM_LM_NONE && r[4 + s] >= P)
-                    return snap_bad(ctx, "snapshot: a window slot names a page past the snapshot's pages");
-            for (uint32_t e = 0; e < V; ++e) {
-                const uint32_t pg = r[4 + W + 3 * e + 2];
-                if (pg != DM_LM_NONE && pg >= P) return snap_bad(ctx, "snapshot: a trail entry names a page past the snapshot's pages");
-            }
-        }
-        return (int)ESLAM_OK;
-    };
-}
-
-// the header, read and checked: no collective yet, and every rank of a sharded filter decides alike
-int snap_load_header(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h, uint64_t known_bytes)
-{
-    if (known_bytes && known_bytes < sizeof(SnapHeader)) return snap_bad(ctx, "snapshot: shorter than its header");
-    if (rd.r(0, &h, sizeof(h)) != 0) return fail(ctx, ESLAM_ERR_COMM, "snapshot: the read callback failed");
-    ++rd.chunks;
-    rd.at = sizeof(h);
-    return snap_check_header(ctx, h, known_bytes);
-}
-
-int snap_load_maps_subset(eslam_ctx* ctx, SnapReader& rd, const SnapHeader& h, uint64_t* pages_loaded);
-
-// everything behind the header.  A sharded filter reads the shared parts in full, its shard
-// [gbase, gbase + nl) of the particle arrays, and of the maps what its particles name.
-int snap_load_body(eslam_ctx* ctx, SnapReader& rd, SnapHeader& h)
-{
-    int rc = ESLAM_OK;
-    const uint64_t ncell = (uint64_t)h.width * h.height, np = h.n_patches, n = h.n;
-    const uint64_t gb = ctx->sharded ? ctx->gbase : 0, nl = ctx->sharded ? ctx->gall[ctx->comm.rank + 1] - ctx->gbase : n;
-    const bool hash = (h.sections >> kSecHash) & 1u, maps = (h.sections >> kSecMaps) & 1u;
-    uint64_t largest = std::max(std::max((ncell + 1) * 4, np * 8), std::max(n * 8, h.hash_n * 8));
-    largest = std::max(largest, std::max(h.tables * h.row_words * 4, h.pages * kPageBytes));
-    rc = snap_staging(ctx, snap_stage_bytes(rd.chunk, pad16(largest), pad16(std::max<uint64_t>(kPageBytes, (uint64_t)h.row_words * 4))));
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    free_particles(ctx);                     // whatever the context held goes first
-    const SnapCheck none;
-    // ---- the shared grid: through eslam_gpu_set_map (occ and cell_tab rebuilt as there)
-    {
-        std::vector<uint32_t> cells(ncell + 1);
-        std::vector<float2> patch(np);
-        std::vector<float> mean(np ? np : 1), stdev(np ? np : 1), height;
-        uint32_t prev = 0;
-        rc = snap_read(rd, PK_HOST, cells.data(), ncell + 1, 4, 0, [&](const void* d, uint64_t k0, uint64_t cnt) {
-            const uint32_t* c = (const uint32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k) {
-                if (c[k] < prev || c[k] > np || (k0 + k == 0 && c[k] != 0)) return snap_bad(ctx, "snapshot: the grid's cell_start is not a prefix sum");
-                prev = c[k];
-            }
-            return (int)ESLAM_OK;
-        });
-        if (!rc && prev != np) rc = snap_bad(ctx, "snapshot: cell_start[width*height] != n_patches");
-        if (!rc) rc = snap_read(rd, PK_HOST, patch.data(), np, 8, 0, none);
-        if (!rc && h.has_height) {
-            height.resize(np ? np : 1);
-            rc = snap_read(rd, PK_HOST, height.data(), np, 4, 0, none);
-        }
-        if (rc) return rc;
-        for (uint64_t k = 0; k < np; ++k) {
-            mean[k] = patch[k].x;
-            stdev[k] = patch[k].y;
-        }
-        eslam_mls_grid g;
-        memset(&g, 0, sizeof(g));
-        g.width = h.width;
-        g.height = h.height;
-        g.scale_x = h.scale_x;
-        g.scale_y = h.scale_y;
-        g.offset_x = h.offset_x;
-        g.offset_y = h.offset_y;
-        memcpy(g.global2local, h.g2l, sizeof(h.g2l));
-        g.cell_start = cells.data();
-        g.n_patches = np;
-        g.patch_mean = mean.data();
-        g.patch_stdev = stdev.data();
-        g.patch_height = h.has_height ? height.data() : nullptr;
-        rc = eslam_gpu_set_map(ctx, &g);
-        if (rc) return rc;
-    }
-    // ---- the pose hash: restored, not recomputed
-    if (hash) {
-        const uint64_t hn = h.hash_n, cap = hn ? hn : 1;
-        const uint32_t nb = h.hash_bins * h.hash_bins;
-        ctx->d_hash.reset();
-        ctx->d_hash_blist.reset();
-        ctx->hash_n = 0;
-        if (ctx->d_hash.alloc(sizeof(double) * 4 * cap) != hipSuccess || ctx->d_hash_blist.alloc(sizeof(uint32_t) * cap) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "hash pose buffers");
-        }
-        for (int f = 0; f < 4 && !rc; ++f) rc = snap_read(rd, PK_DEV, ctx->d_hash + (uint64_t)f * cap, hn, 8, 0, none);
-        std::vector<int32_t> bucket(hn);
-        std::vector<uint32_t> sizes(nb), bstart(nb + 1, 0u);
-        if (!rc) rc = snap_read(rd, PK_HOST, bucket.data(), hn, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
-            const int32_t* b = (const int32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k)
-                if (b[k] < 0 || (uint32_t)b[k] >= nb) return snap_bad(ctx, "snapshot: a hash pose's bucket is out of range");
-            return (int)ESLAM_OK;
-        });
-        if (!rc) rc = snap_read(rd, PK_HOST, sizes.data(), nb, 4, 0, none);
-        if (rc) return rc;
-        for (uint64_t i = 0; i < hn; ++i) bstart[bucket[i] + 1]++;
-        for (uint32_t b = 0; b < nb; ++b) {
-            if (bstart[b + 1] != sizes[b]) return snap_bad(ctx, "snapshot: the hash's bucket sizes do not match its buckets");
-            bstart[b + 1] += bstart[b];
-        }
-        std::vector<uint32_t> blist(cap), fill(bstart.begin(), bstart.end() - 1);
-        for (uint64_t i = 0; i < hn; ++i) blist[fill[bucket[i]]++] = (uint32_t)i;
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (hn) HIPCHK(ctx, hipMemcpy(ctx->d_hash_blist, blist.data(), sizeof(uint32_t) * hn, hipMemcpyHostToDevice));
-        ctx->hash_bucket.swap(bucket);
-        ctx->hash_bstart.swap(bstart);
-        ctx->hash_n = hn;
-        ctx->has_hash = true;
-    }
-    // ---- the particles (the eight arrays of the current buffer, into buffer 0)
-    rc = alloc_particles(ctx, nl);
-    if (rc) return rc;
-    if (maps && !ctx->lm_ready) return fail(ctx, ESLAM_ERR_HIP, "snapshot: per-particle maps not allocated");
-    {
-        const DevState& s = ctx->st[0];
-        double* f7[7] = {s.x, s.y, s.th, s.z, s.zs, s.w, s.mprob};
-        if (ctx->sharded) {
-            for (int f = 0; f < 7 && !rc; ++f) rc = snap_read_slice(rd, PK_DEV, f7[f], n, gb, nl, 8, none);
-            if (!rc) rc = snap_read_slice(rd, PK_DEV, s.flags, n, gb, nl, 1, none);
-        } else {
-            for (int f = 0; f < 7 && !rc; ++f) rc = snap_read(rd, PK_DEV, f7[f], n, 8, 0, none);
-            if (!rc) rc = snap_read(rd, PK_DEV, s.flags, n, 1, 0, none);
-        }
-        if (rc) return rc;
-    }
-    // ---- the scalars
-    SnapScalars sc;
-    rc = snap_read(rd, PK_HOST, &sc, sizeof(sc), 1, 0, none);
-    if (!rc) rc = reset_ctl_for_new_particles(ctx, sc.wexp);
-    if (rc) return rc;
-    {
-        Ctl& ctl = *ctx->ctl_host;           // as reset_ctl_for_new_particles read it
-        ctl.minstd = sc.minstd;
-        ctl.max_weight = sc.max_weight;
-        ctl.update_count = sc.update_count;
-        ctl.inv_n = sc.inv_n;
-        if (maps) {
-            ctl.pg_cursor = 0;
-            ctl.pg_nfree = ctx->lm.npages - h.pages;
-            ctl.pg_total = 0;
-            ctl.pg_gc = 0;
-        }
-        ctx->proj_event = sc.rng.project_count;
-        ctx->init_event = sc.rng.init_count;
-        *ctx->hash_ev = sc.rng.hash_count;
-        memcpy(ctx->ud_pose, sc.rng.ud_pose, sizeof(ctx->ud_pose));
-        memcpy(ctx->libcp->r, sc.rng.libc_rand, sizeof(sc.rng.libc_rand));
-        ctx->libcp->i = sc.rng.libc_rand_pos % 34u;
-        rc = write_ctl(ctx);
-        if (rc) return rc;
-        ctx->dbg_valid = false;
-    }
-    // ---- the per-particle maps of a sharded filter: this rank's subset, then the page counters
-    if (maps && ctx->sharded) {
-        uint64_t ploc = 0;
-        rc = snap_load_maps_subset(ctx, rd, h, &ploc);
-        if (!rc) rc = read_ctl(ctx);
-        if (rc) return rc;
-        ctx->ctl_host->pg_nfree = ctx->lm.npages - ploc;
-        rc = write_ctl(ctx);
-        if (rc) return rc;
-    }
-    // ---- the per-particle maps: table k into pool entry k, page k into pool entry k
-    if (maps && !ctx->sharded) {
-        const uint64_t T = h.tables, P = h.pages;
-        const uint32_t rw = h.row_words, W = h.wx * h.wy, V = h.local_map_trail;
-        rc = snap_read(rd, PK_DEV, ctx->st[0].sid, n, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
-            const uint32_t* v = (const uint32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k)
-                if (v[k] >= T) return snap_bad(ctx, "snapshot: a particle names a table past the snapshot's tables");
-            return (int)ESLAM_OK;
-        });
-        if (!rc) rc = snap_read(rd, PK_TABLES, nullptr, T, (uint64_t)rw * 4, rw, snap_rows_check(ctx, rw, W, V, P));
-        if (!rc) rc = snap_read(rd, PK_OWNER, nullptr, P, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
-            const uint32_t* v = (const uint32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k)
-                if (v[k] != DM_LM_NONE && v[k] >= T) return snap_bad(ctx, "snapshot: a page's owner is past the snapshot's tables");
-            return (int)ESLAM_OK;
-        });
-        if (!rc) rc = snap_read(rd, PK_DEV, ctx->lm.page, P, kPageBytes, 0, none);
-        if (rc) return rc;
-        HIPCHK(ctx, eslam_launch_snap_finish(&ctx->lm, T, P, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return ESLAM_OK;
-}
-
-// f(a, b, local) for every run [a, b) of set bits below `limit`, ascending; local: the set bits below a
-template <typename F>
-int snap_for_runs(const std::vector<uint32_t>& bits, uint64_t limit, F f)
-{
-    uint64_t i = 0, local = 0;
-    auto bit = [&](uint64_t k) { return (bits[k >> 5] >> (k & 31)) & 1u; };
-    while (i < limit) {
-        if (!(i & 31) && bits[i >> 5] == 0u) {
-            i += 32;
-            continue;
-        }
-        if (!bit(i)) {
-            ++i;
-            continue;
-        }
-        uint64_t b = i + 1;
-        while (b < limit) {
-            if (!(b & 31) && bits[b >> 5] == 0xffffffffu) b += 32;
-            else if (bit(b)) ++b;
-            else break;
-        }
-        if (b > limit) b = limit;
-        if (const int rc = f(i, b, local)) return rc;
-        local += b - i;
-        i = b;
-    }
-    return ESLAM_OK;
-}
-
-// The per-particle maps of a sharded load ("Sharded filters"): the tables this
-// rank's particles name, in the snapshot's order, into pool tables 0, 1, ...; the pages those
-// tables name into pool pages 0, 1, ...  Two bitmaps over the snapshot's ids, ranked by
-// popcount on the device; the host walks their runs of set bits and reads each run's rows,
-// owner words and pages.  With every bit set this is the one-GPU load: entry k into pool entry k.
-int snap_load_maps_subset(eslam_ctx* ctx, SnapReader& rd, const SnapHeader& h, uint64_t* pages_loaded)
-{
-    const uint64_t T = h.tables, P = h.pages, n = h.n, gb = ctx->gbase, nl = ctx->n;
-    const uint32_t rw = h.row_words, W = h.wx * h.wy, V = h.local_map_trail;
-    const uint64_t tw = (T + 31) / 32, pw = (P + 31) / 32;
-    const uint64_t off_sid = rd.at, off_tab = off_sid + pad16(n * 4), off_own = off_tab + pad16(T * rw * 4), off_pg = off_own + pad16(P * 4);
-    const SnapCheck none;
-    Dev<uint32_t> scratch;                   // dropped with the call
-    const uint64_t words = tw + (tw + 1) + pw + (pw + 1);
-    if (scratch.alloc(words * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY, "snapshot: no device memory for the subset's bitmaps");
-    }
-    HIPCHK(ctx, hipMemsetAsync(scratch, 0, words * 4, ctx->stream));
-    SnapSubset sub;
-    sub.tbits = scratch;
-    sub.tpre = sub.tbits + tw;
-    sub.pbits = sub.tpre + tw + 1;
-    sub.ppre = sub.pbits + pw;
-    sub.tables = T;
-    sub.pages = P;
-    // the scratch goes only once the stream is idle, whichever way the call ends
-    struct Idle {
-        hipStream_t s;
-        ~Idle() { (void)hipStreamSynchronize(s); }
-    } idle{ctx->stream};
-    // ---- tables: the bits of this shard's names, their ranks, the names rewritten
-    uint32_t* sid = ctx->st[0].sid;
-    int rc = snap_read_slice(rd, PK_DEV, sid, n, gb, nl, 4, [&](const void* d, uint64_t, uint64_t cnt) {
-        const uint32_t* v = (const uint32_t*)d;
-        for (uint64_t k = 0; k < cnt; ++k)
-            if (v[k] >= T) return snap_bad(ctx, "snapshot: a particle names a table past the snapshot's tables");
-        return (int)ESLAM_OK;
-    });
-    if (rc) return rc;
-    HIPCHK(ctx, eslam_launch_snap_mark_ids(sid, nl, sub.tbits, T, ctx->stream));
-    HIPCHK(ctx, eslam_launch_snap_rank_bits(sub.tbits, tw, sub.tpre, ctx->stream));
-    HIPCHK(ctx, eslam_launch_snap_rank_sid(sid, nl, &sub, ctx->stream));
-    std::vector<uint32_t> tbits(tw + 1), pbits(pw + 1);
-    uint32_t tloc = 0, ploc = 0;
-    HIPCHK(ctx, hipMemcpyAsync(tbits.data(), sub.tbits, tw * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&tloc, sub.tpre + tw, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (tloc > ctx->lm.ntables || tloc > nl) return fail(ctx, ESLAM_ERR_HIP, "snapshot: more tables named than particles");
-    // ---- rows: each run of named tables into pool tables local(run start)..., page ids still the snapshot's
-    const SnapCheck rows = snap_rows_check(ctx, rw, W, V, P);
-    rc = snap_for_runs(tbits, T, [&](uint64_t a, uint64_t b, uint64_t local) {
-        rd.dst0 = local;
-        return snap_read_part(rd, PK_TABLES, nullptr, b - a, (uint64_t)rw * 4, rw, rows, off_tab + a * rw * 4, 0);
-    });
-    if (rc) return rc;
-    // ---- pages: the bits of what those rows name, their ranks; this rank's pool must hold them
-    HIPCHK(ctx, eslam_launch_snap_mark_rows(&ctx->lm, tloc, sub.pbits, P, ctx->stream));
-    HIPCHK(ctx, eslam_launch_snap_rank_bits(sub.pbits, pw, sub.ppre, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(pbits.data(), sub.pbits, pw * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(&ploc, sub.ppre + pw, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ploc > ctx->lm.npages)
-        return fail(ctx, ESLAM_ERR_OUT_OF_MEMORY,
-                    "snapshot: more live pages than this rank's pool holds (raise eslam_config.local_map_pages)");
-    HIPCHK(ctx, eslam_launch_snap_renumber_tables(&ctx->lm, tloc, &sub, ctx->stream));
-    rd.sub = &sub;
-    rc = snap_for_runs(pbits, P, [&](uint64_t a, uint64_t b, uint64_t local) {
-        rd.dst0 = local;
-        return snap_read_part(rd, PK_OWNER, nullptr, b - a, 4, 0, [&](const void* d, uint64_t, uint64_t cnt) {
-            const uint32_t* v = (const uint32_t*)d;
-            for (uint64_t k = 0; k < cnt; ++k)
-                if (v[k] != DM_LM_NONE && v[k] >= T) return snap_bad(ctx, "snapshot: a page's owner is past the snapshot's tables");
-            return (int)ESLAM_OK;
-        }, off_own + a * 4, 0);
-    });
-    rd.sub = nullptr;
-    rd.dst0 = 0;
-    if (rc) return rc;
-    // consecutive set bits are consecutive local ids: a run of pages is one plain copy
-    rc = snap_for_runs(pbits, P, [&](uint64_t a, uint64_t b, uint64_t local) {
-        return snap_read_part(rd, PK_DEV, (char*)ctx->lm.page + local * kPageBytes, b - a, kPageBytes, 0, none, off_pg + a * kPageBytes, 0);
-    });
-    if (rc) return rc;
-    HIPCHK(ctx, eslam_launch_snap_finish(&ctx->lm, tloc, ploc, ctx->stream));
-    rd.at = off_pg + P * kPageBytes;
-    *pages_loaded = ploc;
-    return ESLAM_OK;
-}
-
-// positional: the source is read by offset (a sharded filter: a collective, and each rank reads
-// its part only); else in the blob's order, every byte once
-int snap_load(eslam_ctx* ctx, const SnapSource& r, bool positional, uint64_t chunk_bytes, eslam_snapshot_info* info, uint64_t known_bytes)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx || !r) return ESLAM_ERR_INVALID_ARG;
-    if (ctx->sharded && !positional) return fail(ctx, ESLAM_ERR_UNSUPPORTED, kSnapStreamSharded);
-    if (chunk_bytes && chunk_bytes < 4096) return fail(ctx, ESLAM_ERR_INVALID_ARG, "snapshot: chunk_bytes is 0 or at least 4096");
-    SnapReader rd;
-    rd.ctx = ctx;
-    rd.r = r;
-    rd.chunk = (chunk_bytes ? chunk_bytes : kSnapDefaultChunk) & ~(uint64_t)15;
-    SnapHeader h;
-    memset(&h, 0, sizeof(h));
-    int rc = ESLAM_OK;
-    if (ctx->sharded) {
-        // the header decides alike on every rank, before the first collective
-        rc = snap_load_header(ctx, rd, h, known_bytes);
-        if (rc) {
-            const std::string msg = ctx->err;
-            (void)hipStreamSynchronize(ctx->stream);
-            free_particles(ctx);
-            ctx->err = msg;
-            return rc;
-        }
-        rc = settle(ctx);
-    } else {
-        rc = settle(ctx);
-        if (rc) return rc;
-        rc = snap_load_header(ctx, rd, h, known_bytes);
-    }
-    if (!rc) rc = snap_load_body(ctx, rd, h);
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-    rc = agree(ctx, rc, "snapshot");                // sharded: no rank goes on with a filter another rank could not load
-    if (rc) {
-        // the context reads as "no particles"; set_map + init_* or another load starts it over
-        const std::string msg = ctx->err;
-        (void)hipStreamSynchronize(ctx->stream);
-        free_particles(ctx);
-        ctx->err = msg;
-        return rc;
-    }
-    snap_fill_info(h, rd.chunks, info);
-    return ESLAM_OK;
-}
-
-struct SnapMem {
-    char* p;
-    uint64_t left;
-};
-int snap_mem_write(void* user, const void* data, uint64_t bytes)
-{
-    SnapMem* m = (SnapMem*)user;
-    if (bytes > m->left) return 1;
-    memcpy(m->p, data, bytes);
-    m->p += bytes;
-    m->left -= bytes;
-    return 0;
-}
-int snap_mem_read(void* user, void* data, uint64_t bytes)
-{
-    SnapMem* m = (SnapMem*)user;
-    if (bytes > m->left) return 1;
-    memcpy(data, m->p, bytes);
-    m->p += bytes;
-    m->left -= bytes;
-    return 0;
-}
-
-SnapSink snap_stream_sink(eslam_write_fn w, void* user)
-{
-    if (!w) return SnapSink();
-    return [w, user](uint64_t, const void* data, uint64_t bytes) { return w(user, data, bytes); };
-}
-SnapSource snap_stream_source(eslam_read_fn r, void* user)
-{
-    if (!r) return SnapSource();
-    return [r, user](uint64_t, void* data, uint64_t bytes) { return r(user, data, bytes); };
-}
-
-}  // namespace
-
-// a collective on a sharded filter
-extern "C" int eslam_gpu_snapshot_size(eslam_ctx* ctx, eslam_snapshot_info* info)
-{
-    if (info) memset(info, 0, sizeof(*info));
-    if (!ctx || !info) return ESLAM_ERR_INVALID_ARG;
-    SnapPlan pl;
-    const int rc = snap_plan(ctx, pl);
-    if (rc) return rc;
-    snap_fill_info(pl.h, snap_chunk_count(pl.pieces, kSnapDefaultChunk), info);
-    return ESLAM_OK;
-}
-
-extern "C" int eslam_gpu_save_stream(eslam_ctx* ctx, eslam_write_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
-{
-    return snap_save(ctx, snap_stream_sink(w, user), false, chunk_bytes, info, ~0ull);
-}
-
-extern "C" int eslam_gpu_load_stream(eslam_ctx* ctx, eslam_read_fn r, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
-{
-    return snap_load(ctx, snap_stream_source(r, user), false, chunk_bytes, info, 0);
-}
-
-extern "C" int eslam_gpu_save_at(eslam_ctx* ctx, eslam_pwrite_fn w, void* user, uint64_t chunk_bytes, eslam_snapshot_info* info)
-{
-    SnapSink sink;
-    if (w) sink = [w, user](uint64_t off, const void* data, uint64_t bytes) { return w(user, off, data, bytes); };
-    return snap_save(ctx, sink, true, chunk_bytes, info, ~0ull);
-}
-
-extern "C" int eslam_gpu_load_at(eslam_ctx* ctx, eslam_pread_fn r, void* user, uint64_t known_bytes, uint64_t chunk_bytes,
-                                 eslam_snapshot_info* info)
-{
-    SnapSource src;
-    if (r) src = [r, user](uint64_t off, void* data, uint64_t bytes) { return r(user, off, data, bytes); };
-    return snap_load(ctx, src, true, chunk_bytes, info, known_bytes);
-}
-
-extern "C" int eslam_gpu_save(eslam_ctx* ctx, void* buf, uint64_t capacity, uint64_t chunk_bytes, eslam_snapshot_info* info)
-{
-    if (!buf) return ESLAM_ERR_INVALID_ARG;
-    SnapMem m{(char*)buf, capacity};
-    return snap_save(ctx, snap_stream_sink(snap_mem_write, &m), false, chunk_bytes, info, capacity);
-}
-
-// on a sharded filter every rank holds the whole blob and reads its part of it
-extern "C" int eslam_gpu_load(eslam_ctx* ctx, const void* buf, uint64_t bytes, uint64_t chunk_bytes, eslam_snapshot_info* info)
-{
-    if (!buf) return ESLAM_ERR_INVALID_ARG;
-    if (ctx && ctx->sharded) {
-        const char* p = (const char*)buf;
-        const SnapSource src = [p, bytes](uint64_t off, void* data, uint64_t b) {
-            if (off > bytes || b > bytes - off) return 1;
-            memcpy(data, p + off, b);
-            return 0;
-        };
-        return snap_load(ctx, src, true, chunk_bytes, info, bytes ? bytes : 1);
-    }
-    SnapMem m{(char*)const_cast<void*>(buf), bytes};
-    return snap_load(ctx, snap_stream_source(snap_mem_read, &m), false, chunk_bytes, info, bytes ? bytes : 1);
-}
-

@@ -10,7 +10,7 @@
 //                  rows in order, the wave butterfly)
 //   k_gmm_tree     one level of the fixed pairwise tree over the chunk records
 //
-// The host side (eslam_gpu_fit_pose_gmm, eslam_ctx.hip) sequences the passes, runs the M-step
+// The host side (eslam_gpu_fit_pose_gmm, eslam_host_stats.hip) sequences the passes, runs the M-step
 // (dm_gmm_mstep) and the stop test, and reads one record back per pass.  The arithmetic of a
 // particle is eslam_detmath.h's (dm_gmm_*), shared with the CPU restatement, and the file is
 // compiled with -ffp-contract=off: the fit equals tests/c/gmm_ref.c bit for bit.

@@ -75,6 +75,17 @@ int eslam_host::host_allgather(eslam_ctx* ctx, const void* send, void* recv, uin
     return ESLAM_OK;
 }
 
+int eslam_host::same_on_every_rank(eslam_ctx* ctx, const uint64_t* mine, uint32_t nwords, const char* msg)
+{
+    uint64_t all[kHostXBytes / 8 * kMaxRanks] = {};
+    if (nwords * 8ull > kHostXBytes) return fail(ctx, ESLAM_ERR_INVALID_ARG, "host_allgather: more words than set_comm sized the buffer for");
+    const int rc = host_allgather(ctx, mine, all, nwords * 8ull);
+    if (rc) return rc;
+    for (int r = 0; r < ctx->comm.nranks; ++r)
+        if (memcmp(all + (uint64_t)nwords * r, mine, nwords * 8ull) != 0) return fail(ctx, ESLAM_ERR_INVALID_ARG, msg);
+    return ESLAM_OK;
+}
+
 int eslam_host::agree(eslam_ctx* ctx, int rc, const char* what)
 {
     if (!ctx->sharded) return rc;
@@ -94,17 +105,41 @@ int eslam_host::agree(eslam_ctx* ctx, int rc, const char* what)
     return ESLAM_OK;
 }
 
+void eslam_host::chunk_shape(const uint64_t* gall, int G, uint32_t J, uint64_t* nch, uint64_t* maxch, uint64_t* total)
+{
+    const uint64_t csz = 64ull * J;
+    *maxch = 1;
+    *total = 0;
+    for (int r = 0; r < G; ++r) {
+        const uint64_t c = (gall[r + 1] - gall[r] + csz - 1) / csz;
+        if (nch) nch[r] = c;
+        *maxch = c > *maxch ? c : *maxch;
+        *total += c;
+    }
+}
+
+int eslam_host::gather_chunks(eslam_ctx* ctx, const uint64_t* nch, uint64_t maxch, uint32_t R, const double* mine, double* all,
+                              double* a)
+{
+    const int rc = comm_allgather(ctx, mine, all, maxch * R * sizeof(double));
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    uint64_t off = 0;
+    for (int r = 0; r < ctx->comm.nranks && e == hipSuccess; ++r) {
+        if (nch[r]) e = hipMemcpyAsync(a + off * R, all + (uint64_t)r * maxch * R, nch[r] * R * sizeof(double),
+                                       hipMemcpyDeviceToDevice, ctx->stream);
+        off += nch[r];
+    }
+    if (e != hipSuccess) return fail(ctx, ESLAM_ERR_HIP, hipGetErrorString(e));
+    return ESLAM_OK;
+}
+
 // sharded getCentroid: this rank's chunk records (padded to the largest shard), all ranks'
 // (G x that), and the tree's two ping-pong levels over the global chunks; 5 doubles a record
 uint64_t eslam_host::centroid_bytes(const uint64_t* gall, int G, uint32_t J)
 {
-    const uint64_t csz = 64ull * J;
-    uint64_t maxch = 1, total = 0;
-    for (int r = 0; r < G; ++r) {
-        const uint64_t c = (gall[r + 1] - gall[r] + csz - 1) / csz;
-        maxch = c > maxch ? c : maxch;
-        total += c;
-    }
+    uint64_t maxch, total;
+    chunk_shape(gall, G, J, nullptr, &maxch, &total);
     return (maxch + (uint64_t)G * maxch + 2 * (total ? total : 1)) * 5 * sizeof(double);
 }
 

@@ -12,7 +12,7 @@
 //
 // Minima, maxima, integer sums, ORs and a population count do not depend on the order anything
 // arrives in, so the count is the same bits on one GPU, on a sharded filter and in
-// tests/c/kld_ref.c.  The host side (eslam_gpu_kld_count, eslam_ctx.hip) reads the box between
+// tests/c/kld_ref.c.  The host side (eslam_gpu_kld_count, eslam_host_stats.hip) reads the box between
 // pass 1 and pass 2 and computes the bound.  A particle's arithmetic is eslam_detmath.h's, shared
 // with the CPU restatement; the file is compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip, eslam_host_comm.hip), declared once.  All twelve .hip files include it, the defining one too: the
+// (eslam_ctx.hip and the eslam_host_*.hip files), declared once.  All fifteen .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once

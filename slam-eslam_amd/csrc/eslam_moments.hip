@@ -12,7 +12,7 @@
 //                       getCentroid's order (a lane's rows in order, the wave butterfly)
 //
 // The fixed pairwise tree over the chunk records is eslam_gmm.hip's (eslam_launch_gmm_tree).  The
-// host side (eslam_gpu_pose_moments, eslam_ctx.hip) sequences the passes and forms the mean
+// host side (eslam_gpu_pose_moments, eslam_host_stats.hip) sequences the passes and forms the mean
 // (dm_mom_mean) and the covariance (dm_mom_cov).  The arithmetic of a particle is
 // eslam_detmath.h's (dm_mom_*), shared with the CPU restatement, and the file is compiled with
 // -ffp-contract=off: the result equals tests/c/moments_ref.c bit for bit.
