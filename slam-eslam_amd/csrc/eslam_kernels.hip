@@ -174,13 +174,46 @@ __device__ __forceinline__ uint64_t stamp_now()
     return t;
 }
 __device__ uint32_t g_stamps_grid[3];    // gridDim.x of the last stamped K1 / K3 launch
+// blockIdx.x through an empty asm: each stamp forms its address anew, so none is kept in VGPRs
+// from one stamp to the next, across the phase between them (K1's bench instantiation: 99 VGPRs
+// with the addresses kept, 98 without; -DESLAM_K1_WPE=5 holds it to the product's 96 and five
+// waves a SIMD, with 24 bytes of scratch)
+__device__ __forceinline__ uint32_t stamp_block()
+{
+    uint32_t b = blockIdx.x;
+    asm volatile("" : "+s"(b));
+    return b;
+}
 #define ESLAM_STAMP(arr, k) \
     do { \
-        if (threadIdx.x == 0 && blockIdx.x < kStampBlocks) arr[blockIdx.x][(k)] = stamp_now(); \
+        const uint32_t sb_ = stamp_block(); \
+        if (threadIdx.x == 0 && sb_ < kStampBlocks) arr[sb_][(k)] = stamp_now(); \
         if ((k) == 0 && threadIdx.x == 0 && blockIdx.x == 0) g_stamps_grid[&arr == &g_stamps_k1 ? 0 : &arr == &g_stamps_k3 ? 1 : 2] = gridDim.x; \
+    } while (0)
+// K1 also stamps per wave (lane 0 of each wave, slots below), all three outside the row loop
+// and stored at once, so no stamp is live across the rows and the diagnostic kernel keeps the
+// product's registers.  The placement word is HW_ID (wave slot, SIMD, CU, SH, SE) | XCC_ID << 32.
+constexpr uint32_t kWaveStampSlots = 4;  // start, first row starts, last row done, placement
+__device__ uint64_t g_stamps_k1w[kStampBlocks * kWaves][kWaveStampSlots];
+// (K1's stamps test its own lane and wave, which it keeps anyway, not threadIdx.x)
+#define ESLAM_STAMP_K1(k) \
+    do { \
+        const uint32_t sb_ = stamp_block(); \
+        if (lane == 0 && wave == 0 && sb_ < kStampBlocks) g_stamps_k1[sb_][(k)] = stamp_now(); \
+    } while (0)
+#define ESLAM_STAMP_WAVE(k) \
+    do { \
+        const uint32_t sb_ = stamp_block(); \
+        if (lane == 0 && sb_ < kStampBlocks) { \
+            uint64_t* ws_ = g_stamps_k1w[sb_ * kWaves + wave]; \
+            ws_[(k)] = stamp_now(); \
+            if ((k) == 0) ws_[3] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32); \
+        } \
     } while (0)
 #else
 #define ESLAM_STAMP(arr, k) do { } while (0)
+#define ESLAM_STAMP_K1(k) do { } while (0)
+#define ESLAM_STAMP_WAVE(k) do { } while (0)
 #endif
 // Diagnostic builds only (-DESLAM_DRAW_STATS, tools/stamps.py): how many waves counted
 // stratified draws (wave_counts) and how many of them had to evaluate the draws.  Kept apart
@@ -987,16 +1020,48 @@ __device__ __forceinline__ uint32_t decode_source(uint32_t v, uint32_t multi, co
 // stores and agent-coherent sc1 stores measured beside them).  Same values, same bits.
 #define K1_ST(p, v) __builtin_nontemporal_store((v), (p))
 
+// K1's waves paced by rows done.  A launch of one generation starts every wave
+// of a SIMD together on the same J rows, and at equal priority the SIMD serves its oldest wave
+// first: the waves finish one after the other and the SIMD runs its last rows with few waves
+// to hide latency.  Each wave sets its priority from its own progress at the top of a row, so
+// a wave that is behind outranks one that is ahead.  0: nothing is emitted; 1: four bands,
+// level 3 - min(3, 4 j / J); 2: two bands, level 1 for j < J / 2; 3: the control, the bands of
+// 1 reversed (measured once, never shipped).  j and J are scalars and s_setprio takes an
+// immediate: a scalar switch, run only where the band changes.  J == 1 emits nothing.
+#ifndef ESLAM_K1_PACE
+#define ESLAM_K1_PACE 1
+#endif
+__device__ __forceinline__ uint32_t k1_pace_level(uint32_t j, uint32_t J)
+{
+    if (ESLAM_K1_PACE == 2) return j < (J >> 1) ? 1u : 0u;
+    // min(3, 4 j / J) without the division: 4 j / J >= k  <=>  4 j >= k J
+    const uint32_t band = (4u * j >= J ? 1u : 0u) + (4u * j >= 2u * J ? 1u : 0u) + (4u * j >= 3u * J ? 1u : 0u);
+    return ESLAM_K1_PACE == 3 ? band : 3u - band;
+}
+__device__ __forceinline__ void k1_set_priority(uint32_t level)
+{
+    switch (level) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 #ifndef ESLAM_K1D_WPE
 #define ESLAM_K1D_WPE 3                  // K1 DELTA: three waves a SIMD hold the batched own-map lookups unspilled
 #endif
+#ifndef ESLAM_K1_WPE
+#define ESLAM_K1_WPE 1                    // the compiler's own choice; 5 asks a diagnostic build to keep five waves a SIMD
+#endif
 template <bool PROJECT, bool WEIGHT, int MAXP, bool BATCH, bool DELTA = false, bool UNG = false>
-__global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_waves_per_eu(DELTA ? ESLAM_K1D_WPE : 1))) k_project_weight(K1Args a)
+__global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_waves_per_eu(DELTA ? ESLAM_K1D_WPE : ESLAM_K1_WPE))) k_project_weight(K1Args a)
 {
     // Inside the particle loop every argument is read by a scalar load where it is used
     // (KOFF offsets into the K1Args kernel argument); "a." appears only outside the loop.
     ESLAM_STAMP(g_stamps_k1, 0);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    ESLAM_STAMP_WAVE(0);
     const uint64_t n = a.p.n;
     const uint32_t J = a.p.J;
     const uint64_t csz = 64ull * J;
@@ -1045,7 +1110,7 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
         }
         __syncthreads();
     }
-    ESLAM_STAMP(g_stamps_k1, 1);
+    ESLAM_STAMP_K1(1);
 
     // order-free per-lane state, kept across chunks
     double maxm = 0.0;
@@ -1090,9 +1155,21 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
     for (int k = 0; k < (kRegAcc ? DM_NBUCKETS : 1); ++k) accA[k] = accB[k] = 0.0;
     double accSW = 0.0;
 
+    ESLAM_STAMP_WAVE(1);
     for (uint32_t j = 0; j < J; ++j) {
         const uint64_t row0 = lbase + 64ull * j;
         if (row0 >= n) break;
+        if (ESLAM_K1_PACE != 0) {
+            // nothing of this is live across the row: the band is recomputed from j and J.  J
+            // passes through an empty asm, or the compiler hoists 2 J, 3 J and J > 1 out of the
+            // loop into four long-lived SGPRs (one spilled: 97 VGPRs, four waves)
+            uint32_t Jp = J;
+            asm volatile("" : "+s"(Jp));
+            if (Jp > 1u) {
+                const uint32_t level = k1_pace_level(j, Jp);
+                if (j == 0 || level != k1_pace_level(j - 1u, Jp)) k1_set_priority(level);
+            }
+        }
         const uint64_t i = row0 + lane;
         uint32_t src = (uint32_t)i;
         const gmem<const Rec>* rc = nullptr;
@@ -1374,6 +1451,10 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
             }
         }
     }
+    // back to the launch's priority: a short last chunk leaves the loop in a raised band, and
+    // the block's flush below meets its other waves at a barrier
+    if (ESLAM_K1_PACE != 0 && J > 1u) __builtin_amdgcn_s_setprio(0);
+    ESLAM_STAMP_WAVE(2);
 
     if (WEIGHT) {
         // chunk totals (sub-lane sums + the xor butterfly of the sum contract) -> exact fixed
@@ -1457,7 +1538,7 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
     }
     }
 
-    ESLAM_STAMP(g_stamps_k1, 2);
+    ESLAM_STAMP_K1(2);
     Shard* shb = a.shards + (blockIdx.x % kNShard);
     // bounding box of the cloud for the next step's LDS window (maxima, any order): the four
     // maxima in one transposed butterfly (at distances 32 and 16 each lane pair keeps half of
@@ -1532,7 +1613,7 @@ __global__ void __launch_bounds__(kBlock) ESLAM_K1_ATTR __attribute__((amdgpu_wa
         if (f & 0x7fffffffu) atomicOr((unsigned long long*)&sh->flags, (unsigned long long)(f & 0x7fffffffu));
         if (f >> 31) atomicOr((unsigned long long*)&sh->err, 1ull);
     }
-    ESLAM_STAMP(g_stamps_k1, 3);
+    ESLAM_STAMP_K1(3);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -5175,15 +5256,28 @@ extern "C" int eslam_debug_k1_occupancy(int* blocks_per_cu, int lds)
 // early then leaves zeros, not an older launch's stamps)
 extern "C" int eslam_gpu_debug_stamps_clear(void)
 {
-    void *a = nullptr, *b = nullptr, *c = nullptr, *g = nullptr;
+    void *a = nullptr, *b = nullptr, *c = nullptr, *g = nullptr, *w = nullptr;
     if (hipGetSymbolAddress(&a, HIP_SYMBOL(g_stamps_k1)) != hipSuccess || hipGetSymbolAddress(&b, HIP_SYMBOL(g_stamps_k3)) != hipSuccess ||
-        hipGetSymbolAddress(&c, HIP_SYMBOL(g_stamps_mg)) != hipSuccess || hipGetSymbolAddress(&g, HIP_SYMBOL(g_stamps_grid)) != hipSuccess)
+        hipGetSymbolAddress(&c, HIP_SYMBOL(g_stamps_mg)) != hipSuccess || hipGetSymbolAddress(&g, HIP_SYMBOL(g_stamps_grid)) != hipSuccess ||
+        hipGetSymbolAddress(&w, HIP_SYMBOL(g_stamps_k1w)) != hipSuccess)
         return -1;
     const size_t bytes = sizeof(uint64_t) * kStampBlocks * kStampSlots;
     if (hipMemset(a, 0, bytes) != hipSuccess || hipMemset(b, 0, bytes) != hipSuccess || hipMemset(c, 0, bytes) != hipSuccess ||
-        hipMemset(g, 0, 12) != hipSuccess)
+        hipMemset(g, 0, 12) != hipSuccess || hipMemset(w, 0, sizeof(uint64_t) * kStampBlocks * kWaves * kWaveStampSlots) != hipSuccess)
         return -1;
     return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+// copy the per-wave stamps of the last K1 launch (kWaveStampSlots words per wave, wave w of
+// block b at b * kWaves + w); returns the launch's block count, or -1
+extern "C" int64_t eslam_gpu_debug_stamps_k1_waves(uint64_t* out, uint64_t waves)
+{
+    if (waves > (uint64_t)kStampBlocks * kWaves) waves = (uint64_t)kStampBlocks * kWaves;
+    uint32_t grid[3] = {0, 0, 0};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps_k1w), waves * kWaveStampSlots * 8) != hipSuccess ||
+        hipMemcpyFromSymbol(grid, HIP_SYMBOL(g_stamps_grid), sizeof(grid)) != hipSuccess)
+        return -1;
+    return (int64_t)grid[0];
 }
 
 // copy the stamps of the last K1 (which = 1), K3 (which = 3) or map merge (which = 5) launch; returns that launch's

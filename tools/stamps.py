@@ -6,7 +6,11 @@ Runs the bench workload (flat map, resample forced) for `warmup` steps plus one,
 per phase of the last step's K1 and K3 (the stamps are cleared before it, and the block
 counts are the launches' own), the median / max block duration and when the last block left
 the phase (from the kernel's first block start).  Read the shares, not the
-lengths: the stamps' waits make the build slower than the product."""
+lengths: the stamps' waits make the build slower than the product.
+K1 also stamps every wave (start, first row, last row done, and where it ran): the report adds
+the distribution of the waves' end times, per SIMD the end time by start rank, and the
+resident-wave count over time.  For K1 at the product's five waves per SIMD build with
+-DESLAM_STAMPS -DESLAM_K1_WPE=5 (the stamps alone take the bench instantiation to 98 VGPRs)."""
 import ctypes as C
 import os
 import sys
@@ -44,6 +48,63 @@ def report(name, st, phases, nblocks):
     print(f"  block starts: median {np.median(starts):.2f}, p90 {np.percentile(starts, 90):.2f}, last {starts.max():.2f} us")
 
 
+def pct(v, qs=(0, 10, 25, 50, 75, 90, 100)):
+    return "  ".join(f"p{q}={np.percentile(v, q):.2f}" for q in qs)
+
+
+def report_waves(name, ws, nblocks):
+    """K1's per-wave stamps (start, first row starts, last row done, placement): when the waves
+    end, how a SIMD's waves end by the order in which they started, and how many waves are
+    resident over time.  Times in us from the first wave's start; a wave counts as resident
+    from its start to the end of its last row (the block's flush after it is not stamped per
+    wave).  Placement: HW_ID wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13], and
+    XCC_ID [3:0] in the upper word."""
+    ws = ws[:nblocks * 4].astype(np.int64)
+    ran = np.all(ws[:, :3] > 0, axis=1)              # a wave without a chunk stamps its start only
+    ws = ws[ran]
+    if not len(ws):
+        print(f"== {name}: no wave stamped its rows")
+        return
+    t0 = ws[:, 0].min()
+    start, rows0, end = ((ws[:, k] - t0) * 10e-3 for k in range(3))
+    hw, xcc = ws[:, 3] & 0xffffffff, (ws[:, 3] >> 32) & 0xf
+    simd = (xcc << 16) | (hw & 0xff30)               # XCC, SE, SH, CU, SIMD
+    span = end.max()
+    life = end - start
+    print(f"== {name}: {len(ws)} waves with rows, span {span:.2f} us; mean wave lifetime {life.mean():.2f} us "
+          f"= {life.mean() / span:.3f} of the span")
+    print(f"  wave starts       {pct(start)}")
+    print(f"  first row starts  {pct(rows0)}")
+    print(f"  wave ends         {pct(end)}")
+    print(f"  rows phase        {pct(end - rows0)}")
+    keys, inv, counts = np.unique(simd, return_inverse=True, return_counts=True)
+    hist = {int(c): int(np.count_nonzero(counts == c)) for c in np.unique(counts)}
+    print(f"  {len(keys)} SIMDs seen (XCC, SE, SH, CU, SIMD); waves per SIMD -> SIMDs: {hist}")
+    depth = int(np.bincount(counts).argmax())        # the usual number of waves a SIMD ran
+    by_rank = [[] for _ in range(depth)]
+    spread, gens = [], 0
+    for s in np.nonzero(counts == depth)[0]:
+        idx = np.nonzero(inv == s)[0]
+        idx = idx[np.argsort(start[idx], kind="stable")]
+        if np.any(start[idx][1:] >= end[idx].min()):  # a later generation refilled a slot
+            gens += 1
+            continue
+        for r, i in enumerate(idx):
+            by_rank[r].append(end[i])
+        spread.append(end[idx].max() - end[idx].min())
+    if spread:
+        print(f"  per SIMD with {depth} waves of one generation ({len(spread)} SIMDs; {gens} with a refill left out), "
+              "end by start rank, oldest first, median over SIMDs:")
+        print("    " + "  ".join(f"#{r}={np.median(v):.2f}" for r, v in enumerate(by_rank)))
+        fin = np.array([np.sort([by_rank[r][k] for r in range(depth)]) for k in range(len(spread))])
+        print("    end by finishing order, median over SIMDs: " + "  ".join(f"{np.median(fin[:, r]):.2f}" for r in range(depth)))
+        print(f"    first-to-last end within a SIMD: {pct(np.array(spread), (10, 50, 90, 100))} us")
+    print("  resident waves over time (all, and per SIMD seen):")
+    for t in np.linspace(0.0, span, 17)[1:-1]:
+        r = int(np.count_nonzero((start <= t) & (end > t)))
+        print(f"    t={t:7.2f} us  {r:6d}  {r / len(keys):.2f}")
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 4 * 1024 * 1024
     warm = int(sys.argv[2]) if len(sys.argv) > 2 else 8
@@ -70,6 +131,13 @@ def main():
         blocks = L.eslam_gpu_debug_stamps(which, buf.ctypes.data, 32768)
         assert blocks >= 0
         report(f"{label} at n={n} ({blocks} blocks launched)", buf.copy(), phases, min(blocks, 32768))
+    if hasattr(L, "eslam_gpu_debug_stamps_k1_waves"):
+        L.eslam_gpu_debug_stamps_k1_waves.argtypes = [C.c_void_p, C.c_uint64]
+        L.eslam_gpu_debug_stamps_k1_waves.restype = C.c_int64
+        wbuf = np.zeros((32768 * 4, 4), dtype=np.uint64)
+        blocks = L.eslam_gpu_debug_stamps_k1_waves(wbuf.ctypes.data, 32768 * 4)
+        assert blocks >= 0
+        report_waves(f"K1 waves at n={n}", wbuf, min(blocks, 32768))
     if stats:
         assert L.eslam_gpu_debug_draw_waves(waves, 0) == 0
         print(f"== draw counting of the last step: {waves[0]} waves, {waves[1]} of them evaluated their draws")
