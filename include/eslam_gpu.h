@@ -571,6 +571,10 @@ int eslam_gpu_debug_set_spin_limit(eslam_ctx* ctx, uint32_t polls);
  * the rule by particle count).  The tile totals are exact integers, so the tile size never
  * changes a result; the hook lets small filters run the instantiation of large ones.       */
 int eslam_gpu_debug_set_scan_items(eslam_ctx* ctx, uint32_t items);
+/* eslam_config.min_effective of this context from the next update on (every update reads it): 0
+ * never resamples, a value above the particle count resamples at every update.  The ranks of a
+ * sharded filter set the same value.                                                          */
+int eslam_gpu_set_min_effective(eslam_ctx* ctx, uint64_t min_effective);
 
 /* ---- ParticleFilter<T> API (src/ParticleFilter.hpp:34-173) ------------------------------ */
 int eslam_gpu_get_weights_sum(eslam_ctx* ctx, double* sum);          /* getWeightsSum :34-39     */
@@ -747,6 +751,78 @@ typedef struct eslam_pose_moments {
     int32_t weight_exp, pad;
 } eslam_pose_moments;
 int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gate /* may be NULL */, eslam_pose_moments* out);
+
+/* ---- the trajectory: particle ancestry and poses per step, traced and smoothed on the device ----
+ * The reference keeps its history inside each particle's MLSMap and in the logged
+ * PoseDistribution stream; this build keeps a log on the device.  It is opt-in,
+ * created by eslam_gpu_trajectory_enable (no eslam_config field): a ring of capacity_steps
+ * entries allocated in full at once, each SoA for up to max_particles particles (0: the
+ * context's particle capacity, which then must not be 0): x, y, z, yaw, zsigma as fp64 and
+ * parent as uint32, the slot of the particle's ancestor in the previous held entry.  That is 44
+ * bytes per particle per entry, 185 MB per entry at 4M particles, plus two link arrays of 4 bytes
+ * per particle.  No allocation happens on the step path; an allocation that fails at enable is
+ * ESLAM_ERR_OUT_OF_MEMORY with the context as it was.  When the ring is full the oldest entry is
+ * overwritten.  Enabling an enabled log replaces it (empty); disable frees it; clear empties it and
+ * keeps it enabled.  An entry's step id is the number of records taken since enable before it.
+ *   record   at the end of every eslam_gpu_step (its update gate open or closed: the particles
+ *            moved) and every eslam_gpu_update whose kernels were enqueued (one that then returns
+ *            ESLAM_ERR_ZERO_MEAS_VAR has recorded, without a resample); eslam_gpu_project alone
+ *            records nothing.  Enqueued on the context's stream, no host wait: the pending
+ *            resample gather is materialised (so no later kernel fuses it: the feature's per-step
+ *            cost), then one kernel copies the five columns of the particles as they stand --
+ *            after the resample when one happened -- and writes parent.
+ *   link     link[i] is the slot, in the newest entry, of the ancestor of the current particle i:
+ *            the identity after a record.  parent[i] = link[anc[i]] when the update resampled
+ *            (anc: eslam_gpu_get_ancestors' array; the decision is read on the device), else
+ *            link[i].  A resample outside the step (eslam_gpu_resample, _resample_stratified,
+ *            _resample_multinomial, _resample_kld) composes link'[i] = link[anc[i]] over its
+ *            outputs instead of recording, so entries may hold different particle counts.  One
+ *            that would leave more than max_particles particles is ESLAM_ERR_INVALID_ARG before
+ *            anything changes, and so is an upload, init or load of more.
+ *   cleared  (still enabled) by eslam_gpu_upload_particles, the eslam_gpu_init_* calls and every
+ *            eslam_gpu_load*; snapshots do not carry the log.  eslam_gpu_write_particles and the
+ *            hash respawn keep the slot's lineage: the pose jumps between two entries.  The map
+ *            calls do not touch it.
+ * While the log is enabled the filter keeps ancestors as with ESLAM_FLAG_RECORD_ANCESTORS.  The
+ * filter itself -- particles, weights, RNG, maps -- is bit for bit what it is without the log.
+ * Sharded filters: eslam_gpu_trajectory_enable is ESLAM_ERR_UNSUPPORTED, and so is
+ * eslam_gpu_set_comm* on a context whose log is enabled (a sharded log needs a per-entry exchange).
+ *
+ * eslam_gpu_get_trajectories: for each current particle indices[k] (< the particle count, repeats
+ * allowed) its lineage: from link[index] in the newest entry along parent back through the
+ * newest *steps = min(entries held, capacity) entries, written oldest first at
+ * out[k * capacity .. k * capacity + *steps).  A node is the entry's step id and particle count,
+ * the ancestor's slot in it and its five values as recorded.  An empty log or capacity 0:
+ * ESLAM_OK with *steps = 0.  ESLAM_ERR_INVALID_ARG: a null ctx or steps, null indices or out where
+ * they are needed, an index >= the particle count, the log not enabled.
+ * eslam_gpu_trajectory_smoothed: for each of the newest *entries = min(entries held, capacity)
+ * entries k, oldest first, the fixed-lag smoothed estimate: the pose moments of the ancestors at
+ * entry k of the current particles under the current weights.  With a_newest = link and
+ * a_{k-1}[i] = parent_k[a_k[i]], out[k].moments is bit for bit what eslam_gpu_pose_moments
+ * without a gate gives on n particles whose (x, y, zpos, orientation, zsigma) are those of slot
+ * a_k[i] of entry k and whose weight is the current w[i], in the order of i; distinct_ancestors is
+ * the number of distinct values of a_k (where it reaches 1 every older entry holds one common
+ * ancestor).  Needs particles (ESLAM_ERR_NOT_INITIALISED); an empty log: ESLAM_OK, *entries = 0.
+ * Both queries are synchronous, settle and materialise first like eslam_gpu_pose_moments, and
+ * change nothing in the filter or the log.                                                    */
+typedef struct eslam_trajectory_info {
+    uint32_t enabled, capacity_steps;
+    uint64_t max_particles;
+    uint64_t entries;                 /* entries held                                          */
+    uint64_t first_step, last_step;   /* step ids of the oldest and newest held entry (0: none) */
+    uint64_t particles;               /* of the newest held entry                              */
+    uint64_t bytes;                   /* device memory of the ring and the link arrays         */
+} eslam_trajectory_info;
+typedef struct eslam_trajectory_pose { uint64_t step; uint32_t slot, particles; double x, y, z, yaw, zsigma; } eslam_trajectory_pose;
+typedef struct eslam_trajectory_estimate { uint64_t step; uint64_t distinct_ancestors; eslam_pose_moments moments; } eslam_trajectory_estimate;
+int eslam_gpu_trajectory_enable(eslam_ctx* ctx, uint32_t capacity_steps, uint64_t max_particles /* 0: the context's capacity */);
+int eslam_gpu_trajectory_disable(eslam_ctx* ctx);
+int eslam_gpu_trajectory_clear(eslam_ctx* ctx);
+int eslam_gpu_trajectory_info(eslam_ctx* ctx, eslam_trajectory_info* info);
+int eslam_gpu_get_trajectories(eslam_ctx* ctx, const uint64_t* indices, uint64_t count,
+                               eslam_trajectory_pose* out /* count x capacity */, uint64_t capacity,
+                               uint64_t* steps /* nodes written per index */);
+int eslam_gpu_trajectory_smoothed(eslam_ctx* ctx, eslam_trajectory_estimate* out, uint64_t capacity, uint64_t* entries);
 
 /* ---- KLD-sampling (Fox 2003): the particle count the posterior needs --------------------------
  * The reference takes `samples` from its caller (src/ParticleFilter.hpp); the rule is this

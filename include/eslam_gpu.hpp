@@ -1157,6 +1157,47 @@ public:
         return r;
     }
 
+    // The trajectory log (eslam_gpu_trajectory_*): what the reference keeps inside
+    // each particle's map and in the logged PoseDistribution stream.  Once enabled, every update()
+    // and every step of EmbodiedSlamFilter::update ends with a record on the device of the
+    // particles' poses and ancestry, in a ring of `steps` entries of up to maxParticles particles
+    // (0: the filter's capacity), 44 bytes per particle and entry.
+    void enableTrajectory(uint32_t steps, uint64_t maxParticles = 0)
+    {
+        flush();
+        check(ctx_, eslam_gpu_trajectory_enable(ctx_, steps, maxParticles));
+    }
+    void disableTrajectory() { check(ctx_, eslam_gpu_trajectory_disable(ctx_)); }
+    void clearTrajectory() { check(ctx_, eslam_gpu_trajectory_clear(ctx_)); }
+    eslam_trajectory_info trajectoryInfo() const
+    {
+        eslam_trajectory_info info;
+        check(ctx_, eslam_gpu_trajectory_info(ctx_, &info));
+        return info;
+    }
+    // the lineage of the current particle i through the held entries, oldest first
+    std::vector<eslam_trajectory_pose> trajectory(size_t i) const
+    {
+        flush();
+        std::vector<eslam_trajectory_pose> path(trajectoryInfo().entries);
+        const uint64_t index = i;
+        uint64_t steps = 0;
+        check(ctx_, eslam_gpu_get_trajectories(ctx_, &index, 1, path.data(), path.size(), &steps));
+        path.resize(steps);
+        return path;
+    }
+    // per held entry, oldest first: the pose moments of the current particles' ancestors in it
+    // under the current weights (the fixed-lag smoothed estimate) and their distinct count
+    std::vector<eslam_trajectory_estimate> smoothedTrajectory() const
+    {
+        flush();
+        std::vector<eslam_trajectory_estimate> est(trajectoryInfo().entries);
+        uint64_t entries = 0;
+        check(ctx_, eslam_gpu_trajectory_smoothed(ctx_, est.data(), est.size(), &entries));
+        est.resize(entries);
+        return est;
+    }
+
     // getParticles(): the particles as a vector the caller may edit, like the reference's
     // std::vector<Particle>& (src/ParticleFilter.hpp:150-153; processMap edits weights through
     // it, src/EmbodiedSlamFilter.cpp:183-220).  The particles live in HBM: the vector is
@@ -1691,6 +1732,15 @@ public:
     // KLD-sampling: the particle count the posterior asks for, and the resample to it
     eslam_kld_info kldCount(const KldParams& kp = KldParams()) { return estimator().kldCount(kp); }
     void resampleKld(const KldParams& kp = KldParams()) { estimator().resampleKld(kp); }
+    // the trajectory log (PoseEstimator::enableTrajectory); bestTrajectory(): the path the best
+    // particle's map was built along
+    void enableTrajectory(uint32_t steps, uint64_t maxParticles = 0) { estimator().enableTrajectory(steps, maxParticles); }
+    void disableTrajectory() { estimator().disableTrajectory(); }
+    void clearTrajectory() { estimator().clearTrajectory(); }
+    eslam_trajectory_info trajectoryInfo() { return estimator().trajectoryInfo(); }
+    std::vector<eslam_trajectory_pose> trajectory(size_t i) { return estimator().trajectory(i); }
+    std::vector<eslam_trajectory_pose> bestTrajectory() { return trajectory(getBestParticleIndex()); }
+    std::vector<eslam_trajectory_estimate> smoothedTrajectory() { return estimator().smoothedTrajectory(); }
 
     PoseEstimator& estimator()
     {

@@ -31,8 +31,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ESLAM_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["eslam_kernels.hip", "eslam_resample.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_snapshot.hip",
-           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_gmm.hip", "eslam_moments.hip", "eslam_kld.hip", "eslam_ctx.hip", "eslam_host_comm.hip",
-           "eslam_host_map.hip", "eslam_host_stats.hip", "eslam_host_snapshot.hip"]
+           "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_gmm.hip", "eslam_moments.hip", "eslam_kld.hip", "eslam_trajectory.hip", "eslam_ctx.hip", "eslam_host_comm.hip",
+           "eslam_host_map.hip", "eslam_host_stats.hip", "eslam_host_trajectory.hip", "eslam_host_snapshot.hip"]
 HEADERS = [os.path.join(CSRC, "eslam_internal.h"), os.path.join(CSRC, "eslam_launch.h"), os.path.join(CSRC, "eslam_buf.h"),
            os.path.join(CSRC, "eslam_scratch.h"), os.path.join(CSRC, "eslam_ctx.h"),
            os.path.join(ROOT, "include", "eslam_gpu.h"), os.path.join(ROOT, "include", "eslam_detmath.h")]
@@ -107,7 +107,7 @@ def build_facade_test(verbose=True, name="test_facade"):
     """g++ a C++ façade test (include/eslam_gpu.hpp over the C ABI) against the library:
     tests/cpp/<name>.cpp -> tests/cpp/_build/<name> (test_facade, test_facade_shared_map,
     test_snapshot_facade, test_snapshot_facade_file, test_facade_scan, test_facade_resample,
-    test_facade_resample_sharded, test_facade_particle_grid, test_facade_gmm, test_facade_kld, test_facade_moments)."""
+    test_facade_resample_sharded, test_facade_particle_grid, test_facade_gmm, test_facade_kld, test_facade_moments, test_facade_trajectory)."""
     src = os.path.join(os.path.dirname(FACADE_SRC), name + ".cpp")
     exe = os.path.join(os.path.dirname(FACADE_BIN), name)
     deps = [src, LIB, os.path.join(ROOT, "include", "eslam_gpu.hpp"), os.path.join(ROOT, "include", "eslam_gpu.h")]

@@ -1,8 +1,9 @@
 // eslam_ctx.h -- host-only: the context behind the C ABI of include/eslam_gpu.h, and the helpers
 // that more than one host file uses (namespace eslam_host).  Included by the host files:
 // eslam_ctx.hip (lifecycle, particles, the step, the resamplers), eslam_host_map.hip (the maps and
-// the scan build), eslam_host_stats.hip (centroid, mixture, moments, KLD), eslam_host_snapshot.hip
-// (save and load) and eslam_host_comm.hip (the multi-GPU plumbing).
+// the scan build), eslam_host_stats.hip (centroid, mixture, moments, KLD), eslam_host_trajectory.hip
+// (the trajectory log and its queries), eslam_host_snapshot.hip (save and load) and
+// eslam_host_comm.hip (the multi-GPU plumbing).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -72,6 +73,29 @@ struct GridBufs {                            // the shared grid's arrays (MapVie
     Dev<float> height;                       // empty: all horizontal
     Dev<uint4> cell_tab;
     SmGrid view() const { return SmGrid{cells, patch, height, occ, cell_tab}; }
+};
+
+// The trajectory log (eslam_gpu_trajectory_enable): a ring of `capacity` entries of
+// max_particles particles each, 44 bytes per particle (x, y, z, yaw, zsigma as fp64 and the uint32
+// parent: 185 MB per entry at 4M particles), and the two link buffers, all one block allocated at
+// enable.  What the host keeps per entry is its particle count and its step id.
+struct TrajectoryLog {
+    bool on = false;
+    uint32_t capacity = 0;
+    uint64_t max_particles = 0;
+    Dev<void> mem;
+    uint64_t bytes = 0;
+    std::vector<TrajEntry> entry;            // the ring entries' arrays within mem
+    std::vector<uint32_t> count;             // per ring entry: the particles it holds
+    std::vector<uint64_t> step;              // ... and its step id
+    uint32_t* link[2] = {};                  // link[cur][i]: current particle i's ancestor's slot in the newest entry
+    uint32_t cur = 0;
+    uint64_t link_n = 0;                     // entries of link[cur]: the filter's count at the last record or composition
+    uint32_t head = 0, held = 0;             // the ring entry the next record writes, the entries held
+    uint64_t next_step = 0;                  // records since enable: the next entry's step id
+    Dev<char> scratch;                       // the queries' scratch, kept between calls
+    // the ring index of the j-th newest held entry (j < held)
+    uint32_t at(uint32_t j) const { return (head + capacity - 1u - j) % capacity; }
 };
 
 struct eslam_ctx {
@@ -209,6 +233,7 @@ struct eslam_ctx {
     // eslam_gpu_resample_stratified / _multinomial to another count: the cumulative sum, its
     // coarse level, the draws' ancestors and the compaction's counts (resample_to), kept between calls
     Dev<char> rs_mem;
+    TrajectoryLog traj;
     // diagnostics
     std::string err;
     bool timing = false;
@@ -289,6 +314,20 @@ GatherView gather_view(eslam_ctx* ctx);
 int materialize(eslam_ctx* ctx);
 int resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info);
 int resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_resample_info* info);
+
+// ---- eslam_host_stats.hip
+// the ungated or gated pose moments (eslam_gpu_pose_moments' passes) of the context's n particles
+// read from the state pair s0 / s1; rc: what preparing them returned (a sharded filter agrees on it)
+int pose_moments_of(eslam_ctx* ctx, DevState s0, DevState s1, MomPass& P, int rc, eslam_pose_moments* out);
+
+// ---- eslam_host_trajectory.hip (the callers test ctx->traj.on first)
+// the end of a step or an update: materialises a pending gather, then records the particles as
+// they stand; `updated`: an update ran, whose resample decision the device reads
+int trajectory_record(eslam_ctx* ctx, bool updated);
+// after a resample outside the step has written pt.anc for the filter's n outputs: link' = link o anc
+int trajectory_compose(eslam_ctx* ctx);
+// a new particle set: the log is emptied, the link the identity over the filter's n
+int trajectory_reset(eslam_ctx* ctx);
 
 // ---- eslam_host_comm.hip
 int comm_allgather(eslam_ctx* ctx, const void* dsend, void* drecv, uint64_t bytes);

@@ -346,15 +346,16 @@ extern "C" int eslam_gpu_create(const eslam_config* cfg, int device, eslam_ctx**
     return ESLAM_OK;
 }
 
-// ancestors are kept when asked for, and always while contact records are (the records of
-// output i are those of its ancestor)
+// ancestors are kept when asked for, while the trajectory log is enabled (its parents are composed
+// from them), and always while contact records are (the records of output i are those of its
+// ancestor)
 static bool record_contacts(const eslam_ctx* ctx)
 {
     return (ctx->cfg.flags & ESLAM_FLAG_RECORD_CONTACTS) || ctx->cfg.log_debug;
 }
 static bool keep_ancestors(const eslam_ctx* ctx)
 {
-    return (ctx->cfg.flags & ESLAM_FLAG_RECORD_ANCESTORS) || record_contacts(ctx);
+    return (ctx->cfg.flags & ESLAM_FLAG_RECORD_ANCESTORS) || ctx->traj.on || record_contacts(ctx);
 }
 
 static void free_debug(eslam_ctx* ctx)
@@ -505,6 +506,8 @@ int eslam_host::alloc_particles(eslam_ctx* ctx, uint64_t n)
     if (n >= (1ull << 32) - 1) return fail(ctx, ESLAM_ERR_INVALID_ARG, "particle count must be < 2^32 - 1");
     if (ctx->sharded && n != ctx->gall[ctx->comm.rank + 1] - ctx->gall[ctx->comm.rank])
         return fail(ctx, ESLAM_ERR_INVALID_ARG, "sharded context: particle count must equal this rank's shard size");
+    if (ctx->traj.on && n > ctx->traj.max_particles)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "trajectory log: particle count must not exceed its max_particles");
     free_particles(ctx);
     const uint64_t cap = n ? n : 1;
     ParticleSet ps;
@@ -514,6 +517,11 @@ int eslam_host::alloc_particles(eslam_ctx* ctx, uint64_t n)
     if (!ctx->sharded) {
         ctx->n_global = n;
         ctx->gbase = 0;
+    }
+    // a new particle set starts the trajectory log over: no lineage leads into it
+    if (ctx->traj.on) {
+        const int rc = trajectory_reset(ctx);
+        if (rc) return rc;
     }
     return local_maps_reset(ctx);
 }
@@ -1749,8 +1757,11 @@ static bool step_input_ok(const eslam_step_input* in)
     return !(in->sample_cov[0] < 0.0 || in->sample_cov[4] < 0.0 || in->sample_cov[8] < 0.0);
 }
 
-static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project, bool weight)
+// `track`: the call ends a step (eslam_gpu_step, eslam_gpu_update), so an enabled trajectory log
+// takes its record once the step's kernels are enqueued
+static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project, bool weight, bool track)
 {
+    track = track && ctx->traj.on;
     if (!step_input_ok(in))
         return fail(ctx, ESLAM_ERR_INVALID_ARG, "step input: sample_mean and sample_cov must be finite, the variances not negative");
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
@@ -1795,7 +1806,7 @@ static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project,
             if (rc) return rc;
         }
         project = false;                      // done; the update below is weight-only
-        if (!weight) return ESLAM_OK;
+        if (!weight) return track ? trajectory_record(ctx, false) : ESLAM_OK;
     }
     if (records) {
         const uint32_t maxc = p.m ? p.m : 1u;
@@ -1870,6 +1881,12 @@ static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project,
             HIPCHK(ctx, hipMemcpyAsync(ctx->dbg.resampled, &ctx->ctl->resample, 4, hipMemcpyDeviceToDevice, ctx->stream));
             ctx->dbg_valid = true;
         }
+        // the trajectory log: the gather is materialised now (no later kernel fuses it) and the
+        // record reads this update's resample decision on the device, all behind K3 on the stream
+        if (track) {
+            const int rc2 = trajectory_record(ctx, true);
+            if (rc2) return rc2;
+        }
         // measVar = zSigma^2 + measurementError^2 is zero only when measurementError^2 is: in
         // that configuration the update is checked at once, so the error surfaces from this
         // call like the reference's throw (src/ContactModel.cpp:122-123) and the caller's
@@ -1879,19 +1896,19 @@ static int launch_step(eslam_ctx* ctx, const eslam_step_input* in, bool project,
     }
     HIPCHK(ctx, eslam_launch_commit(ctx->ctl, ctx->stream));
     rec(ctx, 2); rec(ctx, 3); rec(ctx, 4);
-    return ESLAM_OK;
+    return track ? trajectory_record(ctx, false) : ESLAM_OK;
 }
 
 extern "C" int eslam_gpu_project(eslam_ctx* ctx, const eslam_step_input* in)
 {
     if (!ctx || !in) return ESLAM_ERR_INVALID_ARG;
-    return launch_step(ctx, in, true, false);
+    return launch_step(ctx, in, true, false, false);
 }
 
 extern "C" int eslam_gpu_update(eslam_ctx* ctx, const eslam_step_input* in)
 {
     if (!ctx || !in) return ESLAM_ERR_INVALID_ARG;
-    return launch_step(ctx, in, false, true);
+    return launch_step(ctx, in, false, true, true);
 }
 
 extern "C" int eslam_gpu_step(eslam_ctx* ctx, const eslam_step_input* in, int* updated)
@@ -1900,7 +1917,7 @@ extern "C" int eslam_gpu_step(eslam_ctx* ctx, const eslam_step_input* in, int* u
     const bool gate = update_gate(ctx->cfg.measurement_threshold_distance, ctx->cfg.measurement_threshold_angle, ctx->ud_pose,
                                   in->body2odometry_rot, in->body2odometry_trans) ||
                       in->ltc_count > 0;
-    const int rc = launch_step(ctx, in, true, gate);
+    const int rc = launch_step(ctx, in, true, gate, true);
     if (rc) return rc;
     if (gate) {
         double R[9];
@@ -1926,6 +1943,13 @@ extern "C" int eslam_gpu_debug_set_scan_items(eslam_ctx* ctx, uint32_t items)
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
     if (items != 0 && items != 1 && items != 2 && items != 4 && items != (uint32_t)kScanItems) return ESLAM_ERR_INVALID_ARG;
     ctx->debug_scan_items = items;
+    return ESLAM_OK;
+}
+
+extern "C" int eslam_gpu_set_min_effective(eslam_ctx* ctx, uint64_t min_effective)
+{
+    if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    ctx->cfg.min_effective = min_effective;  // fin_params reads it at every update
     return ESLAM_OK;
 }
 
@@ -2021,12 +2045,22 @@ extern "C" int eslam_gpu_normalize_weights(eslam_ctx* ctx, double* effective)
     return ESLAM_OK;
 }
 
+// the stand-alone resample at the current count, which always resamples.  With the trajectory log
+// enabled its gather runs at once (it writes pt.anc) and the link is composed with the ancestors
+static int resample_in_place(eslam_ctx* ctx)
+{
+    ctx->dbg_valid = false;                  // the records no longer follow the particles
+    int rc = standalone(ctx, FIN_RESAMPLE);
+    if (rc || !ctx->traj.on) return rc;
+    rc = materialize(ctx);
+    return rc ? rc : trajectory_compose(ctx);
+}
+
 extern "C" int eslam_gpu_resample(eslam_ctx* ctx)
 {
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
     if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
-    ctx->dbg_valid = false;                  // the records no longer follow the particles
-    return standalone(ctx, FIN_RESAMPLE);
+    return resample_in_place(ctx);
 }
 
 // ParticleFilter<T>::resample_stratified(samples) / resample_multinomial(samples)
@@ -2045,6 +2079,8 @@ int eslam_host::resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_
     // the shard boundaries are fixed by set_comm; refused before any collective (settle is one)
     if (ctx->sharded && (multi || samples != ctx->n_global))
         return fail(ctx, ESLAM_ERR_UNSUPPORTED, "resample: a sharded filter resamples to its own count only (stratified)");
+    if (ctx->traj.on && samples > ctx->traj.max_particles)
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample: samples may not exceed the trajectory log's max_particles");
     if (const int rc_ = settle(ctx)) return rc_;
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
     if (check_poisoned(ctx)) return ESLAM_ERR_HIP;
@@ -2052,8 +2088,7 @@ int eslam_host::resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_
     int rc;
     // the current count (a sharded filter's global one: its capacity is the shard's): the resample itself
     if (!multi && samples == ctx->n_global) {
-        ctx->dbg_valid = false;                  // the records no longer follow the particles
-        rc = standalone(ctx, FIN_RESAMPLE);
+        rc = resample_in_place(ctx);
         if (rc || !info) return rc;
         rc = read_ctl(ctx);
         if (rc) return rc;
@@ -2131,7 +2166,8 @@ int eslam_host::resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_
         if (multi) info->dropped = beyond;
         else info->overruns = beyond;
     }
-    return ESLAM_OK;
+    // the trajectory log: the gather above wrote the outputs' ancestors; the link follows them
+    return ctx->traj.on ? trajectory_compose(ctx) : ESLAM_OK;
 }
 
 extern "C" int eslam_gpu_resample_stratified(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)

@@ -172,6 +172,8 @@ int eslam_host::apply_shard_table(eslam_ctx* ctx, int nranks, int rank, uint64_t
 extern "C" int eslam_gpu_set_comm(eslam_ctx* ctx, const eslam_comm* comm, uint64_t n_global, const uint64_t* shard_gbase)
 {
     if (!ctx) return ESLAM_ERR_INVALID_ARG;
+    if (comm && ctx->traj.on)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "eslam_gpu_set_comm: a filter with a trajectory log cannot be sharded (disable the log first)");
     if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     free_particles(ctx);
@@ -343,6 +345,8 @@ extern "C" int eslam_gpu_set_comm_rccl(eslam_ctx* ctx, int32_t nranks, int32_t r
                                        uint64_t n_global, const uint64_t* shard_gbase)
 {
     if (!ctx || !id) return ESLAM_ERR_INVALID_ARG;
+    if (ctx->traj.on)
+        return fail(ctx, ESLAM_ERR_UNSUPPORTED, "eslam_gpu_set_comm_rccl: a filter with a trajectory log cannot be sharded (disable the log first)");
     if (const int rc_ = settle(ctx)) return rc_;    // a deferred sharded exchange first
     const RcclApi& a = rccl_api();
     if (!a.ok) return fail(ctx, ESLAM_ERR_UNSUPPORTED, "eslam_gpu_set_comm_rccl: librccl.so.1 not found");

@@ -320,7 +320,12 @@ extern "C" int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gat
         const int rc = same_on_every_rank(ctx, mine, 6, "pose_moments: the ranks' gates differ");
         if (rc) return rc;
     }
-    int rc = materialize(ctx);                       // the particles as they stand
+    const int rc = materialize(ctx);                 // the particles as they stand
+    return pose_moments_of(ctx, ctx->st[0], ctx->st[1], P, rc, out);
+}
+
+int eslam_host::pose_moments_of(eslam_ctx* ctx, DevState s0, DevState s1, MomPass& P, int rc, eslam_pose_moments* out)
+{
     const uint32_t J = dm_chunk_rows_cfg(ctx->n_global, ctx->cfg.sum_chunk_rows);
     GmmBufs g;                                       // the fit's layout at the wider record
     if (!rc) rc = grow(ctx, ctx->moments, gmm_carve(ctx, DM_MOM_REC2, J, nullptr, &g));
@@ -330,7 +335,7 @@ extern "C" int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gat
 
     // pass B: order-free words, reduced over the ranks identically everywhere
     const int G = ctx->sharded ? ctx->comm.nranks : 1;
-    HIPCHK(ctx, eslam_launch_moments_bounds(ctx->st[0], ctx->st[1], ctx->n, ctx->ctl, &P, g.part, g.words, ctx->stream));
+    HIPCHK(ctx, eslam_launch_moments_bounds(s0, s1, ctx->n, ctx->ctl, &P, g.part, g.words, ctx->stream));
     if (ctx->sharded) {
         rc = comm_allgather(ctx, g.words, g.words_all, kMomWords * sizeof(uint64_t));
         if (rc) return rc;
@@ -356,7 +361,7 @@ extern "C" int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gat
     }
     auto pass = [&](int which, uint32_t R, double* rec) {
         return chunk_pass(ctx, R, g, rec, [&](double* dst) {
-            return eslam_launch_moments_pass(which, ctx->st[0], ctx->st[1], ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
+            return eslam_launch_moments_pass(which, s0, s1, ctx->n, J, ctx->ctl, &P, dst, ctx->stream);
         });
     };
     double rec[DM_MOM_REC2], q[4];

@@ -690,4 +690,51 @@ struct KldScratch {
     uint64_t* all;                       // sharded: every rank's bitmap
 };
 
+#if defined(__HIPCC__)
+// Rounds in which one lane ORs, for every lane of the wave that still has a bit to set in the
+// same word, the combined mask; a lane left after them sets its own bit.
+constexpr int kMarkPeel = 4;
+// Sets bit `m` of bits[wi] for every lane with `need` (k_kld_mark, k_traj_level).  Called by whole
+// waves.  The word is read first: the bitmap only ever gains bits, so a set bit read here is set
+// for good and needs no atomic, and a stale clear one only costs the atomic.  A plain load: through
+// the CU's L1 it was as fast as a device-scope load on a converged cloud and faster on a spread
+// one.  One atomic per lane without the read took 43 ms on a converged cloud of 4M particles.
+__device__ __forceinline__ void mark_bits_wave(uint64_t* bits, bool need, uint64_t wi, uint64_t m)
+{
+    if (need && (bits[wi] & m)) need = false;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (int round = 0; round < kMarkPeel; ++round) {
+        const unsigned long long act = __ballot(need);
+        if (!act) return;
+        const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
+        const uint64_t lw = __shfl(wi, (int)leader, 64);
+        const bool mine = need && wi == lw;
+        uint64_t c = mine ? m : 0;
+        for (int o = 32; o >= 1; o >>= 1) c |= __shfl_xor(c, o, 64);
+        if (lane == leader) atomicOr((unsigned long long*)&bits[lw], (unsigned long long)c);
+        if (mine) need = false;
+    }
+    if (need) atomicOr((unsigned long long*)&bits[wi], (unsigned long long)m);
+}
+#endif
+
+// The trajectory log (eslam_trajectory.hip).  One ring entry's arrays, each with
+// room for the log's max_particles: 44 bytes per particle
+struct TrajEntry {
+    double *x, *y, *z, *yaw, *zs;
+    uint32_t* parent;                    // the slot of the particle's ancestor in the previous held entry
+};
+// a held entry as a query walks it (newest first) with the particles it holds
+struct TrajLevel {
+    TrajEntry e;
+    uint32_t count, pad;
+};
+// k_traj_trace's output: a lineage's node in one entry
+struct TrajNode {
+    uint32_t slot, pad;
+    double x, y, z, yaw, zs;
+};
+// a slot outside its entry: a walk that meets one ends there (a sound log holds none)
+constexpr uint32_t kTrajNone = 0xffffffffu;
+
 }  // namespace eslam_dev

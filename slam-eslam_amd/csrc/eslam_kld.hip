@@ -106,43 +106,17 @@ __global__ void __launch_bounds__(kBlock) k_kld_fold(const int64_t* __restrict__
     }
 }
 
-// Rounds in which one lane ORs, for every lane of the wave that still has a bit to set in the
-// same word, the combined mask; a lane left after them sets its own bit.
-constexpr int kKldPeel = 4;
 // The particles a first small launch marks before the launch over the rest.  On a converged
 // cloud every wave of one launch starts on clear words and sends its atomics to the same few of
 // them; after this head the rest finds its bits set (4M particles: 0.24 ms a call without it,
 // 0.11 ms with it)
 constexpr uint64_t kKldHead = 16384;
 
-// Sets bit `m` of bits[wi] for every lane with `need`.  Called by whole waves.  The word is read
-// first: the bitmap only ever gains bits, so a set bit read here is set for good and needs no
-// atomic, and a stale clear one only costs the atomic.  A plain load: through the CU's L1 it was
-// as fast as a device-scope load on a converged cloud and faster on a spread one.  One atomic
-// per lane without the read took 43 ms on a converged cloud of 4M particles.
-__device__ __forceinline__ void kld_mark_wave(uint64_t* bits, bool need, uint64_t wi, uint64_t m)
-{
-    if (need && (bits[wi] & m)) need = false;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (int round = 0; round < kKldPeel; ++round) {
-        const unsigned long long act = __ballot(need);
-        if (!act) return;
-        const uint32_t leader = (uint32_t)__ffsll((long long)act) - 1u;
-        const uint64_t lw = __shfl(wi, (int)leader, 64);
-        const bool mine = need && wi == lw;
-        uint64_t c = mine ? m : 0;
-        for (int o = 32; o >= 1; o >>= 1) c |= __shfl_xor(c, o, 64);
-        if (lane == leader) atomicOr((unsigned long long*)&bits[lw], (unsigned long long)c);
-        if (mine) need = false;
-    }
-    if (need) atomicOr((unsigned long long*)&bits[wi], (unsigned long long)m);
-}
-
 __global__ void __launch_bounds__(kBlock) k_kld_mark(DevState s0, DevState s1, uint64_t first, uint64_t n, const Ctl* __restrict__ ctl,
                                                      const KldGrid g, uint64_t* __restrict__ bits, uint64_t words)
 {
     const DevState st = (ctl->base ^ ctl->flip) ? s1 : s0;
-    // whole waves take every trip: the shuffles of kld_mark_wave need all 64 lanes
+    // whole waves take every trip: the shuffles of mark_bits_wave (eslam_internal.h) need all 64 lanes
     for (uint64_t b = first + (uint64_t)blockIdx.x * kBlock; b < n; b += (uint64_t)gridDim.x * kBlock) {
         const uint64_t i = b + threadIdx.x;
         bool need = false;
@@ -158,7 +132,7 @@ __global__ void __launch_bounds__(kBlock) k_kld_mark(DevState s0, DevState s1, u
                 need = wi < words;
             }
         }
-        kld_mark_wave(bits, need, wi, m);
+        mark_bits_wave(bits, need, wi, m);
     }
 }
 

@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip and the eslam_host_*.hip files), declared once.  All fifteen .hip files include it, the defining one too: the
+// (eslam_ctx.hip and the eslam_host_*.hip files), declared once.  All seventeen .hip files include it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -92,6 +92,17 @@ hipError_t eslam_launch_kld_mark(DevState s0, DevState s1, uint64_t n, const Ctl
                                  uint64_t words, hipStream_t stream);
 hipError_t eslam_launch_kld_or(const uint64_t* all, uint32_t G, uint64_t words, uint64_t* bits, hipStream_t stream);
 hipError_t eslam_launch_kld_popcount(const uint64_t* bits, uint64_t words, int64_t* part, int64_t* out, hipStream_t stream);
+
+// ---- eslam_trajectory.hip (the trajectory log: the record, the link's composition, the two queries)
+hipError_t eslam_launch_traj_iota(uint32_t* link, uint64_t n, hipStream_t stream);
+hipError_t eslam_launch_traj_record(DevState s0, DevState s1, const Ctl* ctl, uint64_t n, int updated, const uint32_t* anc,
+                                    const uint32_t* link, uint64_t nlink, uint32_t* link_next, const TrajEntry* e,
+                                    hipStream_t stream);
+hipError_t eslam_launch_traj_compose(const uint32_t* anc, const uint32_t* link, uint64_t nlink, uint32_t* link_next, uint64_t n,
+                                     hipStream_t stream);
+hipError_t eslam_launch_traj_trace(const uint32_t* leaf, uint64_t count, const uint32_t* link, uint64_t nlink, const TrajLevel* lv,
+                                   uint32_t steps, TrajNode* out, hipStream_t stream);
+hipError_t eslam_launch_traj_level(uint64_t n, const TrajLevel* L, uint32_t* a, DevState out, uint64_t* bits, hipStream_t stream);
 
 // ---- eslam_resample.hip (resample to a count: the cumulative sum, the draws' searches, the gather)
 uint64_t eslam_resample_tiles(uint64_t items);

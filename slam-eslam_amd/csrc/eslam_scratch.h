@@ -103,6 +103,51 @@ inline void carve_kld(Carver& c, uint64_t words, uint64_t gather, eslam_dev::Kld
     s->all = c.take<uint64_t>(gather * words);
 }
 
+// the trajectory log's block (eslam_gpu_trajectory_enable): `steps` ring entries of `slots`
+// particles each, then the two link buffers
+inline void carve_traj_log(Carver& c, uint64_t steps, uint64_t slots, eslam_dev::TrajEntry* entry, uint32_t* link[2])
+{
+    for (uint64_t k = 0; k < steps; ++k) {
+        eslam_dev::TrajEntry e;
+        e.x = c.take<double>(slots);
+        e.y = c.take<double>(slots);
+        e.z = c.take<double>(slots);
+        e.yaw = c.take<double>(slots);
+        e.zs = c.take<double>(slots);
+        e.parent = c.take<uint32_t>(slots);
+        if (entry) entry[k] = e;
+    }
+    for (int b = 0; b < 2; ++b) link[b] = c.take<uint32_t>(slots);
+}
+
+// a trace of `count` lineages through `steps` entries: the entries, the leaves, the nodes
+struct TrajTraceScratch {
+    eslam_dev::TrajLevel* lv;
+    uint32_t* leaf;
+    eslam_dev::TrajNode* nodes;
+};
+inline void carve_traj_trace(Carver& c, uint64_t count, uint64_t steps, TrajTraceScratch* s)
+{
+    s->lv = c.take<eslam_dev::TrajLevel>(steps);
+    s->leaf = c.take<uint32_t>(count);
+    s->nodes = c.take<eslam_dev::TrajNode>(count * steps);
+}
+
+// the smoothed sweep over n leaves through entries of at most `slots` particles: the scratch
+// state's six columns, the leaves' ancestors, and a KLD count's record, block records and bitmap
+struct TrajSmoothScratch {
+    double *x, *y, *th, *z, *zs, *w;
+    uint32_t* a;
+    eslam_dev::KldScratch k;
+};
+inline void carve_traj_smooth(Carver& c, uint64_t n, uint64_t slots, TrajSmoothScratch* s)
+{
+    double** f[6] = {&s->x, &s->y, &s->th, &s->z, &s->zs, &s->w};
+    for (int j = 0; j < 6; ++j) *f[j] = c.take<double>(n);
+    s->a = c.take<uint32_t>(n);
+    carve_kld(c, (slots + 63) / 64, 0, &s->k);
+}
+
 // a particle-grid composition on tx x ty tiles with `blocks` blocks of cells
 inline void carve_pgrid(Carver& c, uint64_t tx, uint64_t ty, uint64_t blocks, eslam_dev::PgScratch* s)
 {

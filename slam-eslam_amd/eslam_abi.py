@@ -413,6 +413,46 @@ class KldInfo(C.Structure):
                 struct.unpack("<Q", struct.pack("<d", self.bound))[0], self.samples, self.clamped, self.pad)
 
 
+class TrajectoryInfo(C.Structure):
+    """eslam_trajectory_info (include/eslam_gpu.h)."""
+    _fields_ = [
+        ("enabled", C.c_uint32),
+        ("capacity_steps", C.c_uint32),
+        ("max_particles", C.c_uint64),
+        ("entries", C.c_uint64),
+        ("first_step", C.c_uint64),
+        ("last_step", C.c_uint64),
+        ("particles", C.c_uint64),
+        ("bytes", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class TrajectoryPose(C.Structure):
+    """eslam_trajectory_pose: a lineage's node in one entry of the log."""
+    _fields_ = [
+        ("step", C.c_uint64),
+        ("slot", C.c_uint32),
+        ("particles", C.c_uint32),
+        ("x", C.c_double),
+        ("y", C.c_double),
+        ("z", C.c_double),
+        ("yaw", C.c_double),
+        ("zsigma", C.c_double),
+    ]
+
+
+class TrajectoryEstimate(C.Structure):
+    """eslam_trajectory_estimate: an entry's smoothed estimate."""
+    _fields_ = [
+        ("step", C.c_uint64),
+        ("distinct_ancestors", C.c_uint64),
+        ("moments", PoseMoments),
+    ]
+
+
 class RngState(C.Structure):
     _fields_ = [
         ("minstd_x", C.c_uint32),

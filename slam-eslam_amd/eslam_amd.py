@@ -97,6 +97,8 @@ def load_library(path=LIB_PATH):
     L.eslam_gpu_project.argtypes = [vp, C.POINTER(A.StepInput)]
     L.eslam_gpu_update.argtypes = [vp, C.POINTER(A.StepInput)]
     L.eslam_gpu_sync.argtypes = [vp, C.POINTER(A.UpdateInfo)]
+    if hasattr(L, "eslam_gpu_set_min_effective"):        # absent from older builds (A/B runs)
+        L.eslam_gpu_set_min_effective.argtypes = [vp, C.c_uint64]
     if hasattr(L, "eslam_gpu_debug_set_spin_limit"):     # absent from older builds (A/B runs)
         L.eslam_gpu_debug_set_spin_limit.argtypes = [vp, C.c_uint32]
     if hasattr(L, "eslam_gpu_debug_set_scan_items"):     # absent from older builds (A/B runs)
@@ -127,6 +129,15 @@ def load_library(path=LIB_PATH):
         L.eslam_kld_params_default.restype = None
         L.eslam_gpu_kld_count.argtypes = [vp, C.POINTER(A.KldParams), C.POINTER(A.KldInfo)]
         L.eslam_gpu_resample_kld.argtypes = [vp, C.POINTER(A.KldParams), C.POINTER(A.KldInfo), C.POINTER(A.ResampleInfo)]
+    # a library without them is an error at the call
+    if hasattr(L, "eslam_gpu_trajectory_enable"):
+        L.eslam_gpu_trajectory_enable.argtypes = [vp, C.c_uint32, C.c_uint64]
+        L.eslam_gpu_trajectory_disable.argtypes = [vp]
+        L.eslam_gpu_trajectory_clear.argtypes = [vp]
+        L.eslam_gpu_trajectory_info.argtypes = [vp, C.POINTER(A.TrajectoryInfo)]
+        L.eslam_gpu_get_trajectories.argtypes = [vp, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(A.TrajectoryPose), C.c_uint64,
+                                                 C.POINTER(C.c_uint64)]
+        L.eslam_gpu_trajectory_smoothed.argtypes = [vp, C.POINTER(A.TrajectoryEstimate), C.c_uint64, C.POINTER(C.c_uint64)]
     L.eslam_gpu_get_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_set_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_get_ancestors.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64]
@@ -420,6 +431,12 @@ class GpuFilter:
         self._check(self.L.eslam_gpu_sync(self.h, C.byref(info)))
         return info
 
+    def set_min_effective(self, min_effective):
+        """eslam_gpu_set_min_effective: Configuration::minEffective from the next update on (0: no
+        update resamples; above the particle count: every update does)."""
+        self._check(self.L.eslam_gpu_set_min_effective(self.h, min_effective))
+        self.cfg.min_effective = min_effective
+
     def debug_set_spin_limit(self, polls):
         """Testing only: polls of K3's cross-block waits before they give up (0: at once)."""
         self._check(self.L.eslam_gpu_debug_set_spin_limit(self.h, polls))
@@ -552,6 +569,52 @@ class GpuFilter:
             e.info = info
             raise
         return info, rinfo
+
+    # -- the trajectory log ------------------------------------------------------
+    def trajectory_enable(self, capacity_steps, max_particles=0):
+        """eslam_gpu_trajectory_enable: from now on every step and update ends with a record of
+        the particles' poses and ancestry in a ring of capacity_steps entries on the device, each
+        with room for max_particles (0: the filter's capacity) particles."""
+        self._check(self.L.eslam_gpu_trajectory_enable(self.h, capacity_steps, max_particles))
+
+    def trajectory_disable(self):
+        """eslam_gpu_trajectory_disable: frees the log"""
+        self._check(self.L.eslam_gpu_trajectory_disable(self.h))
+
+    def trajectory_clear(self):
+        """eslam_gpu_trajectory_clear: empties the log, which stays enabled"""
+        self._check(self.L.eslam_gpu_trajectory_clear(self.h))
+
+    def trajectory_info(self):
+        info = A.TrajectoryInfo()
+        self._check(self.L.eslam_gpu_trajectory_info(self.h, C.byref(info)))
+        return info
+
+    TRAJECTORY_NODE = np.dtype([("step", "<u8"), ("slot", "<u4"), ("particles", "<u4"), ("x", "<f8"), ("y", "<f8"), ("z", "<f8"),
+                                ("yaw", "<f8"), ("zsigma", "<f8")])
+
+    def trajectories(self, indices, capacity=None):
+        """eslam_gpu_get_trajectories: the lineages of the current particles `indices` through the
+        newest min(entries held, capacity) entries (capacity None: all held).  Returns a structured
+        array (len(indices), steps) of TRAJECTORY_NODE, oldest entry first."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        cap = self.trajectory_info().entries if capacity is None else int(capacity)
+        assert C.sizeof(A.TrajectoryPose) == self.TRAJECTORY_NODE.itemsize
+        out = np.zeros((len(idx), max(cap, 1)), dtype=self.TRAJECTORY_NODE)
+        steps = C.c_uint64()
+        self._check(self.L.eslam_gpu_get_trajectories(self.h, idx.ctypes.data_as(C.POINTER(C.c_uint64)), len(idx),
+                                                      out.ctypes.data_as(C.POINTER(A.TrajectoryPose)), cap, C.byref(steps)))
+        return out[:, :steps.value] if cap else out[:, :0]
+
+    def trajectory_smoothed(self, capacity=None):
+        """eslam_gpu_trajectory_smoothed: per held entry (the newest `capacity`; None: all), oldest
+        first, the pose moments of the current particles' ancestors in it under the current weights
+        and the number of distinct ancestors.  Returns a list of TrajectoryEstimate."""
+        cap = self.trajectory_info().entries if capacity is None else int(capacity)
+        out = (A.TrajectoryEstimate * max(cap, 1))()
+        entries = C.c_uint64()
+        self._check(self.L.eslam_gpu_trajectory_smoothed(self.h, out, cap, C.byref(entries)))
+        return [out[k] for k in range(entries.value)]
 
     def ancestors(self):
         n = self.count()
