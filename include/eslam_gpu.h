@@ -785,8 +785,48 @@ int eslam_gpu_pose_moments(eslam_ctx* ctx, const eslam_pose_gate* gate /* may be
  *            calls do not touch it.
  * While the log is enabled the filter keeps ancestors as with ESLAM_FLAG_RECORD_ANCESTORS.  The
  * filter itself -- particles, weights, RNG, maps -- is bit for bit what it is without the log.
- * Sharded filters: eslam_gpu_trajectory_enable is ESLAM_ERR_UNSUPPORTED, and so is
- * eslam_gpu_set_comm* on a context whose log is enabled (a sharded log needs a per-entry exchange).
+ *
+ * Sharded filters keep the log through eslam_gpu_trajectory_enable_sharded, called after
+ * eslam_gpu_set_comm* like the other *_sharded calls.  Plain eslam_gpu_trajectory_enable on a
+ * sharded filter is ESLAM_ERR_UNSUPPORTED, and so is eslam_gpu_set_comm* on a context whose log
+ * is enabled.  On a context that is not sharded the _sharded call is the plain one.
+ *   enable   a collective in SPMD order; every rank passes the same capacity_steps.
+ *            max_particles is per rank: the slots of this rank's part of an entry (0: the rank's
+ *            particle capacity).  The ranks agree in one small all_gather before anything
+ *            changes: a rank that cannot enable (its arguments, no memory) returns its own code
+ *            and the others ESLAM_ERR_COMM; differing capacity_steps are ESLAM_ERR_INVALID_ARG on
+ *            every rank.  capacity_steps == 0 is refused before the collective.
+ *   contract the ranks' entries, in rank order, are slot for slot the entries of one context
+ *            that holds all n_global particles and took the same calls.  parent and link hold
+ *            GLOBAL slots: indices into the previous held entry / the newest entry in the layout
+ *            (shard table) that entry was recorded under; n_global <= 2^30 - 64 fits the uint32.
+ *            Per entry the host keeps the shard table (nranks + 1 bounds), the global count and
+ *            the step id, identical on every rank.
+ *   record   as on one GPU, at the end of every eslam_gpu_step / eslam_gpu_update; the update's
+ *            deferred exchange is settled first, then the gather is materialised, then the
+ *            record kernel runs.  While the link is the identity (since the last record) the
+ *            parents are the ancestors themselves (old global indices) and the record adds no
+ *            collective; after a resample outside the step, link[anc[i]] is fetched from its owner.
+ *   resample eslam_gpu_resample_*_sharded (and the sharded eslam_gpu_resample, _resample_kld)
+ *            compose the link across the ranks, from the old shard table to the new one.  One
+ *            that would give any rank more than that rank's max_particles is
+ *            ESLAM_ERR_INVALID_ARG on every rank with nothing changed: for the stratified call
+ *            before any collective (the shards follow from eslam_gpu_shard_bounds(samples)), for
+ *            the multinomial call where it learns n_after.
+ *   calls    disable and info are local; clear, eslam_gpu_get_trajectories and
+ *            eslam_gpu_trajectory_smoothed are collectives.  info: entries, first_step, last_step
+ *            and capacity_steps as on one GPU, particles the newest entry's GLOBAL count,
+ *            max_particles and bytes this rank's.
+ *   queries  get_trajectories: every rank passes the same list of GLOBAL particle indices and
+ *            the same capacity, and receives the whole result; slot is the global slot and
+ *            particles the entry's global count, so the result is byte for byte the one
+ *            context's.  An index >= n_global, like every argument error, is refused before the
+ *            first collective; lists that differ between the ranks (count or capacity, then
+ *            contents, compared by all_gather) are ESLAM_ERR_INVALID_ARG on every rank.
+ *            trajectory_smoothed: every rank receives, per held entry, the one context's
+ *            estimate bit for bit; distinct_ancestors is the sum of the owners' marked slots.
+ *   failures a rank that fails inside a query or a composition (scratch memory) says so in the
+ *            counts the exchange gathers: it returns its code, the others ESLAM_ERR_COMM, none waits.
  *
  * eslam_gpu_get_trajectories: for each current particle indices[k] (< the particle count, repeats
  * allowed) its lineage: from link[index] in the newest entry along parent back through the
@@ -816,6 +856,7 @@ typedef struct eslam_trajectory_info {
 typedef struct eslam_trajectory_pose { uint64_t step; uint32_t slot, particles; double x, y, z, yaw, zsigma; } eslam_trajectory_pose;
 typedef struct eslam_trajectory_estimate { uint64_t step; uint64_t distinct_ancestors; eslam_pose_moments moments; } eslam_trajectory_estimate;
 int eslam_gpu_trajectory_enable(eslam_ctx* ctx, uint32_t capacity_steps, uint64_t max_particles /* 0: the context's capacity */);
+int eslam_gpu_trajectory_enable_sharded(eslam_ctx* ctx, uint32_t capacity_steps, uint64_t max_particles /* per rank; 0: the rank's capacity */);
 int eslam_gpu_trajectory_disable(eslam_ctx* ctx);
 int eslam_gpu_trajectory_clear(eslam_ctx* ctx);
 int eslam_gpu_trajectory_info(eslam_ctx* ctx, eslam_trajectory_info* info);

@@ -1162,10 +1162,17 @@ public:
     // and every step of EmbodiedSlamFilter::update ends with a record on the device of the
     // particles' poses and ancestry, in a ring of `steps` entries of up to maxParticles particles
     // (0: the filter's capacity), 44 bytes per particle and entry.
+    // A sharded estimator keeps the log too (eslam_gpu_trajectory_enable_sharded): the call is
+    // then a collective, maxParticles is this rank's, and clearTrajectory(), trajectory() and
+    // smoothedTrajectory() are collectives that give every rank the one-GPU answer.  The index
+    // trajectory(i) takes is global there, which is what getBestParticleIndex() returns.
     void enableTrajectory(uint32_t steps, uint64_t maxParticles = 0)
     {
         flush();
-        check(ctx_, eslam_gpu_trajectory_enable(ctx_, steps, maxParticles));
+        if (sharded())
+            check(ctx_, eslam_gpu_trajectory_enable_sharded(ctx_, steps, maxParticles));
+        else
+            check(ctx_, eslam_gpu_trajectory_enable(ctx_, steps, maxParticles));
     }
     void disableTrajectory() { check(ctx_, eslam_gpu_trajectory_disable(ctx_)); }
     void clearTrajectory() { check(ctx_, eslam_gpu_trajectory_clear(ctx_)); }

@@ -107,7 +107,8 @@ def build_facade_test(verbose=True, name="test_facade"):
     """g++ a C++ façade test (include/eslam_gpu.hpp over the C ABI) against the library:
     tests/cpp/<name>.cpp -> tests/cpp/_build/<name> (test_facade, test_facade_shared_map,
     test_snapshot_facade, test_snapshot_facade_file, test_facade_scan, test_facade_resample,
-    test_facade_resample_sharded, test_facade_particle_grid, test_facade_gmm, test_facade_kld, test_facade_moments, test_facade_trajectory)."""
+    test_facade_resample_sharded, test_facade_particle_grid, test_facade_gmm, test_facade_kld, test_facade_moments, test_facade_trajectory,
+    test_facade_trajectory_sharded)."""
     src = os.path.join(os.path.dirname(FACADE_SRC), name + ".cpp")
     exe = os.path.join(os.path.dirname(FACADE_BIN), name)
     deps = [src, LIB, os.path.join(ROOT, "include", "eslam_gpu.hpp"), os.path.join(ROOT, "include", "eslam_gpu.h")]

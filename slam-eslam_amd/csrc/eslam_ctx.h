@@ -94,6 +94,15 @@ struct TrajectoryLog {
     uint32_t head = 0, held = 0;             // the ring entry the next record writes, the entries held
     uint64_t next_step = 0;                  // records since enable: the next entry's step id
     Dev<char> scratch;                       // the queries' scratch, kept between calls
+    // The log of a sharded filter (eslam_gpu_trajectory_enable_sharded): max_particles, count and
+    // link_n are this rank's, parent and link hold global slots.  Identical on every rank:
+    bool sharded = false;
+    std::vector<uint64_t> gcount;            // per ring entry: its global count
+    std::vector<std::vector<uint64_t>> table;   // ... and the shard table it was recorded under (nranks + 1 bounds)
+    std::vector<uint64_t> link_table;        // the table link[cur] is indexed under: the filter's at the last record or composition
+    std::vector<uint64_t> max_all;           // every rank's max_particles
+    bool link_identity = false;              // link[cur][i] == first + i: set by a record, cleared by a composition
+    Dev<char> xa, xb;                        // the exchange's scratch: by the requests made; by those received and answered
     // the ring index of the j-th newest held entry (j < held)
     uint32_t at(uint32_t j) const { return (head + capacity - 1u - j) % capacity; }
 };
@@ -328,6 +337,9 @@ int trajectory_record(eslam_ctx* ctx, bool updated);
 int trajectory_compose(eslam_ctx* ctx);
 // a new particle set: the log is emptied, the link the identity over the filter's n
 int trajectory_reset(eslam_ctx* ctx);
+// a sharded filter about to be resampled to the shard table nb[0 .. nranks]: false where the log
+// of some rank (eslam_gpu_trajectory_enable_sharded) has no room for its new shard; the same on every rank
+bool trajectory_holds(const eslam_ctx* ctx, const uint64_t* nb);
 
 // ---- eslam_host_comm.hip
 int comm_allgather(eslam_ctx* ctx, const void* dsend, void* drecv, uint64_t bytes);

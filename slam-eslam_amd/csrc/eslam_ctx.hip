@@ -2079,7 +2079,8 @@ int eslam_host::resample_to(eslam_ctx* ctx, uint64_t samples, bool multi, eslam_
     // the shard boundaries are fixed by set_comm; refused before any collective (settle is one)
     if (ctx->sharded && (multi || samples != ctx->n_global))
         return fail(ctx, ESLAM_ERR_UNSUPPORTED, "resample: a sharded filter resamples to its own count only (stratified)");
-    if (ctx->traj.on && samples > ctx->traj.max_particles)
+    // (a sharded filter's log counts per rank, and a resample here keeps every shard's size)
+    if (ctx->traj.on && !ctx->traj.sharded && samples > ctx->traj.max_particles)
         return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample: samples may not exceed the trajectory log's max_particles");
     if (const int rc_ = settle(ctx)) return rc_;
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
@@ -2204,6 +2205,9 @@ int eslam_host::resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, e
     uint64_t nb[kMaxRanks + 1] = {};
     if (!multi && eslam_gpu_shard_bounds(samples, G, ctx->cfg.sum_chunk_rows, nb) != ESLAM_OK)
         return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample_sharded: samples cannot be split into nranks chunk-aligned shards");
+    // the trajectory log: the stratified call's new shards are known from the arguments
+    if (!multi && !trajectory_holds(ctx, nb))
+        return fail(ctx, ESLAM_ERR_INVALID_ARG, "resample_sharded: a rank's new shard would exceed its trajectory log's max_particles");
     if (const int rc_ = settle(ctx)) return rc_;
     if (!ctx->n) return fail(ctx, ESLAM_ERR_NOT_INITIALISED, "no particles");
     if (check_poisoned(ctx)) return ESLAM_ERR_HIP;
@@ -2272,6 +2276,10 @@ int eslam_host::resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, e
         if (n_after == 0 || eslam_gpu_shard_bounds(n_after, G, ctx->cfg.sum_chunk_rows, nb) != ESLAM_OK)
             return fail(ctx, ESLAM_ERR_INVALID_ARG,
                         "resample_sharded: the kept draws cannot be split into nranks chunk-aligned shards (nothing changed)");
+        // every rank counted the same draws: all of them stop here
+        if (!trajectory_holds(ctx, nb))
+            return fail(ctx, ESLAM_ERR_INVALID_ARG,
+                        "resample_sharded: a rank's new shard would exceed its trajectory log's max_particles (nothing changed)");
     }
     for (int d = 0; d <= G; ++d) pl.nb[d] = nb[d];
     // the records this rank sends to every rank
@@ -2358,7 +2366,9 @@ int eslam_host::resample_sharded(eslam_ctx* ctx, uint64_t samples, bool multi, e
         if (multi) info->dropped = beyond;
         else info->overruns = beyond;
     }
-    return ESLAM_OK;
+    // the trajectory log: the route and the expand wrote the outputs' ancestors (old global
+    // indices); the link follows them across the ranks, from the old table to the new one
+    return ctx->traj.on ? trajectory_compose(ctx) : ESLAM_OK;
 }
 
 extern "C" int eslam_gpu_resample_stratified_sharded(eslam_ctx* ctx, uint64_t samples, eslam_resample_info* info)

@@ -737,4 +737,27 @@ struct TrajNode {
 // a slot outside its entry: a walk that meets one ends there (a sound log holds none)
 constexpr uint32_t kTrajNone = 0xffffffffu;
 
+// The log of a sharded filter (eslam_gpu_trajectory_enable_sharded).  Slots are global: rank r
+// holds the slots [b[r], b[r + 1]) of an entry recorded under the shard table b.  "Items of entry
+// E by global slot" is one exchange (traj_fetch, eslam_host_trajectory.hip) with two kinds of
+// item: a 4-byte word (a link) or a node, the slot's five values and its parent.
+struct TrajTable {
+    uint32_t b[kMaxRanks + 1];
+    uint32_t G, me;
+};
+struct alignas(16) TrajItem {            // 48 bytes: three 16-byte accesses
+    double x, y, z, yaw, zs;
+    uint32_t parent, pad;
+};
+// what this rank serves: its part [first, first + count) of the entry (nodes), or of a word array
+struct TrajSrc {
+    const uint32_t* word;                // word items: word[slot - first]; null for node items
+    TrajEntry e;
+    uint64_t* bits;                      // the smoothed sweep: the bitmap over this rank's part (bit slot - first), or null
+    uint32_t first, count;
+};
+constexpr int kTrajBucketBlocks = 1024;      // blocks of the bucketing kernels at most (each a contiguous range of requests)
+// the bucketing's totals: [0, kMaxRanks) requests per owner, then kMaxRanks + 1 exclusive offsets
+constexpr int kTrajTotWords = 2 * kMaxRanks + 1;
+
 }  // namespace eslam_dev

@@ -103,6 +103,22 @@ hipError_t eslam_launch_traj_compose(const uint32_t* anc, const uint32_t* link, 
 hipError_t eslam_launch_traj_trace(const uint32_t* leaf, uint64_t count, const uint32_t* link, uint64_t nlink, const TrajLevel* lv,
                                    uint32_t steps, TrajNode* out, hipStream_t stream);
 hipError_t eslam_launch_traj_level(uint64_t n, const TrajLevel* L, uint32_t* a, DevState out, uint64_t* bits, hipStream_t stream);
+// ... on a sharded filter: the exchange's kernels (bucket, serve, scatter) and its users'
+hipError_t eslam_launch_traj_iota_from(uint32_t* link, uint64_t n, uint32_t first, hipStream_t stream);
+void eslam_traj_bucket_shape(uint64_t count, uint32_t* nblocks, uint64_t* per);
+hipError_t eslam_launch_traj_bucket(const uint32_t* slots, uint64_t count, const TrajTable* T, uint32_t* cnt, uint32_t* tot,
+                                    uint32_t* req, uint32_t* pos, hipStream_t stream);
+hipError_t eslam_launch_traj_serve(int node, const uint32_t* slots, uint64_t n, int own_only, const TrajTable* T, const TrajSrc* src,
+                                   void* out, hipStream_t stream);
+hipError_t eslam_launch_traj_scatter(int node, const void* in, const uint32_t* pos, uint64_t n, void* out, hipStream_t stream);
+hipError_t eslam_launch_traj_sources(const Ctl* ctl, int updated, const uint32_t* anc, uint32_t first, uint64_t n, uint32_t* out,
+                                     hipStream_t stream);
+hipError_t eslam_launch_traj_record_sharded(DevState s0, DevState s1, const Ctl* ctl, uint64_t n, int updated, const uint32_t* anc,
+                                            const uint32_t* pre, uint32_t first, uint32_t* link_next, const TrajEntry* e,
+                                            hipStream_t stream);
+hipError_t eslam_launch_traj_trace_take(const TrajItem* items, uint64_t count, uint32_t gcount, uint32_t* a, uint32_t steps, uint32_t j,
+                                        TrajNode* out, hipStream_t stream);
+hipError_t eslam_launch_traj_level_take(const TrajItem* items, uint64_t n, uint32_t* a, DevState out, hipStream_t stream);
 
 // ---- eslam_resample.hip (resample to a count: the cumulative sum, the draws' searches, the gather)
 uint64_t eslam_resample_tiles(uint64_t items);

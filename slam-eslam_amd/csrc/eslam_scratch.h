@@ -148,6 +148,56 @@ inline void carve_traj_smooth(Carver& c, uint64_t n, uint64_t slots, TrajSmoothS
     carve_kld(c, (slots + 63) / 64, 0, &s->k);
 }
 
+// The log of a sharded filter.  The exchange's scratch by the requests a rank makes (`count`
+// positions bucketed by `nblocks` blocks): the packed requests, their positions, the blocks'
+// counts and the totals ...
+struct TrajFetchOut {
+    uint32_t *req, *pos, *cnt, *tot;
+};
+inline void carve_traj_fetch_out(Carver& c, uint64_t count, uint64_t nblocks, TrajFetchOut* s)
+{
+    s->req = c.take<uint32_t>(count);
+    s->pos = c.take<uint32_t>(count);
+    s->cnt = c.take<uint32_t>(nblocks * eslam_dev::kMaxRanks);
+    s->tot = c.take<uint32_t>(eslam_dev::kTrajTotWords);
+}
+// ... and by the `tin` requests received and the `tout` answers awaited, of `item` bytes each
+struct TrajFetchIn {
+    uint32_t* reqin;
+    void *served, *answers;
+};
+inline void carve_traj_fetch_in(Carver& c, uint64_t tin, uint64_t tout, uint64_t item, TrajFetchIn* s)
+{
+    s->reqin = c.take<uint32_t>(tin);
+    s->served = c.take_bytes(tin * item);
+    s->answers = c.take_bytes(tout * item);
+}
+// a sharded trace of `count` leaves through `steps` entries: the leaves, their slots in the level
+// at hand, the level's items, the nodes; `all`: every rank's leaves, compared before the walk
+struct TrajTraceSharded {
+    uint32_t *leaf, *a, *all;
+    eslam_dev::TrajItem* items;
+    eslam_dev::TrajNode* nodes;
+};
+inline void carve_traj_trace_sharded(Carver& c, uint64_t count, uint64_t steps, uint64_t nranks, TrajTraceSharded* s)
+{
+    s->leaf = c.take<uint32_t>(count);
+    s->a = c.take<uint32_t>(count);
+    s->all = c.take<uint32_t>(count * nranks);
+    s->items = c.take<eslam_dev::TrajItem>(count);
+    s->nodes = c.take<eslam_dev::TrajNode>(count * steps);
+}
+// a record or a composition through a link that is not the identity: the n particles' sources
+// and the words fetched for them
+struct TrajLinkScratch {
+    uint32_t *src, *got;
+};
+inline void carve_traj_link(Carver& c, uint64_t n, TrajLinkScratch* s)
+{
+    s->src = c.take<uint32_t>(n);
+    s->got = c.take<uint32_t>(n);
+}
+
 // a particle-grid composition on tx x ty tiles with `blocks` blocks of cells
 inline void carve_pgrid(Carver& c, uint64_t tx, uint64_t ty, uint64_t blocks, eslam_dev::PgScratch* s)
 {

@@ -414,7 +414,9 @@ class KldInfo(C.Structure):
 
 
 class TrajectoryInfo(C.Structure):
-    """eslam_trajectory_info (include/eslam_gpu.h)."""
+    """eslam_trajectory_info (include/eslam_gpu.h).  On a sharded filter's log
+    (eslam_gpu_trajectory_enable_sharded) `particles` is the newest entry's global count, while
+    `max_particles` and `bytes` are this rank's."""
     _fields_ = [
         ("enabled", C.c_uint32),
         ("capacity_steps", C.c_uint32),

@@ -138,6 +138,8 @@ def load_library(path=LIB_PATH):
         L.eslam_gpu_get_trajectories.argtypes = [vp, C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(A.TrajectoryPose), C.c_uint64,
                                                  C.POINTER(C.c_uint64)]
         L.eslam_gpu_trajectory_smoothed.argtypes = [vp, C.POINTER(A.TrajectoryEstimate), C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(L, "eslam_gpu_trajectory_enable_sharded"):
+        L.eslam_gpu_trajectory_enable_sharded.argtypes = [vp, C.c_uint32, C.c_uint64]
     L.eslam_gpu_get_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_set_rng_state.argtypes = [vp, C.POINTER(A.RngState)]
     L.eslam_gpu_get_ancestors.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint64]
@@ -576,6 +578,14 @@ class GpuFilter:
         the particles' poses and ancestry in a ring of capacity_steps entries on the device, each
         with room for max_particles (0: the filter's capacity) particles."""
         self._check(self.L.eslam_gpu_trajectory_enable(self.h, capacity_steps, max_particles))
+
+    def trajectory_enable_sharded(self, capacity_steps, max_particles=0):
+        """eslam_gpu_trajectory_enable_sharded: the log of a sharded filter, a collective called by
+        every rank with the same capacity_steps after the communicator is set.  max_particles is
+        per rank (0: the rank's capacity).  From then on trajectories() takes global particle
+        indices and, like trajectory_smoothed(), returns on every rank what one filter holding all
+        the particles returns.  On a filter that is not sharded: trajectory_enable."""
+        self._check(self.L.eslam_gpu_trajectory_enable_sharded(self.h, capacity_steps, max_particles))
 
     def trajectory_disable(self):
         """eslam_gpu_trajectory_disable: frees the log"""

@@ -159,6 +159,12 @@ class ShardedGpuFilter:
         """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
         return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
 
+    def trajectory_enable(self, capacity_steps, max_particles=0):
+        """the trajectory log of the sharded filter (eslam_gpu_trajectory_enable_sharded, a
+        collective): max_particles is this rank's; the queries then take global indices and
+        return the one-GPU answer on every rank"""
+        return self.f.trajectory_enable_sharded(capacity_steps, max_particles)
+
     def kld_count(self, **params):
         """eslam_gpu_kld_count on the sharded filter (a collective): the one-GPU KldInfo on every rank"""
         return self.f.kld_count(**params)
@@ -216,6 +222,12 @@ class RcclShardedGpuFilter:
     def resample_multinomial_sharded(self, samples):
         """resample_multinomial(samples) on the sharded filter (see resample_stratified_sharded)"""
         return _resample_sharded(self, self.f.resample_multinomial_sharded, samples)
+
+    def trajectory_enable(self, capacity_steps, max_particles=0):
+        """the trajectory log of the sharded filter (eslam_gpu_trajectory_enable_sharded, a
+        collective): max_particles is this rank's; the queries then take global indices and
+        return the one-GPU answer on every rank"""
+        return self.f.trajectory_enable_sharded(capacity_steps, max_particles)
 
     def kld_count(self, **params):
         """eslam_gpu_kld_count on the sharded filter (a collective): the one-GPU KldInfo on every rank"""
