@@ -1835,14 +1835,17 @@ DM_FN uint32_t dm_store_hash(uint32_t cell) { return (cell * 2654435761u) >> 27;
  * in one generation (power-of-two rows left 8192 chunks, 1.6 generations: the second 60 %
  * full); 2M: 7 rows; up to 327 680 particles one row.  Measured (interleaved A/B,
  * profiles/r05/ab_chunk_rows.log): K1 167 -> 160 us at 4M, 96 -> 91 us at 2M.  Part of the sum
- * contract (the oracle uses the same function); ESLAM_CHUNK_CAP also bounds the packed wave
- * counts (64 J ESLAM_MAX_CONTACTS < 2^16).                                                 */
+ * contract (the oracle uses the same function).  ESLAM_SUM_CHUNK_ROWS_MAX: the most rows
+ * eslam_config::sum_chunk_rows may set; it bounds the weighting kernel's packed wave counts
+ * (64 J ESLAM_MAX_CONTACTS < 2^16), and no default exceeds it.  eslam_gpu_create's error text
+ * (eslam_ctx.hip) and eslam_config::sum_chunk_rows in eslam_gpu.h name its value.            */
 #ifndef ESLAM_CHUNK_WAVES                /* experiment builds only (changes the sum order) */
 #define ESLAM_CHUNK_WAVES 5120u
 #endif
 #ifndef ESLAM_CHUNK_CAP
 #define ESLAM_CHUNK_CAP 13u
 #endif
+#define ESLAM_SUM_CHUNK_ROWS_MAX 31u
 DM_FN uint32_t dm_chunk_rows(uint64_t n_global)
 {
     const uint64_t rows = (n_global + 63) / 64, per = (uint64_t)ESLAM_CHUNK_WAVES * ESLAM_CHUNK_CAP;

@@ -5,13 +5,13 @@
 
 The library is the product: HIP kernels + the C ABI of include/eslam_gpu.h.
 -ffp-contract=off keeps device and host arithmetic bit-identical to the CPU oracle.
-Machine-LICM is disabled for the kernels' translation unit only: it hoists the ~150 fp64
-polynomial constants of the contact model out of the particle loop and drives
-k_project_weight to 256 VGPRs / occupancy 1.
+Machine-LICM is disabled for the step kernels' translation units only (PER_SOURCE): in
+eslam_kernels.hip it hoists the ~150 fp64 polynomial constants of the contact model out of the
+particle loop and drives k_project_weight to 256 VGPRs / occupancy 1.
 
-Provenance: the SHA-256 of every source, of every header they include (HEADERS: the five in
+Provenance: the SHA-256 of every source, of every header they include (HEADERS: the seven in
 csrc/ -- device-visible layouts, launcher declarations, buffer owners, scratch layouts, the host
-side's context -- and the two public ones)
+side's context, the wave primitives, the diagnostic stamps -- and the two public ones)
 and of every flag is compiled into the library (eslam_gpu_build_id()).  A build is skipped only when the existing library reports the hash
 of the current sources, so a run never loads a binary that was not built from them
 (tests/test_abi.py checks the shipped library the same way).
@@ -30,15 +30,21 @@ LIB = os.path.join(OUT_DIR, "libeslam_gpu.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ESLAM_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["eslam_kernels.hip", "eslam_resample.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_snapshot.hip",
+SOURCES = ["eslam_kernels.hip", "eslam_particle_maps.hip", "eslam_selftest.hip",
+           "eslam_resample.hip", "eslam_hash.hip", "eslam_shared_map.hip", "eslam_snapshot.hip",
            "eslam_scan.hip", "eslam_particle_grid.hip", "eslam_gmm.hip", "eslam_moments.hip", "eslam_kld.hip", "eslam_trajectory.hip", "eslam_ctx.hip", "eslam_host_comm.hip",
            "eslam_host_map.hip", "eslam_host_stats.hip", "eslam_host_trajectory.hip", "eslam_host_snapshot.hip"]
 HEADERS = [os.path.join(CSRC, "eslam_internal.h"), os.path.join(CSRC, "eslam_launch.h"), os.path.join(CSRC, "eslam_buf.h"),
            os.path.join(CSRC, "eslam_scratch.h"), os.path.join(CSRC, "eslam_ctx.h"),
+           os.path.join(CSRC, "eslam_wave.h"), os.path.join(CSRC, "eslam_stamps.h"),
            os.path.join(ROOT, "include", "eslam_gpu.h"), os.path.join(ROOT, "include", "eslam_detmath.h")]
 FLAGS = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-mfma", "-Wall", "-Wno-unused-result", "-Wno-unused-function", f"-I{os.path.join(ROOT, 'include')}"]
-PER_SOURCE = {"eslam_kernels.hip": ["-mllvm", "-disable-machine-licm"]}
+# Only eslam_kernels.hip (k_project_weight) is known to need the flag.  The other two were one
+# translation unit with it and have always been compiled this way: dropping it from any of them
+# is a separate, measured change.  tests/test_build_lists.py checks the keys against SOURCES.
+NO_LICM = ["-mllvm", "-disable-machine-licm"]
+PER_SOURCE = {"eslam_kernels.hip": NO_LICM, "eslam_particle_maps.hip": NO_LICM, "eslam_selftest.hip": NO_LICM}
 
 
 def source_hash(defines=(), extra=()):

@@ -283,7 +283,7 @@ extern "C" int eslam_gpu_create(const eslam_config* cfg, int device, eslam_ctx**
     int rc = ESLAM_OK;
     do {
         // nD <= 64 J and the contact points <= ESLAM_MAX_CONTACTS nD share one 32-bit word (K1)
-        if (cfg->sum_chunk_rows > 31) { rc = fail(ctx, ESLAM_ERR_INVALID_ARG, "sum_chunk_rows: at most 31"); break; }
+        if (cfg->sum_chunk_rows > ESLAM_SUM_CHUNK_ROWS_MAX) { rc = fail(ctx, ESLAM_ERR_INVALID_ARG, "sum_chunk_rows: at most 31"); break; }
         hipError_t e = hipSetDevice(device);
         if (e != hipSuccess) { ctx->err = std::string("hipSetDevice: ") + hipGetErrorString(e); rc = ESLAM_ERR_HIP; break; }
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { rc = fail(ctx, ESLAM_ERR_HIP, "stream"); break; }

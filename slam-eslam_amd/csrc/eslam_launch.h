@@ -1,5 +1,5 @@
 // eslam_launch.h -- every entry point the kernel files export to each other and to the host side
-// (eslam_ctx.hip and the eslam_host_*.hip files), declared once.  All seventeen .hip files include it, the defining one too: the
+// (eslam_ctx.hip and the eslam_host_*.hip files), declared once.  Every .hip file includes it, the defining one too: the
 // names have C linkage, so only a declaration the definition sees lets the compiler refuse a
 // parameter list that has drifted from what the callers pass.
 #pragma once
@@ -12,7 +12,7 @@ using namespace eslam_dev;
 
 extern "C" {
 
-// ---- eslam_kernels.hip
+// ---- eslam_kernels.hip (the kernels of an update: the K1 family, the one-block scan, the weight path)
 hipError_t eslam_launch_project_weight(int project, int weight, int maxp, DevState s0, DevState s1, const MapView* map,
                                        const StepParams* p, Ctl* ctl, Shard* shards, const GatherView* gv,
                                        const LocalMaps* store, hipStream_t stream, const ChunkSel* sel, double* bspill);
@@ -25,22 +25,6 @@ hipError_t eslam_launch_pack_records(DevState s0, DevState s1, const Ctl* ctl, u
 hipError_t eslam_launch_gather_records(const uint32_t* req, uint64_t nreq, uint64_t gbase, const DebugRec* d, double* items,
                                        hipStream_t stream);
 hipError_t eslam_launch_scan_excl(uint32_t* a, uint64_t m, hipStream_t stream);
-hipError_t eslam_launch_store_init(uint32_t* sid, const LocalMaps* lm, uint64_t n, uint64_t pool, hipStream_t stream);
-hipError_t eslam_launch_store_refs(SidRef sid, uint64_t n, uint64_t pool, const CowScratch* cs, const GatherView* gv,
-                                   uint32_t* tgen, hipStream_t stream);
-hipError_t eslam_launch_map_plan(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                 const MergeParams* mp, uint32_t* pgc, hipStream_t stream);
-hipError_t eslam_launch_map_match(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                  const MatchParams* mp, hipStream_t stream);
-hipError_t eslam_launch_map_merge(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
-                                  const MergeParams* mp, hipStream_t stream);
-hipError_t eslam_launch_store_receive(SidRef sid, Ctl* ctl, const LocalMaps* lm, const MergeParams* mp, uint64_t n,
-                                      const CowScratch* cs, const void* hdr, uint64_t nrecv, uint32_t* hoff, uint32_t* head,
-                                      const void* pay, uint32_t* pgc, hipStream_t stream);
-hipError_t eslam_launch_pay_hdr(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend, uint64_t gbase,
-                                const LocalMaps* lm, const PaySeg* seg, void* hdr, uint32_t* off, hipStream_t stream);
-hipError_t eslam_launch_pay_pack(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend, uint64_t gbase,
-                                 const LocalMaps* lm, const void* hdr, const uint32_t* off, void* pay, hipStream_t stream);
 hipError_t eslam_launch_weight_stats(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, Shard* shards,
                                      hipStream_t stream);
 hipError_t eslam_launch_finalize(Shard* recs, int nrec, Ctl* ctl, const FinParams* fp, hipStream_t stream);
@@ -63,14 +47,34 @@ hipError_t eslam_launch_expand(const void* recv, uint64_t nrecv, uint64_t W0, ui
 uint64_t eslam_record_bytes(void);
 hipError_t eslam_launch_init_gaussian(DevState s0, uint64_t n, uint64_t gbase, uint64_t seed, uint64_t ev, const double mu[3],
                                       const double sigma[3], double zpos, double zsigma, hipStream_t stream);
-hipError_t eslam_launch_selftest_math(int fn, const double* x, const double* y, double* out, uint64_t n, hipStream_t stream);
-hipError_t eslam_launch_selftest_bm_radius(unsigned long long* bad, hipStream_t stream);
 hipError_t eslam_launch_best_index(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint64_t* out2, hipStream_t stream);
 hipError_t eslam_launch_centroid_chunks(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* chunk_out,
                                         hipStream_t stream);
 hipError_t eslam_launch_centroid_tree(double* a, double* b, uint64_t m, double* out, hipStream_t stream);
 hipError_t eslam_launch_centroid(DevState s0, DevState s1, uint64_t n, uint32_t J, Ctl* ctl, double* tmp, double* out,
                                  hipStream_t stream);
+
+// ---- eslam_particle_maps.hip (per-particle maps: the stores, the page budget, plan / match / merge, the migrating maps)
+hipError_t eslam_launch_store_init(uint32_t* sid, const LocalMaps* lm, uint64_t n, uint64_t pool, hipStream_t stream);
+hipError_t eslam_launch_store_refs(SidRef sid, uint64_t n, uint64_t pool, const CowScratch* cs, const GatherView* gv,
+                                   uint32_t* tgen, hipStream_t stream);
+hipError_t eslam_launch_map_plan(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
+                                 const MergeParams* mp, uint32_t* pgc, hipStream_t stream);
+hipError_t eslam_launch_map_match(DevState s0, DevState s1, const Ctl* ctl, const MapView* map, const LocalMaps* lm,
+                                  const MatchParams* mp, hipStream_t stream);
+hipError_t eslam_launch_map_merge(DevState s0, DevState s1, Ctl* ctl, const MapView* map, const LocalMaps* lm,
+                                  const MergeParams* mp, hipStream_t stream);
+hipError_t eslam_launch_store_receive(SidRef sid, Ctl* ctl, const LocalMaps* lm, const MergeParams* mp, uint64_t n,
+                                      const CowScratch* cs, const void* hdr, uint64_t nrecv, uint32_t* hoff, uint32_t* head,
+                                      const void* pay, uint32_t* pgc, hipStream_t stream);
+hipError_t eslam_launch_pay_hdr(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend, uint64_t gbase,
+                                const LocalMaps* lm, const PaySeg* seg, void* hdr, uint32_t* off, hipStream_t stream);
+hipError_t eslam_launch_pay_pack(DevState s0, DevState s1, const Ctl* ctl, const void* send, uint64_t nsend, uint64_t gbase,
+                                 const LocalMaps* lm, const void* hdr, const uint32_t* off, void* pay, hipStream_t stream);
+
+// ---- eslam_selftest.hip
+hipError_t eslam_launch_selftest_math(int fn, const double* x, const double* y, double* out, uint64_t n, hipStream_t stream);
+hipError_t eslam_launch_selftest_bm_radius(unsigned long long* bad, hipStream_t stream);
 
 // ---- eslam_gmm.hip (the pose distribution's Gaussian mixture: pass B, a pass' chunk records, the tree)
 hipError_t eslam_launch_gmm_bounds(DevState s0, DevState s1, uint64_t n, Ctl* ctl, uint64_t* part, uint64_t* out,

@@ -1,7 +1,7 @@
 """Experiment builds for interleaved A/B (tools/ab_libs.sh): each variant is a library under
 slam-eslam_amd/lib/ab/ built from the current sources with extra defines / flags.
     python tools/build_variants.py name:-DFOO,-DBAR name2:+licm ...
-'+licm' drops -disable-machine-licm for the kernels' translation unit."""
+'+licm' drops -disable-machine-licm from every translation unit that has it (build_lib.PER_SOURCE)."""
 import os
 import sys
 from concurrent.futures import ProcessPoolExecutor
